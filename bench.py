@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
 """Headline benchmark: explicit linear-tet elastodynamics steps on synthetic cantilevers.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One *step* = one explicit time step of the whole mesh (per partition: the resident multi-step kernel, or one fused
 kernel per step; for N > 1 the forces of the shared nodes are summed across ranks every step - by direct xGMI peer
 stores inside the step kernel when that path proves itself in a child-process preflight, else by an RCCL all-reduce;
-with the peer exchange in use the RCCL variant is measured too and reported as `rccl_allreduce`).  N = 1 runs
-BASELINE.json configs[2] (the ~1M-tet beam, one partition); N > 1 keeps ~1M tets per GPU (weak scaling; N = 8 is
-configs[3], the ~8M-tet beam in 8 slabs; `sync_avoiding` = configs[4]).  Rank 0 prints ONE JSON line.
+with --full and the peer exchange in use the RCCL variant is measured too and reported as `rccl_allreduce`).  N = 1
+runs BASELINE.json configs[2] (the ~1M-tet beam, one partition); N > 1 keeps ~1M tets per GPU (weak scaling; N = 8 is
+configs[3], the ~8M-tet beam in 8 slabs; `sync_avoiding` = configs[4], with --full).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs W warm-up steps and one short untimed call of the timed route, times ONE call of exactly K
+steps (`ms_per_step` = its wall time / K, `value` = element-updates per second in it), writes the state those steps
+computed if --dump-outputs is given, and prints the line.  Everything else - the extra legs below - runs only with
+--full.
 
 The run has ONE deadline (`--budget-s`, counted from the start of the job) and every leg a budget inside it; the
 headline is measured first, and once it exists the line is printed no matter what the later legs do - a leg that does
 not fit is skipped, a leg that hangs is cut off by the watchdog, which prints the line with that leg marked and leaves
 with a non-zero status (`legs`, `leg_seconds`).
 
-Extra objects on the N = 1 line:
+Extra objects on the N = 1 line (--full):
   roofline      contract figure: algorithmic bytes/step (16*Ne + 216*Nn) / HIP-event time on the
                 kernel's own stream, against the 8 TB/s HBM peak of MI355X_MICROARCH.md - an EQUIVALENT bandwidth (what a
                 kernel re-reading the partition every step would have to sustain), over a region of >= 1 s (`sustained`)
@@ -62,6 +67,9 @@ N_FOR_GPUS = {1: 19, 2: 24, 3: 27, 4: 30, 5: 32, 6: 34, 7: 36, 8: 38}
 PROFILE_ROUNDS = ("r04", "r03")  # committed PMC summaries, newest first: profiles/<round>_pmc_summary.json / _onchip_summary.json
 PLAN_IDENTITY = ("n_blocks", "max_owned", "max_local", "n_elem_copies", "n_halo_total", "lds_bytes", "threads", "n_items",
                  "n_pairs", "n_by_construction")  # what makes two plans the same work for the same kernel
+PRIME_STEPS = 8  # untimed call before the timed one: the shortest call that takes the resident kernel (kPersistMinSteps)
+DUMP_LIMIT_BYTES = 60 << 20  # --dump-outputs: all files of all ranks together
+DUMP_SEED = 0  # --dump-outputs: seed of the fixed sample written when a state vector exceeds its share of the limit
 
 
 def test_hook(point):
@@ -233,6 +241,22 @@ def build_rank_solver(mesh, n_parts, rank, device, block_nodes=0, threads=0):
                                 dt, ALPHA, shared_local=lay.shared_local, shared_slots=lay.shared_slots,
                                 n_global_shared=len(gshared), device=device, block_nodes=block_nodes, threads=threads)
     return sol, lay, gshared, dt
+
+
+def dump_outputs(directory, part, rank, world):
+    """``--dump-outputs``: what a caller of the timed path receives after its last step - ``part.get_state()``, i.e. the
+    displacements d^n (``d0``) and d^(n-1) (``dn``) of this rank's nodes in its layout's order and the time ``tn`` - as
+    float64 ``.npy`` files (``<name>_rank<r>`` for N > 1).  A vector longer than its share of DUMP_LIMIT_BYTES is written
+    as the sorted fixed sample ``np.random.default_rng(DUMP_SEED).choice(size, share, replace=False)`` of its entries."""
+    d0, dn, tn = part.get_state()
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - (1 << 20)) // (2 * world * 8)  # float64 entries per vector (1 MiB left for tn, headers)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in (("d0", d0), ("dn", dn), ("tn", tn)):
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > share:
+            a = a.ravel()[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share, replace=False))]
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a)
 
 
 def measured_copy_bandwidth(device=0, n_bytes=1 << 30, reps=10):
@@ -1039,14 +1063,19 @@ def main():
     ap.add_argument("--preflight-limit-s", type=float, default=90.0, help=argparse.SUPPRESS)  # cap of the preflight child
     ap.add_argument("--rccl-leg-limit-s", type=float, default=90.0, help=argparse.SUPPRESS)   # cap of the RCCL leg
     ap.add_argument("--min-timed-ms", type=float, default=1000.0,
-                    help="the timed call of --steps steps is repeated until the timed region lasts at least this long; "
-                         "the legs of the N = 1 line time regions of the same length")
+                    help="--full: the legs time regions at least this long (the headline times exactly --steps steps)")
     ap.add_argument("--big-refine", type=int, default=38,
                     help="refinement n of the 8-GPU beam whose rank 3 of 8 / whole mesh the per_gpu_of_8 / cache_exceeding "
                          "legs of the N = 1 line step (38: BASELINE.json's 8.2M tets; smaller values are for tests)")
     ap.add_argument("--legs", default="all",
-                    help="N = 1: comma-separated extra legs to run (roofline, per_gpu_of_8, cache_exceeding, unstructured, "
-                         "predictor, cpu_baseline), or all / none")
+                    help="N = 1 with --full: comma-separated extra legs to run (roofline, per_gpu_of_8, cache_exceeding, "
+                         "unstructured, predictor, cpu_baseline), or all / none")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs that measure or check something else: N = 1 the extra "
+                         "legs (--legs), N > 1 the sync-avoiding leg and the RCCL all-reduce leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they computed (what get_state() returns: d0, dn, tn; "
+                         "one set per rank for N > 1) as float64 .npy files into DIR")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1101,9 +1130,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def build_and_time(how, synced_graph=None):
-        """Partition solver with the given transport, W warm-up and K timed steps; ``ok`` is False on any rank if a
-        wait inside a kernel gave up (peer exchange: a neighbour's values never arrived)."""
+    def build_and_time(how, synced_graph=None, repeat=False):
+        """Partition solver with the given transport, W warm-up steps and ONE timed call of K steps (``repeat``: the
+        timed call is repeated until the region lasts >= --min-timed-ms, the RCCL leg of --full); ``ok`` is False on
+        any rank if a wait inside a kernel gave up (peer exchange: a neighbour's values never arrived)."""
         part = PartitionedSolver(mesh.points, mesh.tets, mesh.triangles, epart, rank, world, E=E, nu=NU, rho=RHO,
                                  fz=FZ, alpha=ALPHA, gamma=GAMMA, device=local_rank, block_nodes=args.block_nodes,
                                  threads=args.threads, exchange=how)
@@ -1113,9 +1143,19 @@ def main():
             part.solver.set_option("synced_graph", synced_graph)  # saa_step_synced: replayed graphs / eager launches
         part.step_synced(args.warmup)  # world == 1: plain steps; else one exchange of shared-node forces per step
         # The timed call is `part.step_synced(args.steps)`.  Which kernels that runs depends on the call length (calls
-        # of >= 8 steps take the resident kernel), so exactly that call is issued once more untimed - the first launch
-        # of a kernel pays code-object upload - and its duration sizes the number of timed repetitions so that the
-        # timed region lasts >= --min-timed-ms.
+        # of >= 8 steps take the resident kernel), and the first launch of a kernel pays code-object upload: a short
+        # call of the same route (min(K, PRIME_STEPS) steps) runs untimed first, whatever W is.
+        if not repeat:
+            part.step_synced(min(args.steps, PRIME_STEPS))
+            fence()
+            t0 = time.perf_counter()
+            part.step_synced(args.steps)
+            fence()
+            elapsed = time.perf_counter() - t0
+            build_and_time.calls = 1
+            return part, *agree(part, elapsed)
+        # --full's RCCL leg: exactly the timed call is issued once more untimed, and its duration sizes the number of
+        # timed repetitions so that the timed region lasts >= --min-timed-ms
         fence()
         t0 = time.perf_counter()
         part.step_synced(args.steps)
@@ -1140,8 +1180,11 @@ def main():
             if total >= args.min_timed_ms * 1e-3 or attempt == 3:
                 break
             calls = int(min(np.ceil(1.15 * calls * args.min_timed_ms * 1e-3 / max(total, 1e-7)), 100000))
-        elapsed = total / calls  # per call of args.steps steps
         build_and_time.calls = calls
+        return part, *agree(part, total / calls)  # (per call of args.steps steps)
+
+    def agree(part, elapsed):
+        """(elapsed, ok) agreed by all ranks: the slowest rank's time; ok unless a bounded wait timed out somewhere."""
         ok = True
         try:
             part.solver.synchronize()  # raises if a bounded wait timed out
@@ -1154,7 +1197,7 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        return part, elapsed, ok
+        return elapsed, ok
 
     legs.end("setup")
     legs.begin("headline")
@@ -1169,6 +1212,8 @@ def main():
     if not ok:
         raise SystemExit("bench: a wait inside the step kernels timed out")
     sol, gshared, dt = part.solver, part.global_shared, part.dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, part, rank, world)
 
     stats = sol.plan_stats()
     out = {
@@ -1207,11 +1252,11 @@ def main():
             out[key] = value
 
     # N > 1: the same partitions in sync-avoiding mode (BASELINE.json configs[4]; Online_predictor.py:251-318).
-    rccl_wanted = (world > 1 and not args.no_rccl_leg and
+    rccl_wanted = (world > 1 and args.full and not args.no_rccl_leg and
                    ((part.exchange == "peer" and args.backend == "nccl" and not args.same_device) or
                     args.force_rccl_leg))
     rccl_reserve = 60.0 if rccl_wanted else 0.0
-    if world > 1 and not args.no_sync_avoiding:
+    if world > 1 and args.full and not args.no_sync_avoiding:
         # what the leg needs besides training: the recorded run, the predictor's capture, the windows (~20 s at N = 8)
         train_s = min(args.sa_train_seconds, legs.left() - rccl_reserve - 45.0)
         t = torch.tensor([train_s], dtype=torch.float64, device="cuda")
@@ -1224,7 +1269,7 @@ def main():
             put("sync_avoiding", sync_avoiding_leg(part, args, rank, world, ne_total, fence, train_s))
             legs.end("sync_avoiding")
 
-    if world == 1:
+    if world == 1 and args.full:
         single_gpu_legs(args, legs, put, sol, stats, n, ne_total, nn_total, local_rank)
     sol.close()  # (idempotent: the N = 1 legs have closed it already to make room for their own solvers)
     # N > 1: BASELINE.json configs[3] names the RCCL all-reduce as the per-step exchange.  When `value` above was
@@ -1253,7 +1298,8 @@ def main():
             res, ok_any = {}, False
             for route, env in (("eager", 0), ("graph", 1)):
                 try:
-                    part_r, elapsed_r, ok_r = build_and_time("rccl" if args.backend == "nccl" else "torch", synced_graph=env)
+                    part_r, elapsed_r, ok_r = build_and_time("rccl" if args.backend == "nccl" else "torch",
+                                                             synced_graph=env, repeat=True)
                     how = part_r.exchange
                     part_r.close()
                 except Exception as e:  # noqa: BLE001 - reported, never fatal for the headline line

@@ -83,3 +83,40 @@ def test_committed_counters_are_only_handed_out_for_the_profiled_plan():
     traffic, onchip, src, note = bench.committed_counters("resident19", other)
     assert traffic is None and onchip is None and "n_items" in note and "profile again" in note
     assert bench.committed_counters("resident7", stats) == (None, None, None, None)  # a mesh that was never profiled
+
+
+def test_dumped_outputs_stay_within_the_limit_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float64 state vectors as returned; vectors beyond their share of the limit (here 8 ranks of a big
+    partition) are written as the same seeded sample in every run, and all files together stay under 64 MB."""
+    import importlib
+
+    import numpy as np
+
+    sys.argv = ["bench.py"]
+    sys.path.insert(0, REPO)
+    bench = importlib.import_module("bench")
+
+    class Part:
+        def __init__(self, n_dof, seed):
+            rng = np.random.default_rng(seed)
+            self.state = (rng.normal(size=(n_dof, 1)), rng.normal(size=(n_dof, 1)), 0.25)
+
+        def get_state(self):
+            return self.state
+
+    small = Part(3000, 1)
+    bench.dump_outputs(str(tmp_path / "one"), small, 0, 1)
+    assert sorted(os.listdir(tmp_path / "one")) == ["d0.npy", "dn.npy", "tn.npy"]
+    assert np.array_equal(np.load(tmp_path / "one" / "d0.npy"), small.state[0])
+    assert np.load(tmp_path / "one" / "tn.npy").dtype == np.float64 and float(np.load(tmp_path / "one" / "tn.npy")) == 0.25
+    big = 3 * 200_000
+    for run in ("a", "b"):
+        for r in range(8):
+            bench.dump_outputs(str(tmp_path / run), Part(big, r), r, 8)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert len(names) == 24 and "d0_rank7.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64e6
+    d0 = np.load(tmp_path / "a" / "d0_rank3.npy")
+    assert d0.dtype == np.float64 and 0 < d0.size < big
+    assert np.array_equal(d0, np.load(tmp_path / "b" / "d0_rank3.npy"))
+    assert np.isin(d0, Part(big, 3).state[0]).all()  # entries of the vector, not anything computed from it

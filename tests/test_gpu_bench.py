@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +32,7 @@ def _run(*flags, timeout=900, extra_env=None, expect_rc=0):
 def test_two_ranks_launch_themselves_and_print_one_line():
     """N = 2 on the one-GPU box: both ranks share cuda:0, gloo process group (what --same-device is for)."""
     out = _run("--gpus", "2", "--same-device", "--backend", "gloo", "--refine", "4", "--steps", "40", "--warmup", "10",
-               "--sa-train-epochs", str(SA_EPOCHS), "--sa-truth-steps", "24000", "--min-timed-ms", "50")
+               "--sa-train-epochs", str(SA_EPOCHS), "--sa-truth-steps", "24000", "--min-timed-ms", "50", "--full")
     assert out["n_gpus"] == 2 and out["steps"] == 40 and out["warmup"] == 10 and out["timed_calls"] >= 1
     assert out["metric"] == "element_updates_per_s" and out["value"] > 0 and out["scaling"] == "weak"
     assert "2 x-slab" in out["config"]["workload"]
@@ -61,7 +62,7 @@ def test_line_survives_a_hung_preflight_and_a_stalled_rccl_leg():
     out = _run("--gpus", "2", "--same-device", "--backend", "gloo", "--refine", "4", "--steps", "40", "--warmup", "10",
                "--sa-train-epochs", "3", "--sa-truth-steps", "12000", "--budget-s", "240", "--force-preflight",
                "--force-rccl-leg", "--min-timed-ms", "50", "--preflight-limit-s", "20", "--rccl-leg-limit-s", "25",
-               expect_rc=3,
+               "--full", expect_rc=3,
                extra_env={"SAA_BENCH_HOOKS": "tests.bench_hooks", "SAA_BENCH_HOOK_PLAN": "preflight=hang,rccl_leg=hang"})
     wall = time.time() - t0
     assert wall < 240, wall
@@ -78,7 +79,7 @@ def test_headline_at_the_drivers_flags_is_warm():
     """The driver's own command (BENCH_r01.json: --steps 20 --warmup 5).  Round 1 timed a cold first cooperative
     launch there (33x below the kernel's rate); the timed call must run warm and agree with the kernel-level figure."""
     out = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--min-timed-ms", "200",
-               "--legs", "roofline,per_gpu_of_8,cache_exceeding,predictor", "--big-refine", "10")
+               "--legs", "roofline,per_gpu_of_8,cache_exceeding,predictor", "--big-refine", "10", "--full")
     roof = out["roofline"]
     assert roof["launches_timed"] >= 10 and 0.3 < roof["frac"] < 1.5
     assert roof["timed_region_ms"] >= 900 and roof["short_region"]["launches"] == 12   # sustained figure beside the short one
@@ -105,15 +106,38 @@ def test_headline_at_the_drivers_flags_is_warm():
     assert pred["max_difference_vs_pytorch_rocm_over_range"] < 1e-4, pred
     kernel_rate = 1028850 / (roof["us_per_step"] * 1e-6)
     assert out["value"] > kernel_rate / 1.5, (out["value"], kernel_rate)
-    assert out["timed_calls"] * out["steps"] * out["ms_per_step"] >= 45.0  # the timed region lasted >= ~50 ms
+    # the timed region is exactly the one call of --steps steps, and value / ms_per_step describe that call
+    assert out["timed_calls"] == 1 and out["steps"] == 20
+    assert abs(out["value"] - 1028850 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
 
 
 def test_a_short_budget_takes_the_small_cpu_sample_and_says_so():
     """With little of the budget left the CPU baseline falls back from the 1M-tet mesh (25 s of assembly) to the 150k-tet
     sample and names the reason; the line still carries headline, roofline and parity, status 0."""
-    out = _run("--gpus", "1", "--steps", "200", "--warmup", "20", "--budget-s", "75")
+    out = _run("--gpus", "1", "--steps", "200", "--warmup", "20", "--budget-s", "75", "--full")
     assert out["legs"]["headline"] == "done" and out["legs"]["roofline"] == "done"
     base = out["cpu_baseline"]
     assert "fallback" in base and "n=10" in base["sample"] and base["value"] > 0
     assert out["parity"]["rel_l2"] < 1e-10 and "n=10" in out["parity"]["mesh"]
     assert out["leg_seconds"]["total"] < 75
+
+
+def test_a_plain_run_times_exactly_its_steps_and_dumps_the_state(tmp_path):
+    """Without --full the run is set-up, warm-up, ONE timed call of --steps steps and the line; --dump-outputs writes the
+    state those steps computed (what get_state() hands a caller) as float64 .npy files."""
+    out = _run("--gpus", "1", "--steps", "300", "--warmup", "30", "--dump-outputs", str(tmp_path / "dump"))
+    assert out["legs"] == {"setup": "done", "headline": "done"}, out["legs"]
+    assert out["steps"] == 300 and out["warmup"] == 30 and out["timed_calls"] == 1
+    assert out["metric"] == "element_updates_per_s" and out["unit"] == "element-updates/s" and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True and out["ms_per_step"] > 0
+    assert abs(out["value"] - 1028850 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    for key in ("roofline", "per_gpu_of_8", "cache_exceeding", "unstructured", "predictor", "cpu_baseline", "parity"):
+        assert key not in out, key
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["d0.npy", "dn.npy", "tn.npy"], files
+    d0, dn, tn = (np.load(tmp_path / "dump" / f) for f in files)
+    n_dof = 3 * 476 * 20 * 20  # the n = 19 beam: (25n + 1)(n + 1)^2 nodes
+    assert d0.dtype == dn.dtype == tn.dtype == np.float64 and d0.shape == dn.shape == (n_dof, 1)
+    assert np.isfinite(d0).all() and np.isfinite(dn).all() and np.abs(d0).max() > 0 and not np.array_equal(d0, dn)
+    dt = float(out["config"]["workload"].rsplit("dt=", 1)[1])
+    assert abs(float(tn) / dt - (30 + 8 + 300)) < 1e-3 * 338  # warm-up + the untimed call of 8 steps + the timed steps

@@ -125,29 +125,20 @@ def test_shape_functions_and_quadrature_match_the_reference():
 
 
 def test_every_tools_name_the_reference_drivers_use_exists():
-    """the reference's four driver scripts run against this package's ``Tools``.  Reads the
-    reference's sources as text (build container only; skipped where /root/reference does not exist)."""
-    import ast
+    """the reference's four driver scripts run against this package's ``Tools``.  The names
+    they use and the ``Tools`` modules that define them were read from the reference's sources as text
+    (golden/tools_names.json, written by golden/make_golden_names.py)."""
     import importlib
+    import json
     import os
 
-    import pytest
+    from conftest import GOLDEN
 
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "Tools")):
-        pytest.skip("the reference is not present on this machine")
-    defined = {}
-    for f in os.listdir(os.path.join(ref, "Tools")):
-        if f.endswith(".py"):
-            with open(os.path.join(ref, "Tools", f)) as fh:
-                for node in ast.parse(fh.read()).body:
-                    if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
-                        defined.setdefault(node.name, []).append(f[:-3])
-    used = set()
-    for drv in ("Data_prepare.py", "Online_predictor.py", "Shared_extraction.py", "Model_training.py"):
-        with open(os.path.join(ref, drv)) as fh:
-            used |= {n.id for n in ast.walk(ast.parse(fh.read())) if isinstance(n, ast.Name) and n.id in defined}
+    with open(os.path.join(GOLDEN, "tools_names.json")) as fh:
+        rec = json.load(fh)
+    assert rec["drivers"] == ["Data_prepare.py", "Online_predictor.py", "Shared_extraction.py", "Model_training.py"]
+    used = rec["used"]
     assert len(used) >= 20
     for name in sorted(used):
-        mods = [importlib.import_module(f"synchronization_avoiding_algorithms_amd.Tools.{m}") for m in defined[name]]
+        mods = [importlib.import_module(f"synchronization_avoiding_algorithms_amd.Tools.{m}") for m in used[name]]
         assert any(hasattr(m, name) for m in mods), name

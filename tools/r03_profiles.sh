@@ -11,14 +11,14 @@ out=$root/gpurun_out/r03_final
 mkdir -p $out
 case "$1" in
 bench)
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_n1_driver_flags.json 2> $out/bench_n1_driver_flags.err
-  python bench.py > $out/bench_n1.json 2> $out/bench_n1.err
-  python bench.py --steps 200 --warmup 50 --refine 38 --no-cpu-baseline > $out/bench_n1_8Mtets.json 2> $out/bench_8m.err
-  python bench.py --mesh jittered --no-cpu-baseline > $out/bench_n1_jittered.json 2> $out/bench_jittered.err
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_n1_driver_flags.json 2> $out/bench_n1_driver_flags.err
+  python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err
+  python bench.py --full --steps 200 --warmup 50 --refine 38 --no-cpu-baseline > $out/bench_n1_8Mtets.json 2> $out/bench_8m.err
+  python bench.py --full --mesh jittered --no-cpu-baseline > $out/bench_n1_jittered.json 2> $out/bench_jittered.err
   python tools/unstructured_point.py > $out/unstructured_1M_tets.txt 2>&1
   ;;
 stats)
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $out/stats.log 2>&1; echo "rocprofv3 exit status $?" >> $out/stats.log)
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python3 $root/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $out/stats.log 2>&1; echo "rocprofv3 exit status $?" >> $out/stats.log)
   rocprofv3 -L 2>/dev/null | grep -i "F64\|FLOPS" > $out/counters_f64.txt
   ;;
 pmc19) tools/pmc_collect.sh r03_resident19 19 --warmup 1000 ;;

@@ -12,7 +12,7 @@ if [ "$1" = kernels ]; then
   echo "pytest rc=$rc" >> $out/tests.log
   exit $rc
 fi
-timeout -k 10 400 python bench.py > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
-timeout -k 10 1000 python bench.py --gpus 2 --same-device --backend gloo --refine 6 --steps 200 --warmup 50 --sa-train-epochs 0 \
+timeout -k 10 400 python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
+timeout -k 10 1000 python bench.py --full --gpus 2 --same-device --backend gloo --refine 6 --steps 200 --warmup 50 --sa-train-epochs 0 \
   --sa-train-seconds 800 --budget-s 950 > $out/bench_2ranks_full_schedule.json 2> $out/bench_2ranks_full_schedule.err
 echo "2-rank rc=$?" >> $out/bench_n1.err

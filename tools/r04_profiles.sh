@@ -13,13 +13,13 @@ out=$root/gpurun_out/r04
 mkdir -p $out
 case "$1" in
 bench)
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_n1_driver_flags.json 2> $out/bench_n1_driver_flags.err
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_n1_driver_flags.json 2> $out/bench_n1_driver_flags.err
   ;;
 bench_default)
-  python bench.py > $out/bench_n1.json 2> $out/bench_n1.err
+  python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err
   ;;
 stats)
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --legs roofline > $out/stats.log 2>&1; echo "rocprofv3 exit status $?" >> $out/stats.log)
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/stats -o run --output-format csv -- python3 $root/bench.py --full --gpus 1 --steps 20 --warmup 5 --legs roofline > $out/stats.log 2>&1; echo "rocprofv3 exit status $?" >> $out/stats.log)
   ;;
 pmc19) tools/pmc_collect.sh r04_resident19 19 --warmup 1000 ;;
 pmc38) tools/pmc_collect.sh r04_fused38 38 --steps 200 --warmup 50 --no-split-stepping ;;
