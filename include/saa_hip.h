@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -302,6 +302,40 @@ int saa_topology_get(const saa_topology *t, int32_t *elements, int32_t *nodes, i
                      int32_t *shared_local, int32_t *shared_slots, int32_t *global_shared, int32_t *dirichlet_nodes,
                      int32_t *dirichlet_local);
 int saa_topology_destroy(saa_topology *t);
+
+/*
+ * Modal analysis: stable time step and vibration modes of one whole mesh on one GPU.  The handle owns the mesh on the device
+ * in the caller's numbering (cells = global node ids, dof = 3*node + component) and is independent of the step plan.
+ *
+ * saa_operator_create: the mesh, the clamped dofs (`Dirichlet`, node_to_dof of Data_prepare.py:127-136) and the material
+ *   (lambda, mu of `elasticity`, commons.py:25-31; rho).  Stands for the matrix pair `M, K, _ = Global_Assembly(deg, Cells,
+ *   Points, Dirichlet, elas, t)` of Eigen_mode (Tools/Steady_solvers.py:25-27, Mat_construction.py:154-196) without the
+ *   matrices.  At most 2^29 elements.
+ * saa_operator_apply: KX and / or MX (either output may be NULL) for 1 <= m <= 16 column-major columns of 3*n_nodes dofs
+ *   (leading dimensions ldx, ldy >= 3*n_nodes), device buffers, in one launch pair per product.  K is the element stiffness
+ *   of Local_K_coronary (Mat_construction.py:79-119), M the consistent mass rho V/20 (1 + delta_ab) I_3 of Local_MKF
+ *   (Mat_construction.py:23-76, the 4-point rule of Qudrature.py:6-12 integrates it exactly).  Dirichlet rows and columns
+ *   are masked like Global_Assembly leaves them out (Mat_construction.py:176-192): inputs there are ignored, outputs there
+ *   are 0.  Bitwise repeatable (nodal sums in ascending element order, no floating-point atomics); enqueued on the
+ *   handle's stream.
+ * saa_operator_element_bound: omega_e = sqrt(lambda_max(K_e) / (rho |V_e| / 4)) of every element (omega_e_dev: n_elems
+ *   doubles, may be NULL), their maximum, its element and the number of elements whose signed volume (detJ / 6,
+ *   Mat_construction.py:93) is <= 0.  2 / omega_max bounds the stable step of the central-difference update
+ *   (Dynamic_solver.py:13-20, lumped mass of commons.py:103-107) from below only when that number is 0.  Synchronises the
+ *   handle's stream.  No counterpart in the reference, whose step comes from the edge-length rule (commons.py:79-90,
+ *   Data_prepare.py:147).
+ */
+typedef struct saa_operator saa_operator;
+int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
+                        const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
+                        saa_operator **out);
+/* All later work of this handle goes to `hip_stream` (a hipStream_t; NULL = null stream). */
+int saa_operator_set_stream(saa_operator *op, void *hip_stream);
+int saa_operator_apply(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *kx_dev, double *mx_dev,
+                       int64_t ldy);
+int saa_operator_element_bound(saa_operator *op, double *omega_e_dev, double *omega_max, int32_t *argmax,
+                               int32_t *n_nonpositive);
+int saa_operator_destroy(saa_operator *op);
 
 /*
  * Shared-node predictor: the per-rank LSTM encoder-decoder of Tools/DNN_tools.py:16-98 (2-layer bidirectional encoder of

@@ -18,6 +18,7 @@
 
 #include "../../include/saa_hip.h"
 #include "saa_device.h"
+#include "saa_modal.h"
 #include "saa_partition.h"
 #include "saa_plan.h"
 #include "saa_predictor.h"
@@ -794,7 +795,7 @@ extern "C" {
 
 const char *saa_last_error(void) { return g_last_error.c_str(); }
 
-int32_t saa_abi_version(void) { return 10; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check
+int32_t saa_abi_version(void) { return 11; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*
 
 int saa_device_copy_bandwidth(int32_t device, int64_t n_bytes, int32_t reps, double *bytes_per_s) {
   if (!bytes_per_s || n_bytes < 16 || reps < 1) return fail(SAA_E_ARG, "saa_device_copy_bandwidth: bad argument");
@@ -1851,6 +1852,81 @@ int saa_topology_get(const saa_topology *t, int32_t *elements, int32_t *nodes, i
 
 int saa_topology_destroy(saa_topology *t) {
   delete t;
+  return SAA_OK;
+}
+
+// ---- modal-analysis operator (saa_modal.hip) -------------------------------------------------------------------
+struct saa_operator {
+  saa::ModalOp *impl = nullptr;
+};
+
+int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
+                        const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
+                        saa_operator **out) {
+  if (!out) return fail(SAA_E_ARG, "saa_operator_create: null output");
+  *out = nullptr;
+  if (n_nodes <= 0 || n_elems < 0 || n_dirichlet < 0 || !xyz || (n_elems > 0 && !tets) || (n_dirichlet > 0 && !dirichlet_dofs))
+    return fail(SAA_E_ARG, "saa_operator_create: bad argument");
+  if (4 * static_cast<int64_t>(n_elems) > INT32_MAX || 3 * static_cast<int64_t>(n_nodes) > INT32_MAX)
+    return fail(SAA_E_CAPACITY, "saa_operator_create: more than 2^29 elements or 2^31 dofs");
+  if (!(std::isfinite(lambda_) && std::isfinite(mu) && std::isfinite(rho) && rho > 0.0))
+    return fail(SAA_E_ARG, "saa_operator_create: material parameters must be finite and rho > 0");
+  for (int64_t i = 0; i < 4 * static_cast<int64_t>(n_elems); ++i)
+    if (tets[i] < 0 || tets[i] >= n_nodes) return fail(SAA_E_ARG, "saa_operator_create: node id out of range");
+  for (int32_t i = 0; i < n_dirichlet; ++i)
+    if (dirichlet_dofs[i] < 0 || dirichlet_dofs[i] >= 3 * n_nodes) return fail(SAA_E_ARG, "saa_operator_create: Dirichlet dof out of range");
+  saa_operator *op = new (std::nothrow) saa_operator;
+  if (!op) return fail(SAA_E_HIP, "saa_operator_create: out of host memory");
+  std::string err;
+  hipError_t e;
+  try {
+    e = saa::modal_create(device, n_nodes, n_elems, xyz, tets, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, &op->impl, err);
+  } catch (const std::bad_alloc &) {
+    delete op;
+    return fail(SAA_E_HIP, "saa_operator_create: out of host memory");
+  }
+  if (e != hipSuccess) {
+    delete op;
+    (void)hipGetLastError();
+    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_create: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+  }
+  *out = op;
+  return SAA_OK;
+}
+
+int saa_operator_set_stream(saa_operator *op, void *hip_stream) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_set_stream: null handle");
+  saa::modal_set_stream(op->impl, static_cast<hipStream_t>(hip_stream));
+  return SAA_OK;
+}
+
+int saa_operator_apply(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *kx_dev, double *mx_dev,
+                       int64_t ldy) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_apply: null handle");
+  if (m < 1 || m > saa::kModalMaxColumns)
+    return fail(SAA_E_ARG, "saa_operator_apply: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+  if (!x_dev || (!kx_dev && !mx_dev)) return fail(SAA_E_ARG, "saa_operator_apply: null input or no output");
+  const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
+  if (ldx < n_dof || ldy < n_dof) return fail(SAA_E_ARG, "saa_operator_apply: leading dimension below 3 * n_nodes");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::modal_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_apply: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_element_bound(saa_operator *op, double *omega_e_dev, double *omega_max, int32_t *argmax,
+                               int32_t *n_nonpositive) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_element_bound: null handle");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::modal_element_bound(op->impl, omega_e_dev, omega_max, argmax, n_nonpositive);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_element_bound: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_destroy(saa_operator *op) {
+  if (!op) return SAA_OK;
+  saa::modal_destroy(op->impl);
+  delete op;
   return SAA_OK;
 }
 

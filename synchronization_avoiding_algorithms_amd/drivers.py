@@ -1,7 +1,8 @@
 """The reference's driver scripts as functions + CLIs (one process per GPU).
 
 ``Data_prepare.py`` -> :func:`data_prepare`, ``Shared_extraction.py`` -> :func:`shared_extraction`,
-``Online_predictor.py`` -> :func:`online_predictor`; same artefact names under ``Results/`` and
+``Online_predictor.py`` -> :func:`online_predictor`, plus :func:`modal` (stable time step and lowest modes, the
+reference's ``Eigen_mode``); same artefact names under ``Results/`` and
 ``Distributed_save/``, same constants by default.  Launch like the reference's
 ``mpirun -np P python3 X.py``:
 
@@ -198,6 +199,17 @@ def online_predictor(mesh, n_steps=100000, save_every=1, out_dir=".", rank=0, wo
     return path, store, hist
 
 
+def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None):
+    """Stable time step and lowest ``k`` natural frequencies of the whole mesh, clamped on ``x = 0`` like the other
+    drivers (``Data_prepare.py:127-136``), on one GPU (:func:`modal.modal_report`).  Does not change how any other
+    driver picks ``dt``."""
+    from .mesh import clamp_nodes
+    from .modal import modal_report
+
+    p = {name: DEFAULTS[name] if v is None else v for name, v in (("E", E), ("nu", nu), ("rho", rho), ("gamma", gamma))}
+    return modal_report(mesh.points, mesh.tets, clamp_nodes(mesh), k=k, device=device, **p)
+
+
 def _has_gpu():
     import torch
 
@@ -211,7 +223,7 @@ def _load_mesh(args):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="synchronization_avoiding_algorithms_amd.drivers")
     ap.add_argument("command", choices=["data_prepare", "steady_state", "shared_extraction", "model_training",
-                                        "online_predictor"])
+                                        "online_predictor", "modal"])
     ap.add_argument("--epochs", type=int, default=None, help="model_training: override the epoch count")
     ap.add_argument("--mesh", default="Mesh_info/beam_coarse.vtk")
     ap.add_argument("--synthetic", type=int, default=0, help="use the 25n x n x n synthetic beam instead")
@@ -227,8 +239,21 @@ def main(argv=None):
                     help="online_predictor: synchronised steps again after every so many predicted windows (extension; "
                          "default: never, like the reference)")
     ap.add_argument("--resync-steps", type=int, default=None, help="how many (default: one window, n_future*filter_size)")
+    ap.add_argument("--delaunay", action="store_true", help="modal: the unstructured delaunay_beam(n) for --synthetic n")
+    ap.add_argument("--k", type=int, default=6, help="modal: number of lowest modes")
     args = ap.parse_args(argv)
     rank, world, local = _dist_env()
+    if args.command == "modal":  # one whole mesh on one GPU; prints one JSON object
+        if rank != 0:
+            return
+        import json
+
+        from .mesh import delaunay_beam
+
+        mesh = (delaunay_beam(args.synthetic) if args.delaunay else structured_beam(args.synthetic)) if args.synthetic \
+            else read_vtk(args.mesh)
+        print(json.dumps(modal(mesh, k=args.k, device=local)))
+        return
     if args.command == "data_prepare":
         path, _ = data_prepare(_load_mesh(args), args.steps, args.save_every, args.out, rank, world,
                                args.partition, device=local, verbose=True)
