@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -324,6 +324,9 @@ int saa_topology_destroy(saa_topology *t);
  *   (Dynamic_solver.py:13-20, lumped mass of commons.py:103-107) from below only when that number is 0.  Synchronises the
  *   handle's stream.  No counterpart in the reference, whose step comes from the edge-length rule (commons.py:79-90,
  *   Data_prepare.py:147).
+ *
+ * The same handle serves stress recovery (saa_operator_stress, saa_operator_nodal_average, below), with the geometry of
+ * the K apply.  The reference has no counterpart: it stores displacement only.
  */
 typedef struct saa_operator saa_operator;
 int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
@@ -335,6 +338,25 @@ int saa_operator_apply(saa_operator *op, int32_t m, const double *x_dev, int64_t
                        int64_t ldy);
 int saa_operator_element_bound(saa_operator *op, double *omega_e_dev, double *omega_max, int32_t *argmax,
                                int32_t *n_nonpositive);
+/*
+ * Stress recovery.  eps_e = sum_a B_a u_a (rows xx, yy, zz, yz, xz, xy, engineering shear: Mat_construction.py:99-104),
+ * sigma_e = D eps_e (commons.py:25-31), von Mises vm_e, strain energy W_e = |V_e| sigma_e . eps_e / 2 with V_e = detJ / 6
+ * (on a consistently oriented mesh sum_e W_e = d^T K d / 2).  The Dirichlet mask is not applied: x is read as given.
+ * Bitwise repeatable (fixed-order reductions, no floating-point atomics); enqueued on the handle's stream, no host sync.
+ *
+ * saa_operator_stress: m in 1..16 column-major displacement columns (x: 3*n_nodes per column, ldx >= 3*n_nodes).  Outputs
+ *   column-major, any may be NULL: sigma (6*n_elems per column, element e component c at 6e+c, ld_sigma >= 6*n_elems);
+ *   von_mises and energy (n_elems per column, ld_elem >= n_elems); energy_total, von_mises_max (m doubles),
+ *   von_mises_argmax (m int32: the lowest element index on ties).
+ * saa_operator_nodal_average: volume-weighted nodal average sum_{e at v} |V_e| f_e / sum_{e at v} |V_e| (ascending element
+ *   order; 0 at a node with no element) of k in 1..8 components per element: elem (k*n_elems per column, e*k+c,
+ *   ld_elem >= k*n_elems), node (k*n_nodes per column, v*k+c, ld_node >= k*n_nodes).
+ */
+int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *sigma_dev, int64_t ld_sigma,
+                        double *von_mises_dev, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
+                        double *von_mises_max_dev, int32_t *von_mises_argmax_dev);
+int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const double *elem_dev, int64_t ld_elem, double *node_dev,
+                               int64_t ld_node);
 int saa_operator_destroy(saa_operator *op);
 
 /*

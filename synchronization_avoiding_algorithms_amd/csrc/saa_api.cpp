@@ -22,6 +22,7 @@
 #include "saa_partition.h"
 #include "saa_plan.h"
 #include "saa_predictor.h"
+#include "saa_stress.h"
 #include "saa_setup.h"
 #include "saa_topology.h"
 
@@ -795,7 +796,7 @@ extern "C" {
 
 const char *saa_last_error(void) { return g_last_error.c_str(); }
 
-int32_t saa_abi_version(void) { return 11; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*
+int32_t saa_abi_version(void) { return 12; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average
 
 int saa_device_copy_bandwidth(int32_t device, int64_t n_bytes, int32_t reps, double *bytes_per_s) {
   if (!bytes_per_s || n_bytes < 16 || reps < 1) return fail(SAA_E_ARG, "saa_device_copy_bandwidth: bad argument");
@@ -1920,6 +1921,51 @@ int saa_operator_element_bound(saa_operator *op, double *omega_e_dev, double *om
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
   const hipError_t e = saa::modal_element_bound(op->impl, omega_e_dev, omega_max, argmax, n_nonpositive);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_element_bound: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *sigma_dev, int64_t ld_sigma,
+                        double *von_mises_dev, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
+                        double *von_mises_max_dev, int32_t *von_mises_argmax_dev) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stress: null handle");
+  if (m < 1 || m > saa::kModalMaxColumns)
+    return fail(SAA_E_ARG, "saa_operator_stress: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+  if (!x_dev) return fail(SAA_E_ARG, "saa_operator_stress: null displacement x_dev");
+  const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
+  const int64_t n_elems = saa::modal_n_elems(op->impl);
+  if (ldx < n_dof)
+    return fail(SAA_E_ARG, "saa_operator_stress: ldx = " + std::to_string(ldx) + " below 3 * n_nodes = " + std::to_string(n_dof));
+  if (sigma_dev && ld_sigma < 6 * n_elems)
+    return fail(SAA_E_ARG, "saa_operator_stress: ld_sigma = " + std::to_string(ld_sigma) + " below 6 * n_elems = " +
+                               std::to_string(6 * n_elems));
+  if ((von_mises_dev || energy_dev) && ld_elem < n_elems)
+    return fail(SAA_E_ARG, "saa_operator_stress: ld_elem = " + std::to_string(ld_elem) + " below n_elems = " +
+                               std::to_string(n_elems));
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, energy_dev, ld_elem,
+                                           energy_total_dev, von_mises_max_dev, von_mises_argmax_dev);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stress: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const double *elem_dev, int64_t ld_elem, double *node_dev,
+                               int64_t ld_node) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_nodal_average: null handle");
+  if (m < 1 || m > saa::kModalMaxColumns)
+    return fail(SAA_E_ARG, "saa_operator_nodal_average: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+  if (k < 1 || k > saa::kStressMaxComponents)
+    return fail(SAA_E_ARG, "saa_operator_nodal_average: k = " + std::to_string(k) + " components, 1 <= k <= 8");
+  if (!elem_dev || !node_dev) return fail(SAA_E_ARG, "saa_operator_nodal_average: null elem_dev or node_dev");
+  const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
+  if (ld_elem < k * n_elems)
+    return fail(SAA_E_ARG, "saa_operator_nodal_average: ld_elem = " + std::to_string(ld_elem) + " below k * n_elems = " +
+                               std::to_string(k * n_elems));
+  if (ld_node < k * n_nodes)
+    return fail(SAA_E_ARG, "saa_operator_nodal_average: ld_node = " + std::to_string(ld_node) + " below k * n_nodes = " +
+                               std::to_string(k * n_nodes));
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::stress_nodal_average(op->impl, m, k, elem_dev, ld_elem, node_dev, ld_node);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_nodal_average: ") + hipGetErrorString(e));
   return SAA_OK;
 }
 

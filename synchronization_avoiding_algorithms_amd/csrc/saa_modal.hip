@@ -20,64 +20,13 @@
 #include <vector>
 
 #include "saa_modal.h"
+#include "saa_modal_op.h"
 
 namespace saa {
-
-struct ModalOp {
-  int device = 0;
-  int32_t n_nodes = 0, n_elems = 0;
-  double lam = 0.0, mu = 0.0, rho = 0.0;
-  double L[6][6] = {};  // D = L L^T (lower triangular)
-  double *xyz = nullptr;        // 3 * n_nodes
-  int32_t *tets = nullptr;      // 4 * n_elems
-  double *free_mask = nullptr;  // 3 * n_nodes: 1 on free dofs, 0 on Dirichlet dofs
-  int64_t *offsets = nullptr;   // n_nodes + 1
-  int32_t *pairs = nullptr;     // 4 * n_elems: 4 * element + corner, grouped by node, ascending
-  double *scratch_k = nullptr, *scratch_m = nullptr;  // 12 * n_elems * cap_columns each
-  int32_t cap_k = 0, cap_m = 0;
-  double *part_val = nullptr;   // per-workgroup maxima of the element bound
-  int32_t *part_idx = nullptr, *part_cnt = nullptr;
-  double *res_val = nullptr;    // final reduction: omega_max
-  int32_t *res_int = nullptr;   // argmax, n_nonpositive
-  hipStream_t stream = nullptr;
-};
 
 namespace {
 
 constexpr int kThreads = 256;
-
-// Gradients of the four shape functions (rows) and detJ; J columns are the edges x_a - x_0 (Shape_function_Deriv.py:60-67).
-__device__ __forceinline__ double element_gradients(const double *__restrict__ xyz, const int32_t *__restrict__ tets,
-                                                    int64_t e, int32_t v[4], double g[4][3]) {
-  double p[4][3];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    v[a] = tets[4 * e + a];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) p[a][c] = xyz[3 * (int64_t)v[a] + c];
-  }
-  double e1[3], e2[3], e3[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    e1[c] = p[1][c] - p[0][c];
-    e2[c] = p[2][c] - p[0][c];
-    e3[c] = p[3][c] - p[0][c];
-  }
-  // rows of adj J: c1 = e2 x e3, c2 = e3 x e1, c3 = e1 x e2; grad N_a = c_a / detJ, grad N_0 = -(sum of the others)
-  const double c1[3] = {e2[1] * e3[2] - e2[2] * e3[1], e2[2] * e3[0] - e2[0] * e3[2], e2[0] * e3[1] - e2[1] * e3[0]};
-  const double c2[3] = {e3[1] * e1[2] - e3[2] * e1[1], e3[2] * e1[0] - e3[0] * e1[2], e3[0] * e1[1] - e3[1] * e1[0]};
-  const double c3[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-  const double det = e1[0] * c1[0] + e1[1] * c1[1] + e1[2] * c1[2];
-  const double r = 1.0 / det;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    g[1][c] = c1[c] * r;
-    g[2][c] = c2[c] * r;
-    g[3][c] = c3[c] * r;
-    g[0][c] = -(g[1][c] + g[2][c] + g[3][c]);
-  }
-  return det;
-}
 
 struct CholD {
   double l[21];  // lower triangle of L, row by row
@@ -342,7 +291,8 @@ void modal_destroy(ModalOp *op) {
   if (!op) return;
   (void)hipSetDevice(op->device);
   void *bufs[] = {op->xyz, op->tets, op->free_mask, op->offsets, op->pairs, op->scratch_k, op->scratch_m,
-                  op->part_val, op->part_idx, op->part_cnt, op->res_val, op->res_int};
+                  op->part_val, op->part_idx, op->part_cnt, op->res_val, op->res_int, op->abs_vol, op->node_wsum,
+                  op->st_part_w, op->st_part_vm, op->st_part_idx};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   delete op;

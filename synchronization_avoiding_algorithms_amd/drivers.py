@@ -2,7 +2,8 @@
 
 ``Data_prepare.py`` -> :func:`data_prepare`, ``Shared_extraction.py`` -> :func:`shared_extraction`,
 ``Online_predictor.py`` -> :func:`online_predictor`, plus :func:`modal` (stable time step and lowest modes, the
-reference's ``Eigen_mode``); same artefact names under ``Results/`` and
+reference's ``Eigen_mode``) and :func:`stress` (stress recovery from the saved trajectories, no counterpart in the
+reference); same artefact names under ``Results/`` and
 ``Distributed_save/``, same constants by default.  Launch like the reference's
 ``mpirun -np P python3 X.py``:
 
@@ -36,7 +37,10 @@ PATHS = dict(local_nodes="Results/Rankwised_Data/Rank={r}_local_nodes.csv",
              truth="Results/Dynamics/Local-rank-{r}.hdf5",
              modeled="Results/Dynamics/Modeled_Local-rank-{r}.hdf5",
              shared_traj="Results/sol_on_shared/rank={r}-shared_dof.hdf5",
-             model="Distributed_save/Rank-{r}/nB-{nB}-nH-{nH}-Lr-{lr}-filter={ns}/model.pth")
+             model="Distributed_save/Rank-{r}/nB-{nB}-nH-{nH}-Lr-{lr}-filter={ns}/model.pth",
+             stress_vtk="Results/Stress/Stress-col-{j}.vtk",
+             modeled_stress_vtk="Results/Stress/Modeled_Stress-col-{j}.vtk",
+             stress_history="Results/Stress/history.npz")
 
 
 def _dist_env():
@@ -210,6 +214,204 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None):
     return modal_report(mesh.points, mesh.tets, clamp_nodes(mesh), k=k, device=device, **p)
 
 
+def _device_recovery(device=0):
+    """The GPU side of :func:`stress`, and its only one: a factory ``make(points, cells, lmd, mu)`` of objects with
+    NumPy-in / NumPy-out ``element(X (m, n_dof))`` (the dict of :meth:`stress.StressRecovery.element`), ``nodal(E (m,
+    n_elems, k))``, ``history(traj (n_dof, n_cols))`` and ``close()`` on :class:`stress.StressRecovery`.  Tests pass a
+    NumPy stand-in with the same methods."""
+    import torch
+
+    from .stress import StressRecovery
+
+    class _Host:
+        def __init__(self, points, cells, lmd, mu):
+            self.rec = StressRecovery(points, cells, lmd, mu, device=device)
+
+        def _dev(self, a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.rec.torch_device)
+
+        def element(self, X):
+            return {k: v.cpu().numpy() for k, v in self.rec.element(self._dev(X)).items()}
+
+        def nodal(self, E):
+            return self.rec.nodal(self._dev(E)).cpu().numpy()
+
+        def history(self, traj):
+            return {k: v.cpu().numpy() for k, v in self.rec.history(traj).items()}
+
+        def close(self):
+            self.rec.close()
+
+    return _Host
+
+
+def _merge_max(best, arg, val, idx):
+    """Element-wise: keep (best, arg) unless val is larger, or equal with a smaller element index."""
+    take = (val > best) | ((val == best) & (idx < arg))
+    return np.where(take, val, best), np.where(take, idx, arg)
+
+
+def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=True, device=0, E=None, nu=None,
+           recovery=None):
+    """Stress recovery from the artefact tree of :func:`data_prepare` / :func:`online_predictor` under ``out_dir``, on
+    one GPU.  Each element's stress comes from the trajectory of the rank that owns it (``Rank={r}_elements.csv``,
+    local dofs through ``Rank={r}_local_nodes.csv``); nodal averages are taken on the whole mesh from the assembled
+    element field.  For every saved column in ``columns`` (negative = from the end) writes
+    ``Results/Stress/Stress-col-{j}.vtk`` (and ``Modeled_Stress-col-{j}.vtk`` with ``modeled``) unless ``vtk`` is
+    False; ``history`` writes every column's strain energy and von Mises maximum to ``Results/Stress/history.npz``.
+    Returns the report that the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` (default: the GPU)."""
+    from . import fem_setup as fs
+    from .stress import VOIGT, von_mises
+
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    make = _device_recovery(device) if recovery is None else recovery
+    points = np.asarray(mesh.points, dtype=np.float64)
+    tets = np.asarray(mesh.tets, dtype=np.int64)
+    ne, nn = len(tets), len(points)
+    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+
+    ranks = []  # (local nodes, elements) for r = 0, 1, ... while Rank={r}_elements.csv exists
+    while os.path.exists(p["elements"].format(r=len(ranks))):
+        r = len(ranks)
+        ranks.append((rio.load_int_list(p["local_nodes"].format(r=r)), rio.load_int_list(p["elements"].format(r=r))))
+    if not ranks:
+        raise FileNotFoundError(f"no {p['elements'].format(r=0)}: run data_prepare first")
+    owner = np.full(ne, -1, dtype=np.int64)
+    for r, (_, elems) in enumerate(ranks):
+        if elems.size and (elems.min() < 0 or elems.max() >= ne):
+            raise ValueError(f"Rank={r}_elements.csv: element id out of range 0..{ne - 1}")
+        u, cnt = np.unique(elems, return_counts=True)
+        if (cnt > 1).any():
+            raise ValueError(f"Rank={r}_elements.csv lists element {int(u[cnt > 1][0])} more than once")
+        twice = owner[elems] >= 0
+        if twice.any():
+            e = int(elems[twice][0])
+            raise ValueError(f"element {e} is owned by ranks {int(owner[e])} and {r}")
+        owner[elems] = r
+    if (owner < 0).any():
+        missing = np.nonzero(owner < 0)[0]
+        raise ValueError(f"{len(missing)} element(s) owned by no rank (first: {int(missing[0])})")
+    local_cells = []
+    for r, (nodes, elems) in enumerate(ranks):
+        pos = np.full(nn, -1, dtype=np.int64)
+        pos[nodes] = np.arange(len(nodes))
+        lc = pos[tets[elems]]
+        if (lc < 0).any():
+            raise ValueError(f"Rank={r}: element {int(elems[(lc < 0).any(axis=1)][0])} has a node outside "
+                             f"Rank={r}_local_nodes.csv")
+        local_cells.append(lc)
+
+    runs = ["truth"] + (["modeled"] if modeled else [])
+    trajs = {}
+    for run in runs:
+        trajs[run] = []
+        for r, (nodes, _) in enumerate(ranks):
+            path = p[run].format(r=r)
+            data = np.asarray(rio.load_displacement(path), dtype=np.float64)
+            if data.ndim != 2 or data.shape[0] != 3 * len(nodes):
+                raise ValueError(f"{path}: {data.shape[0] if data.ndim else 0} rows, expected 3 * {len(nodes)} = "
+                                 f"{3 * len(nodes)} (3 per local node)")
+            trajs[run].append(data)
+    n_cols = trajs["truth"][0].shape[1]
+    for run in runs:
+        for r, data in enumerate(trajs[run]):
+            if data.shape[1] != n_cols:
+                raise ValueError(f"{p[run].format(r=r)}: {data.shape[1]} saved columns, rank 0 has {n_cols}")
+    cols = []
+    for j in columns:
+        jj = int(j) + n_cols if int(j) < 0 else int(j)
+        if not 0 <= jj < n_cols:
+            raise ValueError(f"column {j} out of range for {n_cols} saved columns")
+        cols.append(jj)
+    m = len(cols)
+
+    fields = {run: dict(sigma=np.zeros((m, ne, 6)), von_mises=np.zeros((m, ne)), energy=np.zeros((m, ne)),
+                        total=np.zeros(m), vmax=np.full(m, -np.inf), arg=np.full(m, -1, dtype=np.int64)) for run in runs}
+    hist = {run: dict(total=np.zeros(n_cols), vmax=np.full(n_cols, -np.inf), arg=np.full(n_cols, -1, dtype=np.int64))
+            for run in runs}
+    for r, (nodes, elems) in enumerate(ranks):
+        if not len(elems):
+            continue
+        rec = make(points[nodes], local_cells[r], lmd, mu)
+        try:
+            for run in runs:
+                T = trajs[run][r]
+                f = fields[run]
+                if m:
+                    res = rec.element(np.ascontiguousarray(T[:, cols].T))
+                    for k in ("sigma", "von_mises", "energy"):
+                        f[k][:, elems] = res[k]
+                    f["total"] += res["energy_total"]
+                    f["vmax"], f["arg"] = _merge_max(f["vmax"], f["arg"], res["von_mises_max"],
+                                                     elems[np.asarray(res["von_mises_argmax"], dtype=np.int64)])
+                if history:
+                    h, hr = hist[run], rec.history(T)
+                    h["total"] += hr["energy_total"]
+                    h["vmax"], h["arg"] = _merge_max(h["vmax"], h["arg"], hr["von_mises_max"],
+                                                     elems[np.asarray(hr["von_mises_argmax"], dtype=np.int64)])
+        finally:
+            rec.close()
+
+    centroid = points[tets].mean(axis=1)
+    interface = np.isin(tets, rio.load_int_list(p["global_shared"])).any(axis=1) if modeled else None
+
+    def summary(f, i):
+        e = int(f["arg"][i])
+        return {"strain_energy": float(f["total"][i]), "von_mises_max": float(f["vmax"][i]), "element": e,
+                "centroid": [float(c) for c in centroid[e]]}
+
+    report = {"n_elems": ne, "n_nodes": nn, "n_ranks": len(ranks), "n_saved": n_cols, "columns": [], "files": [],
+              "history": None}
+    for i, j in enumerate(cols):
+        entry = {"column": j, **summary(fields["truth"], i)}
+        if modeled:
+            vt, vmod = fields["truth"]["von_mises"][i], fields["modeled"]["von_mises"][i]
+            dvm = np.abs(vmod - vt)
+            nt = float(np.linalg.norm(vt))
+            k = int(np.argmax(dvm))
+            entry["modeled"] = summary(fields["modeled"], i)
+            entry.update({"von_mises_rel_l2": float(np.linalg.norm(vmod - vt)) / nt if nt > 0 else float(np.linalg.norm(dvm)),
+                          "dvm_max": float(dvm[k]), "dvm_element": k,
+                          "dvm_max_interface": float(dvm[interface].max()) if interface.any() else 0.0,
+                          "dvm_max_interior": float(dvm[~interface].max()) if (~interface).any() else 0.0})
+        report["columns"].append(entry)
+
+    if vtk and m:
+        vol = np.abs(np.einsum("ij,ij->i", points[tets[:, 1]] - points[tets[:, 0]],
+                               np.cross(points[tets[:, 2]] - points[tets[:, 0]], points[tets[:, 3]] - points[tets[:, 0]])))
+        vol /= 6.0
+        whole = make(points, tets, lmd, mu)
+        try:
+            nodal = {run: whole.nodal(fields[run]["sigma"]) for run in runs}
+        finally:
+            whole.close()
+        for run in runs:
+            disp = np.zeros((m, nn, 3))
+            for r in reversed(range(len(ranks))):  # a node held by several ranks shows the lowest rank's value
+                disp[:, ranks[r][0]] = trajs[run][r][:, cols].T.reshape(m, -1, 3)
+            for i, j in enumerate(cols):
+                f = fields[run]
+                pd = {f"displacement-{c}": disp[i, :, a] for a, c in enumerate("xyz")}
+                pd.update({f"sigma-{c}": nodal[run][i, :, a] for a, c in enumerate(VOIGT)})
+                pd["von-mises"] = von_mises(nodal[run][i])
+                cd = {f"sigma-{c}": f["sigma"][i, :, a] for a, c in enumerate(VOIGT)}
+                cd["von-mises"] = f["von_mises"][i]
+                cd["energy-density"] = np.divide(f["energy"][i], vol, out=np.zeros(ne), where=vol > 0)
+                key = "stress_vtk" if run == "truth" else "modeled_stress_vtk"
+                report["files"].append(rio.write_vtk_fields(p[key].format(j=j), points, tets, pd, cd,
+                                                            title=f"stress, saved column {j} ({run})"))
+    if history:
+        out = {"columns": np.arange(n_cols)}
+        for run in runs:
+            pre = "" if run == "truth" else "modeled_"
+            out.update({pre + "strain_energy": hist[run]["total"], pre + "von_mises_max": hist[run]["vmax"],
+                        pre + "von_mises_element": hist[run]["arg"]})
+        os.makedirs(os.path.dirname(p["stress_history"]), exist_ok=True)
+        np.savez(p["stress_history"], **out)
+        report["history"] = p["stress_history"]
+    return report
+
+
 def _has_gpu():
     import torch
 
@@ -223,7 +425,7 @@ def _load_mesh(args):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="synchronization_avoiding_algorithms_amd.drivers")
     ap.add_argument("command", choices=["data_prepare", "steady_state", "shared_extraction", "model_training",
-                                        "online_predictor", "modal"])
+                                        "online_predictor", "modal", "stress"])
     ap.add_argument("--epochs", type=int, default=None, help="model_training: override the epoch count")
     ap.add_argument("--mesh", default="Mesh_info/beam_coarse.vtk")
     ap.add_argument("--synthetic", type=int, default=0, help="use the 25n x n x n synthetic beam instead")
@@ -239,11 +441,16 @@ def main(argv=None):
                     help="online_predictor: synchronised steps again after every so many predicted windows (extension; "
                          "default: never, like the reference)")
     ap.add_argument("--resync-steps", type=int, default=None, help="how many (default: one window, n_future*filter_size)")
-    ap.add_argument("--delaunay", action="store_true", help="modal: the unstructured delaunay_beam(n) for --synthetic n")
+    ap.add_argument("--delaunay", action="store_true",
+                    help="modal, stress: the unstructured delaunay_beam(n) for --synthetic n")
     ap.add_argument("--k", type=int, default=6, help="modal: number of lowest modes")
+    ap.add_argument("--columns", default="-1", help="stress: saved columns, comma-separated, negative from the end")
+    ap.add_argument("--modeled", action="store_true", help="stress: the modelled run too, and its differences")
+    ap.add_argument("--history", action="store_true", help="stress: every column's strain energy and von Mises maximum")
+    ap.add_argument("--no-vtk", action="store_true", help="stress: no VTK files")
     args = ap.parse_args(argv)
     rank, world, local = _dist_env()
-    if args.command == "modal":  # one whole mesh on one GPU; prints one JSON object
+    if args.command in ("modal", "stress"):  # one whole mesh on one GPU; prints one JSON object
         if rank != 0:
             return
         import json
@@ -252,7 +459,12 @@ def main(argv=None):
 
         mesh = (delaunay_beam(args.synthetic) if args.delaunay else structured_beam(args.synthetic)) if args.synthetic \
             else read_vtk(args.mesh)
-        print(json.dumps(modal(mesh, k=args.k, device=local)))
+        if args.command == "modal":
+            print(json.dumps(modal(mesh, k=args.k, device=local)))
+        else:
+            cols = [int(c) for c in args.columns.split(",") if c.strip()]
+            print(json.dumps(stress(mesh, args.out, cols, modeled=args.modeled, history=args.history, vtk=not args.no_vtk,
+                                    device=local)))
         return
     if args.command == "data_prepare":
         path, _ = data_prepare(_load_mesh(args), args.steps, args.save_every, args.out, rank, world,

@@ -65,3 +65,31 @@ def save_int_list(path: str, values) -> None:
 
 def load_int_list(path: str) -> np.ndarray:
     return np.atleast_1d(np.genfromtxt(path, delimiter=",")).astype(np.int64)
+
+
+def write_vtk_fields(path, points, cells, point_data=None, cell_data=None, title="fields"):
+    """Legacy ASCII VTK of a tetrahedral mesh with named scalar ``POINT_DATA`` and ``CELL_DATA`` arrays
+    (``{name: (n,) array}``, written in order), in the ``%.17g`` format of ``steady.write_vtk_point_data``."""
+    points, cells = np.asarray(points, dtype=np.float64), np.asarray(cells)
+    for section, data, n in (("point", point_data, len(points)), ("cell", cell_data, len(cells))):
+        for name, a in (data or {}).items():
+            if np.shape(a) != (n,) or not name or any(ch.isspace() for ch in name):
+                raise ValueError(f"{section} data {name!r}: need a name without spaces and shape ({n},), got "
+                                 f"{np.shape(a)}")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write(f"# vtk DataFile Version 4.2\n{title}\nASCII\nDATASET UNSTRUCTURED_GRID\n")
+        fh.write(f"POINTS {len(points)} double\n")
+        np.savetxt(fh, points, fmt="%.17g")
+        fh.write(f"CELLS {len(cells)} {5 * len(cells)}\n")
+        np.savetxt(fh, np.column_stack([np.full(len(cells), 4), cells]), fmt="%d")
+        fh.write(f"CELL_TYPES {len(cells)}\n")
+        np.savetxt(fh, np.full(len(cells), 10), fmt="%d")
+        for section, data, n in (("POINT_DATA", point_data, len(points)), ("CELL_DATA", cell_data, len(cells))):
+            if not data:
+                continue
+            fh.write(f"{section} {n}\n")
+            for name, a in data.items():
+                fh.write(f"SCALARS {name} double 1\nLOOKUP_TABLE default\n")
+                np.savetxt(fh, np.asarray(a, dtype=np.float64), fmt="%.17g")
+    return path

@@ -1,0 +1,157 @@
+"""Stress recovery on the GPU: element stress, von Mises, strain energy and volume-weighted nodal averages.
+
+Definitions follow the reference's Voigt conventions (rows xx, yy, zz, yz, xz, xy with engineering shear,
+``Mat_construction.py:93-104``; ``D`` of ``commons.py:25-31``):
+
+* ``eps_e = sum_a B_a u_a``, ``sigma_e = D eps_e`` (constant per linear tetrahedron);
+* ``vm_e = sqrt(((sxx-syy)^2 + (syy-szz)^2 + (szz-sxx)^2)/2 + 3 (syz^2 + sxz^2 + sxy^2))``;
+* ``W_e = |V_e| sigma_e . eps_e / 2`` with ``V_e = detJ/6``; on a consistently oriented mesh ``sum_e W_e = d^T K d / 2``;
+* nodal average ``sigma_v = sum_{e at v} |V_e| sigma_e / sum_{e at v} |V_e|`` (0 at a node with no element).
+
+The kernels (``saa_operator_stress``, ``saa_operator_nodal_average``) run on the ``saa_operator`` handle of
+:class:`modal.ModalOperator`, i.e. with the geometry of the K apply.  Its Dirichlet mask is not applied: the displacement
+is read as given (recorded trajectories are already 0 on clamped dofs).  Blocks of vectors are ``(m, n)`` tensors, one
+column per row, as in :mod:`modal`.  The reference has no counterpart: it stores displacement only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+VOIGT = ("xx", "yy", "zz", "yz", "xz", "xy")
+
+
+def von_mises(sigma):
+    """Von Mises stress of Voigt stresses ``(..., 6)`` (torch tensor or NumPy array)."""
+    s = sigma
+    v = 0.5 * ((s[..., 0] - s[..., 1]) ** 2 + (s[..., 1] - s[..., 2]) ** 2 + (s[..., 2] - s[..., 0]) ** 2) \
+        + 3.0 * (s[..., 3] ** 2 + s[..., 4] ** 2 + s[..., 5] ** 2)
+    return np.sqrt(v) if isinstance(s, np.ndarray) else v.sqrt()
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class StressRecovery:
+    """Stress recovery of one whole mesh on one GPU.  Wraps ``operator`` (a :class:`modal.ModalOperator`, whose mesh
+    and material are then used) or builds one with no Dirichlet dofs.  float64 CUDA tensors in and out."""
+
+    MAX_COLUMNS = 16
+    MAX_COMPONENTS = 8
+
+    def __init__(self, points, cells, lmd, mu, device=0, operator=None):
+        from .modal import ModalOperator
+
+        self._own = operator is None
+        self.op = ModalOperator(points, cells, (), lmd, mu, 1.0, device=device) if operator is None else operator
+        self._lib = self.op._lib
+        self.n_nodes, self.n_elems, self.n_dof = self.op.n_nodes, self.op.n_elems, self.op.n_dof
+        self.torch_device = self.op.torch_device
+
+    def close(self):
+        if self._own and getattr(self, "op", None) is not None:
+            self.op.close()
+        self.op = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- raw calls (any m, k and leading dimension: the library checks them) -----------------------------------------
+    def stress_raw(self, m, x, ldx, sigma=None, ld_sigma=0, von_mises=None, energy=None, ld_elem=0, energy_total=None,
+                   von_mises_max=None, von_mises_argmax=None):
+        _lib.check(self._lib.saa_operator_stress(self.op._h, int(m), _ptr(x), int(ldx), _ptr(sigma), int(ld_sigma),
+                                                 _ptr(von_mises), _ptr(energy), int(ld_elem), _ptr(energy_total),
+                                                 _ptr(von_mises_max), _ptr(von_mises_argmax)))
+
+    def nodal_raw(self, m, k, elem, ld_elem, node, ld_node):
+        _lib.check(self._lib.saa_operator_nodal_average(self.op._h, int(m), int(k), _ptr(elem), int(ld_elem), _ptr(node),
+                                                        int(ld_node)))
+
+    # ---- tensors -------------------------------------------------------------------------------------------------
+    def _check(self, t, name):
+        import torch
+
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+            raise ValueError(f"{name} must be a float64 CUDA tensor")
+
+    def element(self, X, sigma=True, von_mises=True, energy=True) -> dict:
+        """Element fields of a ``(n_dof,)`` vector or an ``(m, n_dof)`` block, in launches of at most 16 columns:
+        ``sigma (m, n_elems, 6)``, ``von_mises``, ``energy (m, n_elems)`` (those asked for) and ``energy_total``,
+        ``von_mises_max``, ``von_mises_argmax (m,)``.  A vector input drops the leading ``m``."""
+        import torch
+
+        self._check(X, "X")
+        vec = X.dim() == 1
+        X = (X.reshape(1, -1) if vec else X).contiguous()
+        if X.shape[1] != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} dofs per column, got {X.shape[1]}")
+        m, ne, dev = X.shape[0], self.n_elems, self.torch_device
+        out = {}
+        if sigma:
+            out["sigma"] = torch.empty((m, ne, 6), dtype=torch.float64, device=dev)
+        if von_mises:
+            out["von_mises"] = torch.empty((m, ne), dtype=torch.float64, device=dev)
+        if energy:
+            out["energy"] = torch.empty((m, ne), dtype=torch.float64, device=dev)
+        out["energy_total"] = torch.empty(m, dtype=torch.float64, device=dev)
+        out["von_mises_max"] = torch.empty(m, dtype=torch.float64, device=dev)
+        out["von_mises_argmax"] = torch.empty(m, dtype=torch.int32, device=dev)
+        for j in range(0, m, self.MAX_COLUMNS):
+            c = min(self.MAX_COLUMNS, m - j)
+            g = {k: v[j] for k, v in out.items()}
+            self.stress_raw(c, X[j], self.n_dof, g.get("sigma"), 6 * ne, g.get("von_mises"), g.get("energy"), ne,
+                            g["energy_total"], g["von_mises_max"], g["von_mises_argmax"])
+        return {k: v[0] for k, v in out.items()} if vec else out
+
+    def nodal(self, E):
+        """Volume-weighted nodal average of element fields ``(m, n_elems, k)`` (or ``(n_elems, k)``) ->
+        ``(m, n_nodes, k)``; more than 8 components go in groups of 8."""
+        import torch
+
+        self._check(E, "E")
+        vec = E.dim() == 2
+        E = E.reshape(1, *E.shape) if vec else E
+        if E.dim() != 3 or E.shape[1] != self.n_elems:
+            raise ValueError(f"expected (m, {self.n_elems}, k) element fields, got {tuple(E.shape)}")
+        m, k = E.shape[0], E.shape[2]
+        out = torch.empty((m, self.n_nodes, k), dtype=torch.float64, device=self.torch_device)
+        for c0 in range(0, k, self.MAX_COMPONENTS):
+            kc = min(self.MAX_COMPONENTS, k - c0)
+            Ec = E[..., c0:c0 + kc].contiguous()
+            Nc = out if kc == k else torch.empty((m, self.n_nodes, kc), dtype=torch.float64, device=self.torch_device)
+            for j in range(0, m, self.MAX_COLUMNS):
+                c = min(self.MAX_COLUMNS, m - j)
+                self.nodal_raw(c, kc, Ec[j], kc * self.n_elems, Nc[j], kc * self.n_nodes)
+            if Nc is not out:
+                out[..., c0:c0 + kc] = Nc
+        return out[0] if vec else out
+
+    def history(self, traj) -> dict:
+        """``energy_total``, ``von_mises_max`` and ``von_mises_argmax`` of every column of a row-major
+        ``(n_dof, n_cols)`` trajectory (the recorder's and the HDF5 layout), host array or device tensor.  Only the
+        reductions are computed; no per-element field is written."""
+        import torch
+
+        if traj.shape[0] != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} rows, got {traj.shape[0]}")
+        n = traj.shape[1]
+        dev = self.torch_device
+        out = {"energy_total": torch.empty(n, dtype=torch.float64, device=dev),
+               "von_mises_max": torch.empty(n, dtype=torch.float64, device=dev),
+               "von_mises_argmax": torch.empty(n, dtype=torch.int32, device=dev)}
+        for j in range(0, n, self.MAX_COLUMNS):
+            c = min(self.MAX_COLUMNS, n - j)
+            if isinstance(traj, torch.Tensor):
+                blk = traj[:, j:j + c].to(device=dev, dtype=torch.float64).T.contiguous()
+            else:
+                blk = torch.from_numpy(np.ascontiguousarray(np.asarray(traj[:, j:j + c], dtype=np.float64).T)).to(dev)
+            self.stress_raw(c, blk, self.n_dof, energy_total=out["energy_total"][j:], von_mises_max=out["von_mises_max"][j:],
+                            von_mises_argmax=out["von_mises_argmax"][j:])
+        return out
