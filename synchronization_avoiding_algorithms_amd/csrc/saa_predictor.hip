@@ -762,13 +762,20 @@ hipError_t predictor_create(int device, const PredictorShape &sh, const float *c
       err = "saa_predictor_create: null weight tensor";
       return hipErrorInvalidValue;
     }
-  const size_t lds = (size_t)(G + D + (size_t)sh.n_past * D + (size_t)sh.n_past * G) * sizeof(float);
-  if (lds > 160 * 1024) {
-    err = "saa_predictor_create: n_past * hidden too large for the LDS of one workgroup";
-    return hipErrorInvalidValue;
-  }
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return e;
+  // the recurrence kernel's LDS - gates, h, and the layer-0 outputs and input projections of every step: 40 H (n_p + 1)
+  // bytes - against what the device grants one workgroup (160 KiB on gfx950), so that a shape beyond it is refused here
+  // and not at its first launch
+  const size_t lds = (size_t)(G + D + (size_t)sh.n_past * D + (size_t)sh.n_past * G) * sizeof(float);
+  int lds_max = 0;
+  e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+  if (e != hipSuccess) return e;
+  if (lds > (size_t)lds_max) {
+    err = "saa_predictor_create: n_past * hidden too large for the LDS of one workgroup (" + std::to_string(lds) +
+          " bytes; the device allows " + std::to_string(lds_max) + ")";
+    return hipErrorInvalidValue;
+  }
   Predictor *p = new Predictor;
   p->device = device;
   p->sh = sh;

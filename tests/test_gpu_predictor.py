@@ -9,11 +9,11 @@ import pytest
 import torch
 
 from conftest import load_golden
+from predictor_double import TOL, fp64_table
 from synchronization_avoiding_algorithms_amd import _lib
 from synchronization_avoiding_algorithms_amd import predictor as pr
 
 pytestmark = pytest.mark.gpu
-TOL = 2e-5
 
 
 def _oracle_table(model, n, n_p, n_f, n_s, hist, smax, smin):
@@ -75,20 +75,6 @@ def test_against_the_sequential_oracle(shape):
     assert torch.equal(nat.predict(n, poisoned, smax, smin), nat.predict(n, dh, smax, smin))
 
 
-def _fp64_table(model, n, n_p, n_f, n_s, hist, smax, smin):
-    """The same model evaluated in fp64 on the GPU (weights widened, the scaled history not rounded to fp32)."""
-    import copy
-
-    m64 = copy.deepcopy(model).double()
-    past, fut = pr._phase_indices(n, n_p, n_f, n_s)
-    with torch.no_grad():
-        X = pr.scale_forward(hist[torch.as_tensor(np.stack(past), device=hist.device)], smax, smin)
-        Y = pr.scale_it_back(pr.model_predict(hist.device, m64, X, n_f), smax, smin)
-    table = torch.zeros((n_s * n_f, hist.shape[1]), dtype=torch.float64, device=hist.device)
-    table[torch.as_tensor(np.stack(fut), device=hist.device).reshape(-1)] = Y.reshape(-1, hist.shape[1])
-    return table
-
-
 def test_config4_shape_against_the_fp64_evaluation_and_pytorch_rocm():
     """9126 inputs (the interior slab of the 8-way partition of the 8.2M-tet beam), H = 50, 20/20/150.  Two fp32
     evaluations that add 9126 terms in different orders - these kernels and PyTorch-ROCm (MIOpen LSTM, rocBLAS GEMMs) -
@@ -102,7 +88,7 @@ def test_config4_shape_against_the_fp64_evaluation_and_pytorch_rocm():
     smax, smin = float(hist.max()) * 1.05, float(hist.min()) * 1.05
     nat = pr.NativePredictor(model, n_p, n_f, n_s)
     for n in (n_p * n_s, n_p * n_s + 100):
-        ref = _fp64_table(model, n, n_p, n_f, n_s, hist, smax, smin)
+        ref = fp64_table(model, n, n_p, n_f, n_s, hist, smax, smin)
         with torch.no_grad():
             pt32 = pr.predict_table(model, n, n_p, n_f, n_s, hist, smax, smin)
         got = nat.predict(n, hist, smax, smin)

@@ -136,7 +136,8 @@ def test_fused_cell_kernels_forward_and_backward_on_gpu():
     from synchronization_avoiding_algorithms_amd import training as tr
 
     torch.manual_seed(0)
-    for B, D in ((10, 100), (3, 7), (1, 1)):
+    # 255, 256, 257 elements: a last workgroup of 255 threads, none ragged, one thread alone; then more than 2^20
+    for B, D in ((10, 100), (3, 7), (1, 1), (5, 51), (2, 128), (1, 257), (1025, 1024)):
         gates = torch.randn(B, 4 * D, device="cuda", requires_grad=True)
         c0 = torch.randn(B, D, device="cuda", requires_grad=True)
         wh, wc = torch.randn(B, D, device="cuda"), torch.randn(B, D, device="cuda")
@@ -227,32 +228,44 @@ def test_train_stats_kernel_against_the_formulas():
 def test_whole_recurrence_kernels_against_step_by_step_autograd(width, reverse):
     """``saa_lstm_recurrence_forward`` / ``_backward`` behind ``training._Recurrence``: every h_t, the final c and the
     gradients with respect to the input projections, the recurrent matrix and the initial states against the same
-    recurrence written step by step in PyTorch ops."""
+    recurrence written step by step in PyTorch ops, in fp32 and in fp64.  T = 1 and 2 are where the kernels' one step
+    ahead requests clamp (the forward's next projection, the backward's fetch of the step before); B = 300 is a grid of
+    300 workgroups."""
     import torch
 
     from synchronization_avoiding_algorithms_amd import training as tr
 
-    torch.manual_seed(width + int(reverse))
-    B, T, H = 7, 9, width
-    pre = (torch.randn(B, T, 4 * H, device="cuda") * 0.5).requires_grad_()
-    W = (torch.randn(4 * H, H, device="cuda") * 0.2).requires_grad_()
-    h0 = (torch.randn(B, H, device="cuda") * 0.3).requires_grad_()
-    c0 = (torch.randn(B, H, device="cuda") * 0.3).requires_grad_()
-    wh, wc = torch.randn(B, T, H, device="cuda"), torch.randn(B, H, device="cuda")
-    for with_state in (True, False):
-        Hall, cT = tr._Recurrence.apply(pre, h0 if with_state else None, c0 if with_state else None, W, reverse)
-        h = h0 if with_state else torch.zeros(B, H, device="cuda")
-        c = c0 if with_state else torch.zeros(B, H, device="cuda")
+    def step_by_step(pre, W, h, c, T):
         seq = [None] * T
         for t in (range(T - 1, -1, -1) if reverse else range(T)):
             gi, gf, gg, go = (pre[:, t, :] + h @ W.t()).chunk(4, dim=1)
             c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
             h = torch.sigmoid(go) * torch.tanh(c)
             seq[t] = h
-        ref = torch.stack(seq, dim=1)
-        assert float((Hall - ref).detach().abs().max()) < 3e-6 and float((cT - c).detach().abs().max()) < 3e-6
-        wrt = (pre, W, h0, c0) if with_state else (pre, W)
-        ga = torch.autograd.grad((Hall * wh).sum() + (cT * wc).sum(), wrt)
-        gb = torch.autograd.grad((ref * wh).sum() + (c * wc).sum(), wrt)
-        for a, b in zip(ga, gb):
-            assert float((a - b).abs().max()) < 2e-5 * max(1.0, float(b.abs().max())), (width, reverse, with_state)
+        return torch.stack(seq, dim=1), c
+
+    torch.manual_seed(width + int(reverse))
+    H = width
+    for B, T in ((7, 9), (1, 1), (1, 2), (300, 20)):
+        pre = (torch.randn(B, T, 4 * H, device="cuda") * 0.5).requires_grad_()
+        W = (torch.randn(4 * H, H, device="cuda") * 0.2).requires_grad_()
+        h0 = (torch.randn(B, H, device="cuda") * 0.3).requires_grad_()
+        c0 = (torch.randn(B, H, device="cuda") * 0.3).requires_grad_()
+        wh, wc = torch.randn(B, T, H, device="cuda"), torch.randn(B, H, device="cuda")
+        # the same leaves widened: the fp64 reference
+        pre64, W64, h064, c064 = (x.detach().double().requires_grad_() for x in (pre, W, h0, c0))
+        for with_state in (True, False):
+            Hall, cT = tr._Recurrence.apply(pre, h0 if with_state else None, c0 if with_state else None, W, reverse)
+            wrt = (pre, W, h0, c0) if with_state else (pre, W)
+            ga = torch.autograd.grad((Hall * wh).sum() + (cT * wc).sum(), wrt)
+            for dt, leaves in ((torch.float32, (pre, W, h0, c0)), (torch.float64, (pre64, W64, h064, c064))):
+                p, w, hs, cs = leaves
+                h = hs if with_state else torch.zeros(B, H, device="cuda", dtype=dt)
+                c = cs if with_state else torch.zeros(B, H, device="cuda", dtype=dt)
+                ref, c = step_by_step(p, w, h, c, T)
+                case = (B, T, width, reverse, with_state, dt)
+                assert float((Hall.double() - ref.double()).detach().abs().max()) < 3e-6, case
+                assert float((cT.double() - c.double()).detach().abs().max()) < 3e-6, case
+                gb = torch.autograd.grad((ref * wh.to(dt)).sum() + (c * wc.to(dt)).sum(), (p, w, hs, cs) if with_state else (p, w))
+                for a, b in zip(ga, gb):
+                    assert float((a.double() - b.double()).abs().max()) < 2e-5 * max(1.0, float(b.abs().max())), case
