@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -133,6 +133,12 @@ int saa_plan_host_stats(int32_t n_nodes, int32_t n_elems, const double *xyz, con
  * kernels assume).  No reference counterpart (its LocalK is an assembled matrix); used by the CPU tests. */
 int saa_plan_host_check(int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets, int32_t block_nodes,
                         int64_t *violations_out);
+/* Per-block extremes of that plan (host only, no GPU; saa_plan_stats holds maxima of the node counts and totals only):
+ * out6 = { largest halo, largest work-item list, largest interior list, largest boundary list (items - interior),
+ * smallest owned count, smallest halo } over the blocks.  The CPU tests prove with them which sweep-depth regime of the
+ * step kernels a (mesh, block_nodes, threads) point reaches. */
+int saa_plan_host_block_maxima(int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets, int32_t block_nodes,
+                               int32_t *out6);
 
 /* All later work of this handle goes to `hip_stream` (a hipStream_t; NULL = null stream). */
 int saa_set_stream(saa_solver *s, void *hip_stream);

@@ -21,7 +21,7 @@ SOURCES = ["saa_plan.cpp", "saa_partition.cpp", "saa_kernels.hip", "saa_setup.hi
            "saa_stress.hip", "saa_api.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-ldl"]
 
-ABI_VERSION = 12  # what saa_abi_version() of a matching library returns (include/saa_hip.h)
+ABI_VERSION = 13  # what saa_abi_version() of a matching library returns (include/saa_hip.h)
 SAA_OK, SAA_E_ARG, SAA_E_HIP, SAA_E_STATE, SAA_E_CAPACITY = 0, -1, -2, -3, -4
 
 
@@ -80,6 +80,7 @@ SIGNATURES = {
     "saa_plan_stats_get": (C.c_int, [_H, C.POINTER(PlanStats)]),
     "saa_plan_host_stats": (C.c_int, [C.c_int32, C.c_int32, _dp, _ip, C.c_int32, C.POINTER(PlanStats)]),
     "saa_plan_host_check": (C.c_int, [C.c_int32, C.c_int32, _dp, _ip, C.c_int32, C.POINTER(C.c_int64)]),
+    "saa_plan_host_block_maxima": (C.c_int, [C.c_int32, C.c_int32, _dp, _ip, C.c_int32, _ip]),
     "saa_set_stream": (C.c_int, [_H, C.c_void_p]),
     "saa_set_state": (C.c_int, [_H, _dp, _dp, C.c_double]),
     "saa_get_state": (C.c_int, [_H, _dp, _dp, _dp]),

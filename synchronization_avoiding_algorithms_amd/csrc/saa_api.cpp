@@ -140,6 +140,7 @@ struct saa_solver {
   DevBuf<int32_t> ps_err;
   DevBuf<saa::PeerEntry> ps_entries;  // 2 x 3*n_nodes stamped displacements
   int32_t ps_lds = 0, ps_max_items = 0, ps_steps = 0;
+  int64_t ps_launches = 0;  // resident launches enqueued so far (read by diagnostic builds only)
   int32_t ps_lds_peer = 0;  // LDS of the PEER variant: the image plus the block's push / receive records (0: does not fit)
   bool ps_capable = false;  // plan fits LDS and all workgroups can be co-resident
   bool ps_capable_predict = false;  // ... and the PREDICT instantiation passed its own census (saa_step_predicted)
@@ -173,6 +174,8 @@ struct saa_solver {
   saa::PeerMap peer{};
   bool peer_ready = false;
   unsigned peer_seq = 0;
+  unsigned peer_seq0 = 0;            // where saa_peer_attach starts the sequence (diagnostic builds may preset it; else 0)
+  int64_t peer_parity_repeats = 0;   // consecutive exchanges that used the same inbox parity (must stay 0)
   // Split stepping (plans of several rounds of workgroups, i.e. partitions beyond the resident kernel's capacity): the
   // blocks in three sets - left, right and the blocks between them - stepped on three streams, setup_split_stepping()
   DevBuf<saa::BlockDesc> split_blocks[3];
@@ -363,6 +366,19 @@ int check_peer_error(saa_solver *s) {
   return SAA_OK;
 }
 
+// Sequence number of the next peer exchange.  0 marks an inbox entry as "never written", and the inboxes are double-buffered
+// by the number's parity: two consecutive exchanges must differ in it, or a rank that is one exchange ahead overwrites the
+// value its neighbour is still polling for.  After 0xffffffff (odd) the sequence therefore continues at 2, not at 1.  No
+// stale entry can carry the new number: every shared value is pushed in every exchange, so the even half of an inbox holds
+// 0xfffffffe by then (or 0 where nothing was ever pushed), the odd half 0xffffffff, and 2, 3, ... match neither.
+inline unsigned next_peer_seq(unsigned seq) { return seq == 0xffffffffu ? 2u : seq + 1u; }
+
+void advance_peer_seq(saa_solver *s) {
+  const unsigned next = next_peer_seq(s->peer_seq);
+  if (s->peer_seq != s->peer_seq0 && ((next ^ s->peer_seq) & 1u) == 0u) ++s->peer_parity_repeats;
+  s->peer_seq = next;
+}
+
 // Steps shorter than this use one launch per step (the resident kernel pays its set-up once per launch).
 constexpr int32_t kPersistMinSteps = 8;
 
@@ -443,6 +459,9 @@ void setup_persistent(saa_solver *s) {
   s->ps_lds = lds;
   s->ps_max_items = max_items;
   s->ps_steps = 0;
+  // (diagnostic build, tests/test_gpu_step_edges.py: start the stamps near their wrap; launches stage their first step's
+  // halo from the state buffers, so the zeroed entries are consistent with any starting count)
+  if (const char *env = saa::diag_env("SAA_PRESET_PS_STEPS")) s->ps_steps = static_cast<int32_t>(std::strtoul(env, nullptr, 0));
   // nothing else may occupy the CUs while the census counts (another handle's resident launch would make it fail)
   if (hipDeviceSynchronize() != hipSuccess || !persistent_census(s, lds, 0)) {
     (void)hipGetLastError();
@@ -549,6 +568,7 @@ int try_persistent_steps(saa_solver *s, int32_t nsteps, const double *table_dev,
       return SAA_OK;
     }
     s->ps_steps = static_cast<int32_t>(static_cast<uint32_t>(s->ps_steps) + static_cast<uint32_t>(n));
+    ++s->ps_launches;
     if (n & 1) std::swap(s->i0, s->in_);
     for (int32_t k = 0; k < n; ++k) s->tn = s->tn + s->consts.dt;  // the kernel advanced its copy the same way
     if (peer) s->peer_seq += static_cast<uint32_t>(n);
@@ -796,7 +816,7 @@ extern "C" {
 
 const char *saa_last_error(void) { return g_last_error.c_str(); }
 
-int32_t saa_abi_version(void) { return 12; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average
+int32_t saa_abi_version(void) { return 13; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima
 
 int saa_device_copy_bandwidth(int32_t device, int64_t n_bytes, int32_t reps, double *bytes_per_s) {
   if (!bytes_per_s || n_bytes < 16 || reps < 1) return fail(SAA_E_ARG, "saa_device_copy_bandwidth: bad argument");
@@ -816,6 +836,28 @@ int saa_plan_host_stats(int32_t n_nodes, int32_t n_elems, const double *xyz, con
   std::string err;
   if (!build_fitting_plan(n_nodes, n_elems, xyz, tets, block_nodes, plan, err)) return fail(SAA_E_ARG, err);
   fill_stats(plan, lds_bytes_of(plan), pick_threads(plan, 0), out);
+  return SAA_OK;
+}
+
+// Per-block maxima of the plan saa_plan_host_stats describes (host only; the tests of the step kernels' sweep-depth edges
+// prove with them which loop of a kernel a shape reaches): out[0..5] = largest halo, largest item list, largest interior
+// list, largest boundary list (items - interior), smallest owned count, smallest halo.
+int saa_plan_host_block_maxima(int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets, int32_t block_nodes,
+                               int32_t *out6) {
+  if (!out6) return fail(SAA_E_ARG, "saa_plan_host_block_maxima: null out");
+  saa::Plan plan;
+  std::string err;
+  if (!build_fitting_plan(n_nodes, n_elems, xyz, tets, block_nodes, plan, err)) return fail(SAA_E_ARG, err);
+  int32_t v[6] = {0, 0, 0, 0, INT32_MAX, INT32_MAX};
+  for (const saa::BlockDesc &b : plan.blocks) {
+    v[0] = std::max(v[0], b.n_halo);
+    v[1] = std::max(v[1], b.n_elem);
+    v[2] = std::max(v[2], b.n_interior);
+    v[3] = std::max(v[3], b.n_elem - b.n_interior);
+    v[4] = std::min(v[4], b.n_owned);
+    v[5] = std::min(v[5], b.n_halo);
+  }
+  std::copy(v, v + 6, out6);
   return SAA_OK;
 }
 
@@ -990,6 +1032,8 @@ int saa_create(const saa_problem *pb, saa_solver **out) {
 
   saa_solver *s = new (std::nothrow) saa_solver();
   if (!s) return fail(SAA_E_HIP, "saa_create: out of host memory");
+  // (diagnostic build, tests/test_gpu_step_edges.py: start the peer exchange's sequence near its wrap)
+  if (const char *env = saa::diag_env("SAA_PRESET_PEER_SEQ")) s->peer_seq0 = static_cast<unsigned>(std::strtoul(env, nullptr, 0));
   std::string err;
   // a shared node costs its workgroup a push to and a collect from the neighbour ranks on top of its elements
   // (tools/peer_loopback.py: ~1.9 us for ~95 shared nodes against ~11 us for ~5300 element copies): the blocks are
@@ -1579,7 +1623,8 @@ static int peer_attach_impl(saa_solver *s, int32_t rank, int32_t world, const ui
   pm.world = world;
   pm.n_shared = nsh;
   HIP_TRY(s->px_map.upload(std::vector<saa::PeerMap>(1, pm)));
-  s->peer_seq = 0;
+  s->peer_seq = s->peer_seq0;
+  s->peer_parity_repeats = 0;
   // resident PEER kernel: every block keeps its push / receive / second-neighbour records (16 bytes each per shared node)
   // behind its LDS image; the larger workgroup has to pass the census again
   s->ps_lds_peer = 0;
@@ -1606,7 +1651,7 @@ int saa_peer_selftest(saa_solver *s, int32_t *ok) {
   if (!s->peer_ready) return fail(SAA_E_STATE, "saa_peer_selftest: saa_peer_attach first");
   if (s->pending) return fail(SAA_E_STATE, "saa_peer_selftest: a synchronised step is in flight");
   HIP_TRY(hipSetDevice(s->device));
-  ++s->peer_seq;
+  advance_peer_seq(s);
   saa::launch_peer_selftest(s->peer, s->stream, s->px_own.p, s->px_test.p, s->peer_seq);
   if (int rc = check_launch()) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1636,7 +1681,7 @@ int saa_step_peer(saa_solver *s, int32_t nsteps, double *hist_dev, int64_t hist_
   if (int rc = try_persistent_steps(s, nsteps, nullptr, 0, hist_dev, hist_row0, &k0, true)) return rc;
   for (int32_t k = k0; k < nsteps; ++k) {
     s->set_ramp();
-    if (++s->peer_seq == 0) ++s->peer_seq;  // 0 marks "never written"
+    advance_peer_seq(s);  // skips 0 ("never written") and keeps the parities alternating across the wrap
     saa::launch_fused_step_peer(s->mesh, s->threads, s->lds_bytes, s->stream, s->dbuf[s->i0].p, s->dbuf[s->in_].p,
                                 s->dbuf[s->i1].p, hist_dev ? hist_dev + (hist_row0 + k) * width : nullptr, s->consts,
                                 s->px_map.p, s->peer_seq);
@@ -2146,6 +2191,17 @@ int saa_debug_time_peer(saa_solver *s, int32_t nsteps, double *elapsed_ms) {
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);
   return rc ? rc : check_peer_error(s);
+}
+
+// Diagnostic (tests/test_gpu_step_edges.py): the peer exchange's sequence number, the resident kernel's stamp count, how
+// many consecutive exchanges shared an inbox parity since saa_peer_attach, and the resident launches enqueued so far.
+int saa_debug_counters(saa_solver *s, uint32_t *peer_seq, uint32_t *ps_steps, int64_t *parity_repeats, int64_t *resident_launches) {
+  if (!s) return fail(SAA_E_ARG, "saa_debug_counters: null handle");
+  if (peer_seq) *peer_seq = s->peer_seq;
+  if (ps_steps) *ps_steps = static_cast<uint32_t>(s->ps_steps);
+  if (parity_repeats) *parity_repeats = s->peer_parity_repeats;
+  if (resident_launches) *resident_launches = s->ps_launches;
+  return SAA_OK;
 }
 
 // Diagnostic (tools/persist_stamps.py): buffer of 8 * waves uint64 that a -DSAA_PERSIST_STAMPS build of the resident

@@ -301,3 +301,14 @@ def plan_host_check(points, cells, block_nodes=0) -> int:
     bad = C.c_int64()
     _lib.check(lib.saa_plan_host_check(pts.size // 3, tets.size // 4, _dptr(pts), _iptr(tets), int(block_nodes), C.byref(bad)))
     return int(bad.value)
+
+
+def plan_host_block_maxima(points, cells, block_nodes=0) -> dict:
+    """Per-block extremes of the plan :func:`plan_host_stats` describes (``saa_plan_host_block_maxima``).  No GPU needed."""
+    lib = _lib.load()
+    pts, tets = _f64(points), _i32(cells)
+    out = np.zeros(6, dtype=np.int32)
+    _lib.check(lib.saa_plan_host_block_maxima(pts.size // 3, tets.size // 4, _dptr(pts), _iptr(tets), int(block_nodes),
+                                              out.ctypes.data_as(C.POINTER(C.c_int32))))
+    names = ("max_halo", "max_items", "max_interior", "max_boundary", "min_owned", "min_halo")
+    return {k: int(v) for k, v in zip(names, out)}
