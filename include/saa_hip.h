@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -331,8 +331,8 @@ int saa_topology_destroy(saa_topology *t);
  *   handle's stream.  No counterpart in the reference, whose step comes from the edge-length rule (commons.py:79-90,
  *   Data_prepare.py:147).
  *
- * The same handle serves stress recovery (saa_operator_stress, saa_operator_nodal_average, below), with the geometry of
- * the K apply.  The reference has no counterpart: it stores displacement only.
+ * The same handle serves stress recovery (saa_operator_stress, saa_operator_nodal_average, saa_operator_stress_error,
+ * below), with the geometry of the K apply.  The reference has no counterpart: it stores displacement only.
  */
 typedef struct saa_operator saa_operator;
 int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
@@ -363,6 +363,24 @@ int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_
                         double *von_mises_max_dev, int32_t *von_mises_argmax_dev);
 int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const double *elem_dev, int64_t ld_elem, double *node_dev,
                                int64_t ld_node);
+/*
+ * Stress error per element in the energy norm, with the compliance C = D^-1 (engineering shear):
+ *   eta_e^2 = integral_e (sigma_A - sigma_e)^T C (sigma_A - sigma_e) dV,
+ * sigma_e the element stress (sigma_elem: 6*n_elems per column, 6e+c, ld_sigma >= 6*n_elems) and sigma_A exactly one of
+ *   sigma_node: nodal values (6*n_nodes per column, 6v+c, ld_node >= 6*n_nodes), interpolated linearly over the element.
+ *     With the nodal average of sigma_e this is the Zienkiewicz-Zhu estimate; the integral is exact:
+ *     eta_e^2 = |V_e| / 20 (s^T C s + sum_a delta_a^T C delta_a), delta_a = sigma_A(vertex a) - sigma_e, s = sum_a delta_a;
+ *   sigma_other: a second element field (6*n_elems per column, 6e+c, ld_other >= 6*n_elems): eta_e^2 = |V_e| delta^T C delta.
+ * The other one is NULL.  m in 1..16 columns.  Outputs, any may be NULL (all NULL: nothing is launched): eta2 (n_elems per
+ * column, ld_eta >= n_elems); eta2_total, eta2_max (m doubles), eta2_argmax (m int32: the lowest element index on ties; -1
+ * and 0.0 on a mesh without elements).  Needs mu > 0 and 3 lambda + 2 mu > 0.  Bitwise repeatable (fixed-order reductions, no
+ * floating-point atomics), a column's results do not depend on the other columns of the call; enqueued on the handle's
+ * stream, no host sync.  No counterpart in the reference.
+ */
+int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_elem_dev, int64_t ld_sigma,
+                              const double *sigma_node_dev, int64_t ld_node, const double *sigma_other_dev, int64_t ld_other,
+                              double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
+                              int32_t *eta2_argmax_dev);
 int saa_operator_destroy(saa_operator *op);
 
 /*

@@ -816,7 +816,7 @@ extern "C" {
 
 const char *saa_last_error(void) { return g_last_error.c_str(); }
 
-int32_t saa_abi_version(void) { return 13; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima
+int32_t saa_abi_version(void) { return 14; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error
 
 int saa_device_copy_bandwidth(int32_t device, int64_t n_bytes, int32_t reps, double *bytes_per_s) {
   if (!bytes_per_s || n_bytes < 16 || reps < 1) return fail(SAA_E_ARG, "saa_device_copy_bandwidth: bad argument");
@@ -2011,6 +2011,39 @@ int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const dou
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
   const hipError_t e = saa::stress_nodal_average(op->impl, m, k, elem_dev, ld_elem, node_dev, ld_node);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_nodal_average: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_elem_dev, int64_t ld_sigma,
+                              const double *sigma_node_dev, int64_t ld_node, const double *sigma_other_dev, int64_t ld_other,
+                              double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
+                              int32_t *eta2_argmax_dev) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stress_error: null handle");
+  if (m < 1 || m > saa::kModalMaxColumns)
+    return fail(SAA_E_ARG, "saa_operator_stress_error: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+  if (!sigma_elem_dev) return fail(SAA_E_ARG, "saa_operator_stress_error: null element stress sigma_elem_dev");
+  if (!sigma_node_dev == !sigma_other_dev)
+    return fail(SAA_E_ARG, std::string("saa_operator_stress_error: ") + (sigma_node_dev ? "both" : "neither") +
+                               " of sigma_node_dev and sigma_other_dev given, exactly one is needed");
+  const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
+  if (ld_sigma < 6 * n_elems)
+    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_sigma = " + std::to_string(ld_sigma) + " below 6 * n_elems = " +
+                               std::to_string(6 * n_elems));
+  if (sigma_node_dev && ld_node < 6 * n_nodes)
+    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_node = " + std::to_string(ld_node) + " below 6 * n_nodes = " +
+                               std::to_string(6 * n_nodes));
+  if (sigma_other_dev && ld_other < 6 * n_elems)
+    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_other = " + std::to_string(ld_other) + " below 6 * n_elems = " +
+                               std::to_string(6 * n_elems));
+  if (eta2_dev && ld_eta < n_elems)
+    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_eta = " + std::to_string(ld_eta) + " below n_elems = " +
+                               std::to_string(n_elems));
+  if (!saa::stress_has_compliance(op->impl))
+    return fail(SAA_E_ARG, "saa_operator_stress_error: the compliance D^-1 needs mu > 0 and 3 lambda + 2 mu > 0");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::stress_error(op->impl, m, sigma_elem_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev,
+                                         ld_other, eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stress_error: ") + hipGetErrorString(e));
   return SAA_OK;
 }
 

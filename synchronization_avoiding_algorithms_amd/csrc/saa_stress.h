@@ -1,5 +1,6 @@
 // Stress recovery on the saa_operator handle (saa_stress.hip): element stress, von Mises, strain energy and their
-// per-column totals, and the volume-weighted nodal average of element fields.
+// per-column totals, the volume-weighted nodal average of element fields, and the energy norm of a stress difference per
+// element (the Zienkiewicz-Zhu error estimate).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,5 +24,16 @@ hipError_t stress_element(ModalOp *op, int32_t m, const double *x, int64_t ldx, 
 // no element) for 1 <= k <= kStressMaxComponents.  Enqueued on the op's stream.
 hipError_t stress_nodal_average(ModalOp *op, int32_t m, int32_t k, const double *elem, int64_t ld_elem, double *node,
                                 int64_t ld_node);
+
+// The compliance C = D^-1 of the error norm exists: mu > 0 and 3 lambda + 2 mu > 0.
+bool stress_has_compliance(const ModalOp *op);
+
+// Energy norm of the difference between the element stress sigma [column][6 e + c] and either the piecewise-linear field
+// of the nodal values sigma_node [column][6 v + c] (the Zienkiewicz-Zhu estimate) or a second element field sigma_other
+// [column][6 e + c]; exactly one of the two is non-null.  eta2: [column][e]; eta2_total, eta2_max, eta2_argmax: m entries;
+// any output may be null.  Enqueued on the op's stream; arguments are validated by the caller.
+hipError_t stress_error(ModalOp *op, int32_t m, const double *sigma, int64_t ld_sigma, const double *sigma_node, int64_t ld_node,
+                        const double *sigma_other, int64_t ld_other, double *eta2, int64_t ld_eta, double *eta2_total,
+                        double *eta2_max, int32_t *eta2_argmax);
 
 }  // namespace saa

@@ -175,6 +175,115 @@ __global__ void __launch_bounds__(kThreads) stress_final_kernel(int32_t n_parts,
   }
 }
 
+namespace {
+
+// six consecutive doubles; wide = the address is 16-byte aligned (three 16-byte loads instead of six 8-byte ones)
+__device__ __forceinline__ void load6(const double *__restrict__ p, bool wide, double t[6]) {
+  if (wide) {  // (uniform branch)
+    const double2 *q = reinterpret_cast<const double2 *>(p);
+    const double2 a = q[0], b = q[1], c = q[2];
+    t[0] = a.x, t[1] = a.y, t[2] = b.x, t[3] = b.y, t[4] = c.x, t[5] = c.y;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) t[c] = p[c];
+  }
+}
+
+// t^T C t with C = D^-1 (commons.py:25-31, engineering shear): half_imu = 1 / (2 mu), ctr = lambda / (3 lambda + 2 mu)
+__device__ __forceinline__ double compliance_form(const double t[6], double half_imu, double ctr) {
+  const double tr = t[0] + t[1] + t[2];
+  return half_imu * ((t[0] * t[0] + t[1] * t[1] + t[2] * t[2] - ctr * (tr * tr)) + 2.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5]));
+}
+
+}  // namespace
+
+// Error pass, one element per lane, the columns looped inside.  kNodal: against the piecewise-linear field of the nodal
+// values other[column][6 v + c], eta_e^2 = |V_e| / 20 (s^T C s + sum_a delta_a^T C delta_a) with delta_a = other(v_a) -
+// sigma_e and s = sum_a delta_a (the exact integral of a quadratic over the tetrahedron); otherwise against the element
+// field other[column][6 e + c], eta_e^2 = |V_e| delta^T C delta.  The 24 nodal values per element and column are the only
+// reads that do not stream; each is a 48-byte row.  Partials as in stress_elem_kernel (sum, max, lowest argmax).
+template <bool kNodal>
+__global__ void __launch_bounds__(kThreads) stress_error_kernel(int32_t n_elems, int32_t m, const int32_t *__restrict__ tets,
+                                                                const double *__restrict__ abs_vol, double half_imu, double ctr,
+                                                                const double *__restrict__ sigma, int64_t ld_sigma,
+                                                                const double *__restrict__ other, int64_t ld_other,
+                                                                bool wide_sigma, bool wide_other, double *__restrict__ eta2,
+                                                                int64_t ld_eta, double *__restrict__ part_w,
+                                                                double *__restrict__ part_vm, int32_t *__restrict__ part_idx) {
+  __shared__ double lw[kModalMaxColumns][kWaves], lvm[kModalMaxColumns][kWaves];
+  __shared__ int32_t li[kModalMaxColumns][kWaves];
+  const int64_t e = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+  const bool valid = e < n_elems;
+  int32_t v[4] = {0, 0, 0, 0};
+  double scale = 0.0;
+  if (valid) {
+    if (kNodal) {
+      const int4 t = reinterpret_cast<const int4 *>(tets)[e];  // (hipMalloc'ed by the handle: 16-byte aligned)
+      v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    }
+    scale = kNodal ? abs_vol[e] / 20.0 : abs_vol[e];
+  }
+  for (int32_t j = 0; j < m; ++j) {
+    double w = 0.0, best = -1.0;
+    if (valid) {
+      double se[6];
+      load6(sigma + j * ld_sigma + 6 * e, wide_sigma, se);
+      const double *oj = other + j * ld_other;
+      double q;
+      if (kNodal) {
+        double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        q = 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          double d[6];
+          load6(oj + 6 * (int64_t)v[a], wide_other, d);
+#pragma unroll
+          for (int c = 0; c < 6; ++c) {
+            d[c] -= se[c];
+            s[c] += d[c];
+          }
+          q += compliance_form(d, half_imu, ctr);
+        }
+        q += compliance_form(s, half_imu, ctr);
+      } else {
+        double d[6];
+        load6(oj + 6 * e, wide_other, d);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) d[c] -= se[c];
+        q = compliance_form(d, half_imu, ctr);
+      }
+      w = scale * q;
+      best = w;
+      if (eta2) eta2[j * ld_eta + e] = w;
+    }
+    if (part_w) {  // (uniform branch)
+      int32_t arg = valid ? (int32_t)e : INT32_MAX;
+      wave_reduce(w, best, arg);
+      if ((threadIdx.x & 63) == 0) {
+        lw[j][threadIdx.x >> 6] = w;
+        lvm[j][threadIdx.x >> 6] = best;
+        li[j][threadIdx.x >> 6] = arg;
+      }
+    }
+  }
+  if (part_w) {
+    __syncthreads();
+    const int32_t j = threadIdx.x;
+    if (j < m) {
+      double w = lw[j][0], best = lvm[j][0];
+      int32_t arg = li[j][0];
+#pragma unroll
+      for (int k = 1; k < kWaves; ++k) {
+        w += lw[j][k];
+        max_merge(best, arg, lvm[j][k], li[j][k]);
+      }
+      part_w[(int64_t)j * gridDim.x + blockIdx.x] = w;
+      part_vm[(int64_t)j * gridDim.x + blockIdx.x] = best;
+      part_idx[(int64_t)j * gridDim.x + blockIdx.x] = arg;
+    }
+  }
+}
+
 // Node pass: node[j][K v + c] = sum_{e at v} |V_e| elem[j][K e + c] / node_wsum[v], ascending e.
 template <int K>
 __global__ void __launch_bounds__(kThreads) nodal_average_kernel(int32_t n_nodes, int32_t m, const int64_t *__restrict__ offsets,
@@ -267,6 +376,40 @@ hipError_t stress_element(ModalOp *op, int32_t m, const double *x, int64_t ldx, 
   if (reduce) {
     hipLaunchKernelGGL(stress_final_kernel, dim3(static_cast<unsigned>(m)), dim3(kThreads), 0, op->stream, n_parts,
                        op->st_part_w, op->st_part_vm, op->st_part_idx, energy_total, von_mises_max, von_mises_argmax);
+    STRESS_TRY(hipGetLastError());
+  }
+  return hipSuccess;
+}
+
+bool stress_has_compliance(const ModalOp *op) { return op->mu > 0.0 && 3.0 * op->lam + 2.0 * op->mu > 0.0; }
+
+hipError_t stress_error(ModalOp *op, int32_t m, const double *sigma, int64_t ld_sigma, const double *sigma_node, int64_t ld_node,
+                        const double *sigma_other, int64_t ld_other, double *eta2, int64_t ld_eta, double *eta2_total,
+                        double *eta2_max, int32_t *eta2_argmax) {
+  const bool reduce = eta2_total || eta2_max || eta2_argmax;
+  if (!reduce && !eta2) return hipSuccess;
+  STRESS_TRY(stress_prepare(op));
+  const int32_t n_parts = n_parts_of(op);
+  if (n_parts > 0) {
+    const double half_imu = 0.5 / op->mu, ctr = op->lam / (3.0 * op->lam + 2.0 * op->mu);
+    const double *other = sigma_node ? sigma_node : sigma_other;
+    const int64_t ldo = sigma_node ? ld_node : ld_other;
+    const auto wide = [m](const double *p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (m == 1 || ld % 2 == 0); };
+    double *pw = reduce ? op->st_part_w : nullptr;
+#define STRESS_ERROR(NODAL)                                                                                                    \
+  hipLaunchKernelGGL(stress_error_kernel<NODAL>, dim3(static_cast<unsigned>(n_parts)), dim3(kThreads), 0, op->stream,          \
+                     op->n_elems, m, op->tets, op->abs_vol, half_imu, ctr, sigma, ld_sigma, other, ldo, wide(sigma, ld_sigma), \
+                     wide(other, ldo), eta2, ld_eta, pw, op->st_part_vm, op->st_part_idx)
+    if (sigma_node)
+      STRESS_ERROR(true);
+    else
+      STRESS_ERROR(false);
+#undef STRESS_ERROR
+    STRESS_TRY(hipGetLastError());
+  }
+  if (reduce) {
+    hipLaunchKernelGGL(stress_final_kernel, dim3(static_cast<unsigned>(m)), dim3(kThreads), 0, op->stream, n_parts,
+                       op->st_part_w, op->st_part_vm, op->st_part_idx, eta2_total, eta2_max, eta2_argmax);
     STRESS_TRY(hipGetLastError());
   }
   return hipSuccess;

@@ -2,8 +2,9 @@
 
 ``Data_prepare.py`` -> :func:`data_prepare`, ``Shared_extraction.py`` -> :func:`shared_extraction`,
 ``Online_predictor.py`` -> :func:`online_predictor`, plus :func:`modal` (stable time step and lowest modes, the
-reference's ``Eigen_mode``) and :func:`stress` (stress recovery from the saved trajectories, no counterpart in the
-reference); same artefact names under ``Results/`` and
+reference's ``Eigen_mode``), :func:`stress` (stress recovery from the saved trajectories) and :func:`estimate` (the
+Zienkiewicz-Zhu estimate of the stress error of the mesh, the scale for the error of the modelled run; neither has a
+counterpart in the reference); same artefact names under ``Results/`` and
 ``Distributed_save/``, same constants by default.  Launch like the reference's
 ``mpirun -np P python3 X.py``:
 
@@ -40,7 +41,8 @@ PATHS = dict(local_nodes="Results/Rankwised_Data/Rank={r}_local_nodes.csv",
              model="Distributed_save/Rank-{r}/nB-{nB}-nH-{nH}-Lr-{lr}-filter={ns}/model.pth",
              stress_vtk="Results/Stress/Stress-col-{j}.vtk",
              modeled_stress_vtk="Results/Stress/Modeled_Stress-col-{j}.vtk",
-             stress_history="Results/Stress/history.npz")
+             stress_history="Results/Stress/history.npz",
+             estimate_vtk="Results/Stress/Estimate-col-{j}.vtk")
 
 
 def _dist_env():
@@ -215,10 +217,11 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None):
 
 
 def _device_recovery(device=0):
-    """The GPU side of :func:`stress`, and its only one: a factory ``make(points, cells, lmd, mu)`` of objects with
-    NumPy-in / NumPy-out ``element(X (m, n_dof))`` (the dict of :meth:`stress.StressRecovery.element`), ``nodal(E (m,
-    n_elems, k))``, ``history(traj (n_dof, n_cols))`` and ``close()`` on :class:`stress.StressRecovery`.  Tests pass a
-    NumPy stand-in with the same methods."""
+    """The GPU side of :func:`stress` and :func:`estimate`, and its only one: a factory ``make(points, cells, lmd, mu)`` of
+    objects with NumPy-in / NumPy-out ``element(X (m, n_dof))`` (the dict of :meth:`stress.StressRecovery.element`),
+    ``nodal(E (m, n_elems, k))``, ``error(sigma_elem, nodal=None, other=None)`` (the dict of
+    :meth:`stress.StressRecovery.error`), ``history(traj (n_dof, n_cols))`` and ``close()`` on
+    :class:`stress.StressRecovery`.  Tests pass a NumPy stand-in with the same methods."""
     import torch
 
     from .stress import StressRecovery
@@ -236,6 +239,11 @@ def _device_recovery(device=0):
         def nodal(self, E):
             return self.rec.nodal(self._dev(E)).cpu().numpy()
 
+        def error(self, sigma_elem, nodal=None, other=None):
+            res = self.rec.error(self._dev(sigma_elem), nodal=None if nodal is None else self._dev(nodal),
+                                 other=None if other is None else self._dev(other))
+            return {k: v.cpu().numpy() for k, v in res.items()}
+
         def history(self, traj):
             return {k: v.cpu().numpy() for k, v in self.rec.history(traj).items()}
 
@@ -251,25 +259,19 @@ def _merge_max(best, arg, val, idx):
     return np.where(take, val, best), np.where(take, idx, arg)
 
 
-def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=True, device=0, E=None, nu=None,
-           recovery=None):
-    """Stress recovery from the artefact tree of :func:`data_prepare` / :func:`online_predictor` under ``out_dir``, on
-    one GPU.  Each element's stress comes from the trajectory of the rank that owns it (``Rank={r}_elements.csv``,
-    local dofs through ``Rank={r}_local_nodes.csv``); nodal averages are taken on the whole mesh from the assembled
-    element field.  For every saved column in ``columns`` (negative = from the end) writes
-    ``Results/Stress/Stress-col-{j}.vtk`` (and ``Modeled_Stress-col-{j}.vtk`` with ``modeled``) unless ``vtk`` is
-    False; ``history`` writes every column's strain energy and von Mises maximum to ``Results/Stress/history.npz``.
-    Returns the report that the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` (default: the GPU)."""
-    from . import fem_setup as fs
-    from .stress import VOIGT, von_mises
+def _abs_volumes(points, tets):
+    vol = np.abs(np.einsum("ij,ij->i", points[tets[:, 1]] - points[tets[:, 0]],
+                           np.cross(points[tets[:, 2]] - points[tets[:, 0]], points[tets[:, 3]] - points[tets[:, 0]])))
+    return vol / 6.0
 
-    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
-    make = _device_recovery(device) if recovery is None else recovery
-    points = np.asarray(mesh.points, dtype=np.float64)
-    tets = np.asarray(mesh.tets, dtype=np.int64)
-    ne, nn = len(tets), len(points)
-    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
 
+def _load_recovery_tree(p, tets, nn, runs, columns):
+    """What :func:`stress` and :func:`estimate` read from the artefact tree (``p``: ``PATHS`` under the output directory):
+    per rank ``(local nodes, elements)`` and the owned elements' cells in local node numbers, per run in ``runs`` the
+    ranks' trajectories, the number of saved columns and ``columns`` resolved against it.  Every element must be owned
+    by exactly one rank, with its nodes among that rank's local nodes; every trajectory has 3 rows per local node and
+    the same columns."""
+    ne = len(tets)
     ranks = []  # (local nodes, elements) for r = 0, 1, ... while Rank={r}_elements.csv exists
     while os.path.exists(p["elements"].format(r=len(ranks))):
         r = len(ranks)
@@ -301,7 +303,6 @@ def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=T
                              f"Rank={r}_local_nodes.csv")
         local_cells.append(lc)
 
-    runs = ["truth"] + (["modeled"] if modeled else [])
     trajs = {}
     for run in runs:
         trajs[run] = []
@@ -323,6 +324,30 @@ def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=T
         if not 0 <= jj < n_cols:
             raise ValueError(f"column {j} out of range for {n_cols} saved columns")
         cols.append(jj)
+    return ranks, local_cells, trajs, n_cols, cols
+
+
+def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=True, device=0, E=None, nu=None,
+           recovery=None):
+    """Stress recovery from the artefact tree of :func:`data_prepare` / :func:`online_predictor` under ``out_dir``, on
+    one GPU.  Each element's stress comes from the trajectory of the rank that owns it (``Rank={r}_elements.csv``,
+    local dofs through ``Rank={r}_local_nodes.csv``); nodal averages are taken on the whole mesh from the assembled
+    element field.  For every saved column in ``columns`` (negative = from the end) writes
+    ``Results/Stress/Stress-col-{j}.vtk`` (and ``Modeled_Stress-col-{j}.vtk`` with ``modeled``) unless ``vtk`` is
+    False; ``history`` writes every column's strain energy and von Mises maximum to ``Results/Stress/history.npz``.
+    Returns the report that the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` (default: the GPU)."""
+    from . import fem_setup as fs
+    from .stress import VOIGT, von_mises
+
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    make = _device_recovery(device) if recovery is None else recovery
+    points = np.asarray(mesh.points, dtype=np.float64)
+    tets = np.asarray(mesh.tets, dtype=np.int64)
+    ne, nn = len(tets), len(points)
+    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+
+    runs = ["truth"] + (["modeled"] if modeled else [])
+    ranks, local_cells, trajs, n_cols, cols = _load_recovery_tree(p, tets, nn, runs, columns)
     m = len(cols)
 
     fields = {run: dict(sigma=np.zeros((m, ne, 6)), von_mises=np.zeros((m, ne)), energy=np.zeros((m, ne)),
@@ -377,9 +402,7 @@ def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=T
         report["columns"].append(entry)
 
     if vtk and m:
-        vol = np.abs(np.einsum("ij,ij->i", points[tets[:, 1]] - points[tets[:, 0]],
-                               np.cross(points[tets[:, 2]] - points[tets[:, 0]], points[tets[:, 3]] - points[tets[:, 0]])))
-        vol /= 6.0
+        vol = _abs_volumes(points, tets)
         whole = make(points, tets, lmd, mu)
         try:
             nodal = {run: whole.nodal(fields[run]["sigma"]) for run in runs}
@@ -412,6 +435,94 @@ def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=T
     return report
 
 
+def estimate(mesh, out_dir=".", columns=(-1,), modeled=False, vtk=True, device=0, E=None, nu=None, recovery=None):
+    """Zienkiewicz-Zhu estimate of the stress error of the mesh, from the artefact tree that :func:`stress` reads and with
+    its ownership rule: each element's stress comes from the trajectory of the rank that owns it; the nodal average and
+    ``eta_e^2 = integral_e (sigma* - sigma_e)^T D^-1 (sigma* - sigma_e) dV`` are taken on the whole mesh.  For every saved
+    column in ``columns`` reports ``eta = sqrt(sum_e eta_e^2)``, ``energy_norm = sqrt(2 * strain energy)``, ``relative =
+    eta / sqrt(energy_norm^2 + eta^2)`` and the element of the largest ``eta_e^2``.  With ``modeled`` also the estimate of
+    the modelled run, ``model_error = sqrt(sum_e |V_e| dsigma^T D^-1 dsigma)`` (``dsigma``: modelled minus synchronised
+    element stress), its ratio to ``eta``, both squared sums over interface elements (those with a ``Global_shared`` node)
+    and the others, and how many elements of each set have a model error above their own ``eta_e^2``.  Writes
+    ``Results/Stress/Estimate-col-{j}.vtk`` (cell data ``eta2``, ``error-density = eta2 / |V_e|`` and, with ``modeled``,
+    ``model-error2``) unless ``vtk`` is False.  Returns the report that the CLI prints as JSON.  ``recovery``: see
+    :func:`_device_recovery` (default: the GPU)."""
+    from . import fem_setup as fs
+
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    make = _device_recovery(device) if recovery is None else recovery
+    points = np.asarray(mesh.points, dtype=np.float64)
+    tets = np.asarray(mesh.tets, dtype=np.int64)
+    ne, nn = len(tets), len(points)
+    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+    runs = ["truth"] + (["modeled"] if modeled else [])
+    ranks, local_cells, trajs, n_cols, cols = _load_recovery_tree(p, tets, nn, runs, columns)
+    m = len(cols)
+
+    sigma = {run: np.zeros((m, ne, 6)) for run in runs}
+    energy = {run: np.zeros(m) for run in runs}
+    for r, (nodes, elems) in enumerate(ranks):
+        if not len(elems) or not m:
+            continue
+        rec = make(points[nodes], local_cells[r], lmd, mu)
+        try:
+            for run in runs:
+                res = rec.element(np.ascontiguousarray(trajs[run][r][:, cols].T))
+                sigma[run][:, elems] = res["sigma"]
+                energy[run] += res["energy_total"]
+        finally:
+            rec.close()
+    zz, model = {}, None
+    if m:
+        whole = make(points, tets, lmd, mu)
+        try:
+            for run in runs:
+                zz[run] = whole.error(sigma[run], nodal=whole.nodal(sigma[run]))
+            if modeled:
+                model = whole.error(sigma["modeled"], other=sigma["truth"])
+        finally:
+            whole.close()
+
+    centroid = points[tets].mean(axis=1)
+    interface = np.isin(tets, rio.load_int_list(p["global_shared"])).any(axis=1) if modeled else None
+
+    def summary(run, i):
+        eta2, w2 = float(zz[run]["eta2_total"][i]), 2.0 * float(energy[run][i])
+        e = int(zz[run]["eta2_argmax"][i])
+        return {"eta": float(np.sqrt(eta2)), "energy_norm": float(np.sqrt(w2)),
+                "relative": float(np.sqrt(eta2 / (w2 + eta2))) if w2 + eta2 > 0 else 0.0, "element": e,
+                "eta2_max": float(zz[run]["eta2_max"][i]), "centroid": [float(c) for c in centroid[e]]}
+
+    report = {"n_elems": ne, "n_nodes": nn, "n_ranks": len(ranks), "n_saved": n_cols, "columns": [], "files": []}
+    for i, j in enumerate(cols):
+        entry = {"column": j, **summary("truth", i)}
+        if modeled:
+            eta2, me2 = zz["truth"]["eta2"][i], model["eta2"][i]
+            above = me2 > eta2
+            entry["modeled"] = summary("modeled", i)
+            entry.update({"model_error": float(np.sqrt(model["eta2_total"][i])),
+                          "model_over_discretisation": float(np.sqrt(model["eta2_total"][i])) / entry["eta"]
+                          if entry["eta"] > 0 else None,
+                          "eta2_interface": float(eta2[interface].sum()), "eta2_interior": float(eta2[~interface].sum()),
+                          "model_error2_interface": float(me2[interface].sum()),
+                          "model_error2_interior": float(me2[~interface].sum()),
+                          "n_interface": int(interface.sum()), "n_interior": int((~interface).sum()),
+                          "n_model_above_eta_interface": int((above & interface).sum()),
+                          "n_model_above_eta_interior": int((above & ~interface).sum())})
+        report["columns"].append(entry)
+
+    if vtk and m:
+        vol = _abs_volumes(points, tets)
+        for i, j in enumerate(cols):
+            eta2 = zz["truth"]["eta2"][i]
+            cd = {"eta2": eta2, "error-density": np.divide(eta2, vol, out=np.zeros(ne), where=vol > 0)}
+            if modeled:
+                cd["model-error2"] = model["eta2"][i]
+            report["files"].append(rio.write_vtk_fields(p["estimate_vtk"].format(j=j), points, tets, None, cd,
+                                                        title=f"stress error estimate, saved column {j}"))
+    return report
+
+
 def _has_gpu():
     import torch
 
@@ -425,7 +536,7 @@ def _load_mesh(args):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="synchronization_avoiding_algorithms_amd.drivers")
     ap.add_argument("command", choices=["data_prepare", "steady_state", "shared_extraction", "model_training",
-                                        "online_predictor", "modal", "stress"])
+                                        "online_predictor", "modal", "stress", "estimate"])
     ap.add_argument("--epochs", type=int, default=None, help="model_training: override the epoch count")
     ap.add_argument("--mesh", default="Mesh_info/beam_coarse.vtk")
     ap.add_argument("--synthetic", type=int, default=0, help="use the 25n x n x n synthetic beam instead")
@@ -442,15 +553,15 @@ def main(argv=None):
                          "default: never, like the reference)")
     ap.add_argument("--resync-steps", type=int, default=None, help="how many (default: one window, n_future*filter_size)")
     ap.add_argument("--delaunay", action="store_true",
-                    help="modal, stress: the unstructured delaunay_beam(n) for --synthetic n")
+                    help="modal, stress, estimate: the unstructured delaunay_beam(n) for --synthetic n")
     ap.add_argument("--k", type=int, default=6, help="modal: number of lowest modes")
-    ap.add_argument("--columns", default="-1", help="stress: saved columns, comma-separated, negative from the end")
-    ap.add_argument("--modeled", action="store_true", help="stress: the modelled run too, and its differences")
+    ap.add_argument("--columns", default="-1", help="stress, estimate: saved columns, comma-separated, negative from the end")
+    ap.add_argument("--modeled", action="store_true", help="stress, estimate: the modelled run too, and its differences")
     ap.add_argument("--history", action="store_true", help="stress: every column's strain energy and von Mises maximum")
-    ap.add_argument("--no-vtk", action="store_true", help="stress: no VTK files")
+    ap.add_argument("--no-vtk", action="store_true", help="stress, estimate: no VTK files")
     args = ap.parse_args(argv)
     rank, world, local = _dist_env()
-    if args.command in ("modal", "stress"):  # one whole mesh on one GPU; prints one JSON object
+    if args.command in ("modal", "stress", "estimate"):  # one whole mesh on one GPU; prints one JSON object
         if rank != 0:
             return
         import json
@@ -461,6 +572,9 @@ def main(argv=None):
             else read_vtk(args.mesh)
         if args.command == "modal":
             print(json.dumps(modal(mesh, k=args.k, device=local)))
+        elif args.command == "estimate":
+            cols = [int(c) for c in args.columns.split(",") if c.strip()]
+            print(json.dumps(estimate(mesh, args.out, cols, modeled=args.modeled, vtk=not args.no_vtk, device=local)))
         else:
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
             print(json.dumps(stress(mesh, args.out, cols, modeled=args.modeled, history=args.history, vtk=not args.no_vtk,

@@ -8,7 +8,13 @@ Definitions follow the reference's Voigt conventions (rows xx, yy, zz, yz, xz, x
 * ``W_e = |V_e| sigma_e . eps_e / 2`` with ``V_e = detJ/6``; on a consistently oriented mesh ``sum_e W_e = d^T K d / 2``;
 * nodal average ``sigma_v = sum_{e at v} |V_e| sigma_e / sum_{e at v} |V_e|`` (0 at a node with no element).
 
-The kernels (``saa_operator_stress``, ``saa_operator_nodal_average``) run on the ``saa_operator`` handle of
+* stress error in the energy norm, ``eta_e^2 = integral_e (sigma_A - sigma_e)^T C (sigma_A - sigma_e) dV`` with ``C = D^-1``:
+  against the piecewise-linear field of nodal values (with the nodal average: the Zienkiewicz-Zhu estimate of the
+  discretisation error, ``|V_e|/20 (s^T C s + sum_a delta_a^T C delta_a)``, ``delta_a = sigma_A(vertex a) - sigma_e``,
+  ``s = sum_a delta_a``) or against a second element field (``|V_e| delta^T C delta``).
+
+The kernels (``saa_operator_stress``, ``saa_operator_nodal_average``, ``saa_operator_stress_error``) run on the
+``saa_operator`` handle of
 :class:`modal.ModalOperator`, i.e. with the geometry of the K apply.  Its Dirichlet mask is not applied: the displacement
 is read as given (recorded trajectories are already 0 on clamped dofs).  Blocks of vectors are ``(m, n)`` tensors, one
 column per row, as in :mod:`modal`.  The reference has no counterpart: it stores displacement only.
@@ -74,6 +80,12 @@ class StressRecovery:
         _lib.check(self._lib.saa_operator_nodal_average(self.op._h, int(m), int(k), _ptr(elem), int(ld_elem), _ptr(node),
                                                         int(ld_node)))
 
+    def error_raw(self, m, sigma_elem, ld_sigma, sigma_node=None, ld_node=0, sigma_other=None, ld_other=0, eta2=None, ld_eta=0,
+                  eta2_total=None, eta2_max=None, eta2_argmax=None):
+        _lib.check(self._lib.saa_operator_stress_error(self.op._h, int(m), _ptr(sigma_elem), int(ld_sigma), _ptr(sigma_node),
+                                                       int(ld_node), _ptr(sigma_other), int(ld_other), _ptr(eta2), int(ld_eta),
+                                                       _ptr(eta2_total), _ptr(eta2_max), _ptr(eta2_argmax)))
+
     # ---- tensors -------------------------------------------------------------------------------------------------
     def _check(self, t, name):
         import torch
@@ -132,6 +144,51 @@ class StressRecovery:
             if Nc is not out:
                 out[..., c0:c0 + kc] = Nc
         return out[0] if vec else out
+
+    def error(self, sigma_elem, nodal=None, other=None) -> dict:
+        """Stress error per element in the energy norm: element stresses ``(m, n_elems, 6)`` against exactly one of
+        ``nodal (m, n_nodes, 6)`` (interpolated linearly over each element; with :meth:`nodal` of ``sigma_elem`` this is
+        the Zienkiewicz-Zhu estimate) and ``other (m, n_elems, 6)`` (a second element field).  Returns ``eta2 (m,
+        n_elems)`` and ``eta2_total``, ``eta2_max``, ``eta2_argmax (m,)``, in launches of at most 16 columns.  2-D inputs
+        drop the leading ``m``."""
+        import torch
+
+        if (nodal is None) == (other is None):
+            raise ValueError("exactly one of nodal and other is needed")
+        second, rows, name = (nodal, self.n_nodes, "nodal") if nodal is not None else (other, self.n_elems, "other")
+        self._check(sigma_elem, "sigma_elem")
+        self._check(second, name)
+        vec = sigma_elem.dim() == 2
+        S = (sigma_elem.reshape(1, *sigma_elem.shape) if vec else sigma_elem).contiguous()
+        O = (second.reshape(1, *second.shape) if second.dim() == 2 else second).contiguous()
+        if S.dim() != 3 or tuple(S.shape[1:]) != (self.n_elems, 6):
+            raise ValueError(f"expected (m, {self.n_elems}, 6) element stresses, got {tuple(sigma_elem.shape)}")
+        if O.dim() != 3 or tuple(O.shape) != (S.shape[0], rows, 6):
+            raise ValueError(f"expected {name} of shape ({S.shape[0]}, {rows}, 6), got {tuple(second.shape)}")
+        m, ne, dev = S.shape[0], self.n_elems, self.torch_device
+        out = {"eta2": torch.empty((m, ne), dtype=torch.float64, device=dev),
+               "eta2_total": torch.empty(m, dtype=torch.float64, device=dev),
+               "eta2_max": torch.empty(m, dtype=torch.float64, device=dev),
+               "eta2_argmax": torch.empty(m, dtype=torch.int32, device=dev)}
+        for j in range(0, m, self.MAX_COLUMNS):
+            c = min(self.MAX_COLUMNS, m - j)
+            node, oth = (O[j], None) if nodal is not None else (None, O[j])
+            self.error_raw(c, S[j], 6 * ne, node, 6 * rows, oth, 6 * rows, out["eta2"][j], ne, out["eta2_total"][j:],
+                           out["eta2_max"][j:], out["eta2_argmax"][j:])
+        return {k: v[0] for k, v in out.items()} if vec else out
+
+    def estimate(self, X) -> dict:
+        """Zienkiewicz-Zhu estimate of the stress error of displacement columns ``(m, n_dof)`` (or one ``(n_dof,)``
+        vector): element stress -> nodal average -> :meth:`error`.  Returns the dict of :meth:`error` plus
+        ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish)."""
+        import torch
+
+        el = self.element(X, von_mises=False, energy=False)
+        out = self.error(el["sigma"], nodal=self.nodal(el["sigma"]))
+        out["energy_total"] = el["energy_total"]
+        den = 2.0 * el["energy_total"] + out["eta2_total"]
+        out["relative"] = torch.where(den > 0, out["eta2_total"] / den, torch.zeros_like(den)).sqrt()
+        return out
 
     def history(self, traj) -> dict:
         """``energy_total``, ``von_mises_max`` and ``von_mises_argmax`` of every column of a row-major
