@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -333,11 +333,40 @@ int saa_topology_destroy(saa_topology *t);
  *
  * The same handle serves stress recovery (saa_operator_stress, saa_operator_nodal_average, saa_operator_stress_error,
  * below), with the geometry of the K apply.  The reference has no counterpart: it stores displacement only.
+ *
+ * Quadratic tetrahedra (p = 2, the reference's second element: `Global_Assembly(2, ...)`, n_basis = 10).
+ * saa_operator_create_p2: as saa_operator_create with 10 node ids per element in the reference's local order
+ *   (Shape_function_Deriv.py:14-23, VTK cell type 24): the four vertices, then the nodes on the edges (0,1), (1,2), (0,2),
+ *   (0,3), (1,3), (2,3).  The geometry is isoparametric: the Jacobian comes from all ten nodes at every quadrature point
+ *   (Shape_function_Deriv.py:60-67), so curved elements are legal; detJ is signed.  At most 214 748 364 elements
+ *   (10 * n_elems + corner must fit 32 bits).
+ * saa_operator_order: 1 or 2.
+ * saa_operator_apply on an order-2 handle means the same: 1..16 columns, Dirichlet rows and columns masked, bitwise
+ *   repeatable without floating-point atomics, every column independent of the others in the call.  K uses the reference's
+ *   rule for deg == 2 (n_quad = 2: the 4-point rule, Mat_construction.py:84-89).  M uses the 14-point rule Gauss_Legendre(4)
+ *   and NOT the reference's 4-point rule: a DELIBERATE DEVIATION.  With four points the 30 x 30 element mass has rank 12
+ *   and the assembled mass is singular (36-tet 6 x 1 x 1 beam: 18 of 351 eigenvalues are 0, the smallest is -1e-17), so the
+ *   reference's own Eigen_mode(2, ...) cannot work; the 14-point mass is positive definite on the same mesh (smallest
+ *   eigenvalue 3.3e-3) and its total is exact.
+ * saa_operator_load (either order): the consistent body-force vector sum_q w_q detJ_q N_a(xi_q) (fx, fy, fz) with the K rule,
+ *   `Fe` of Local_MKF assembled (the reference's load is (0, -fz, -fz), commons.py:35-41); 3*n_nodes doubles on the device,
+ *   0 on Dirichlet dofs.
+ * saa_operator_diagonal (either order): diag(K) and / or diag(M) of the masked operator (0 on Dirichlet dofs), 3*n_nodes
+ *   doubles each on the device, either may be NULL - what a Jacobi preconditioner needs.  Order 1: the closed form of
+ *   Local_K_coronary's diagonal and rho V / 10.
+ * saa_operator_element_bound, saa_operator_stress, saa_operator_nodal_average and saa_operator_stress_error are formulas of
+ *   the linear element: on an order-2 handle they return SAA_E_ARG, say so in saa_last_error and launch nothing.
  */
 typedef struct saa_operator saa_operator;
 int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
                         const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
                         saa_operator **out);
+int saa_operator_create_p2(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *cells10,
+                           const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
+                           saa_operator **out);
+int saa_operator_order(const saa_operator *op);
+int saa_operator_load(saa_operator *op, double fx, double fy, double fz, double *f_dev);
+int saa_operator_diagonal(saa_operator *op, double *diag_k_dev, double *diag_m_dev);
 /* All later work of this handle goes to `hip_stream` (a hipStream_t; NULL = null stream). */
 int saa_operator_set_stream(saa_operator *op, void *hip_stream);
 int saa_operator_apply(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *kx_dev, double *mx_dev,

@@ -19,6 +19,7 @@
 #include "../../include/saa_hip.h"
 #include "saa_device.h"
 #include "saa_modal.h"
+#include "saa_p2.h"
 #include "saa_partition.h"
 #include "saa_plan.h"
 #include "saa_predictor.h"
@@ -816,7 +817,7 @@ extern "C" {
 
 const char *saa_last_error(void) { return g_last_error.c_str(); }
 
-int32_t saa_abi_version(void) { return 14; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error
+int32_t saa_abi_version(void) { return 15; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal
 
 int saa_device_copy_bandwidth(int32_t device, int64_t n_bytes, int32_t reps, double *bytes_per_s) {
   if (!bytes_per_s || n_bytes < 16 || reps < 1) return fail(SAA_E_ARG, "saa_device_copy_bandwidth: bad argument");
@@ -1940,6 +1941,66 @@ int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const 
   return SAA_OK;
 }
 
+int saa_operator_create_p2(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *cells10,
+                           const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
+                           saa_operator **out) {
+  if (!out) return fail(SAA_E_ARG, "saa_operator_create_p2: null output");
+  *out = nullptr;
+  if (n_nodes <= 0 || n_elems < 0 || n_dirichlet < 0 || !xyz || (n_elems > 0 && !cells10) || (n_dirichlet > 0 && !dirichlet_dofs))
+    return fail(SAA_E_ARG, "saa_operator_create_p2: bad argument");
+  if (n_elems > saa::kP2MaxElems || 3 * static_cast<int64_t>(n_nodes) > INT32_MAX)
+    return fail(SAA_E_CAPACITY, "saa_operator_create_p2: more than 214748364 elements (10 * n_elems must fit 32 bits) or 2^31 dofs");
+  if (!(std::isfinite(lambda_) && std::isfinite(mu) && std::isfinite(rho) && rho > 0.0))
+    return fail(SAA_E_ARG, "saa_operator_create_p2: material parameters must be finite and rho > 0");
+  for (int64_t i = 0; i < 10 * static_cast<int64_t>(n_elems); ++i)
+    if (cells10[i] < 0 || cells10[i] >= n_nodes) return fail(SAA_E_ARG, "saa_operator_create_p2: node id out of range");
+  for (int32_t i = 0; i < n_dirichlet; ++i)
+    if (dirichlet_dofs[i] < 0 || dirichlet_dofs[i] >= 3 * n_nodes)
+      return fail(SAA_E_ARG, "saa_operator_create_p2: Dirichlet dof out of range");
+  saa_operator *op = new (std::nothrow) saa_operator;
+  if (!op) return fail(SAA_E_HIP, "saa_operator_create_p2: out of host memory");
+  std::string err;
+  hipError_t e;
+  try {
+    e = saa::modal_create(device, n_nodes, n_elems, xyz, cells10, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, &op->impl, err, 2);
+  } catch (const std::bad_alloc &) {
+    delete op;
+    return fail(SAA_E_HIP, "saa_operator_create_p2: out of host memory");
+  }
+  if (e != hipSuccess) {
+    delete op;
+    (void)hipGetLastError();
+    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_create_p2: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+  }
+  *out = op;
+  return SAA_OK;
+}
+
+int saa_operator_order(const saa_operator *op) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_order: null handle");
+  return saa::modal_order(op->impl);
+}
+
+int saa_operator_load(saa_operator *op, double fx, double fy, double fz, double *f_dev) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_load: null handle");
+  if (!f_dev) return fail(SAA_E_ARG, "saa_operator_load: null output f_dev");
+  if (!(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(fz)))
+    return fail(SAA_E_ARG, "saa_operator_load: the force density must be finite");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_load(op->impl, fx, fy, fz, f_dev);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_load: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_diagonal(saa_operator *op, double *diag_k_dev, double *diag_m_dev) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_diagonal: null handle");
+  if (!diag_k_dev && !diag_m_dev) return fail(SAA_E_ARG, "saa_operator_diagonal: no output");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_diagonal(op->impl, diag_k_dev, diag_m_dev);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_diagonal: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
 int saa_operator_set_stream(saa_operator *op, void *hip_stream) {
   if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_set_stream: null handle");
   saa::modal_set_stream(op->impl, static_cast<hipStream_t>(hip_stream));
@@ -1955,7 +2016,8 @@ int saa_operator_apply(saa_operator *op, int32_t m, const double *x_dev, int64_t
   const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
   if (ldx < n_dof || ldy < n_dof) return fail(SAA_E_ARG, "saa_operator_apply: leading dimension below 3 * n_nodes");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::modal_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy);
+  const hipError_t e = saa::modal_order(op->impl) == 2 ? saa::p2_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy)
+                                                       : saa::modal_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_apply: ") + hipGetErrorString(e));
   return SAA_OK;
 }
@@ -1963,6 +2025,7 @@ int saa_operator_apply(saa_operator *op, int32_t m, const double *x_dev, int64_t
 int saa_operator_element_bound(saa_operator *op, double *omega_e_dev, double *omega_max, int32_t *argmax,
                                int32_t *n_nonpositive) {
   if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_element_bound: null handle");
+  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_element_bound: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
   const hipError_t e = saa::modal_element_bound(op->impl, omega_e_dev, omega_max, argmax, n_nonpositive);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_element_bound: ") + hipGetErrorString(e));
@@ -1973,6 +2036,7 @@ int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_
                         double *von_mises_dev, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
                         double *von_mises_max_dev, int32_t *von_mises_argmax_dev) {
   if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stress: null handle");
+  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_stress: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
   if (m < 1 || m > saa::kModalMaxColumns)
     return fail(SAA_E_ARG, "saa_operator_stress: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
   if (!x_dev) return fail(SAA_E_ARG, "saa_operator_stress: null displacement x_dev");
@@ -1996,6 +2060,7 @@ int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_
 int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const double *elem_dev, int64_t ld_elem, double *node_dev,
                                int64_t ld_node) {
   if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_nodal_average: null handle");
+  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_nodal_average: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
   if (m < 1 || m > saa::kModalMaxColumns)
     return fail(SAA_E_ARG, "saa_operator_nodal_average: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
   if (k < 1 || k > saa::kStressMaxComponents)
@@ -2019,6 +2084,7 @@ int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_e
                               double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
                               int32_t *eta2_argmax_dev) {
   if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stress_error: null handle");
+  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_stress_error: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
   if (m < 1 || m > saa::kModalMaxColumns)
     return fail(SAA_E_ARG, "saa_operator_stress_error: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
   if (!sigma_elem_dev) return fail(SAA_E_ARG, "saa_operator_stress_error: null element stress sigma_elem_dev");

@@ -15,10 +15,10 @@ constexpr int kModalMaxColumns = 16;
 
 // Copies the mesh to `device`, builds the node -> (element, corner) CSR on the host (counting sort: every node's entries in
 // ascending element order) and factors D = L L^T.  Arguments must be validated by the caller except the factorisation
-// (err is set when D is not positive definite).
+// (err is set when D is not positive definite).  order 1: `tets` holds 4 node ids per element; order 2: 10 (saa_p2.h).
 hipError_t modal_create(int device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
                         const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
-                        ModalOp **out, std::string &err);
+                        ModalOp **out, std::string &err, int order = 1);
 void modal_destroy(ModalOp *op);
 int modal_device(const ModalOp *op);
 int32_t modal_n_nodes(const ModalOp *op);

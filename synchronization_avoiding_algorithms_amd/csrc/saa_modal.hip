@@ -304,7 +304,7 @@ void modal_set_stream(ModalOp *op, hipStream_t stream) { op->stream = stream; }
 
 hipError_t modal_create(int device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
                         const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
-                        ModalOp **out, std::string &err) {
+                        ModalOp **out, std::string &err, int order) {
   *out = nullptr;
   // D (commons.py:25-31, Voigt xx, yy, zz, yz, xz, xy) = L L^T
   double D[6][6] = {};
@@ -329,7 +329,7 @@ hipError_t modal_create(int device, int32_t n_nodes, int32_t n_elems, const doub
     }
   }
   // node -> (element, corner) CSR by a counting sort: entries of a node in ascending element order
-  const int64_t n_pairs = 4 * static_cast<int64_t>(n_elems);
+  const int64_t n_pairs = (order == 2 ? 10 : 4) * static_cast<int64_t>(n_elems);
   std::vector<int64_t> offsets(static_cast<size_t>(n_nodes) + 1, 0);
   for (int64_t i = 0; i < n_pairs; ++i) ++offsets[static_cast<size_t>(tets[i]) + 1];
   for (int32_t v = 0; v < n_nodes; ++v) offsets[v + 1] += offsets[v];
@@ -344,6 +344,7 @@ hipError_t modal_create(int device, int32_t n_nodes, int32_t n_elems, const doub
   ModalOp *op = new (std::nothrow) ModalOp;
   if (!op) return hipErrorOutOfMemory;
   op->device = device;
+  op->order = order;
   op->n_nodes = n_nodes;
   op->n_elems = n_elems;
   op->lam = lambda_;
@@ -417,6 +418,13 @@ hipError_t modal_apply(ModalOp *op, int32_t m, const double *x, int64_t ldx, dou
   if (mx)
     hipLaunchKernelGGL(node_sum_kernel, ngrid, dim3(kThreads), 0, op->stream, op->n_nodes, m, op->offsets, op->pairs, op->free_mask,
                        op->scratch_m, stride, mx, ldy);
+  return hipGetLastError();
+}
+
+hipError_t modal_node_sum(ModalOp *op, int32_t m, const double *contrib, int64_t stride, double *y, int64_t ldy) {
+  const dim3 ngrid(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads));
+  hipLaunchKernelGGL(node_sum_kernel, ngrid, dim3(kThreads), 0, op->stream, op->n_nodes, m, op->offsets, op->pairs, op->free_mask,
+                     contrib, stride, y, ldy);
   return hipGetLastError();
 }
 

@@ -9,15 +9,16 @@ namespace saa {
 
 struct ModalOp {
   int device = 0;
+  int order = 1;  // 1: 4-node elements, 2: 10-node elements (saa_p2.hip)
   int32_t n_nodes = 0, n_elems = 0;
   double lam = 0.0, mu = 0.0, rho = 0.0;
   double L[6][6] = {};  // D = L L^T (lower triangular)
   double *xyz = nullptr;        // 3 * n_nodes
-  int32_t *tets = nullptr;      // 4 * n_elems
+  int32_t *tets = nullptr;      // 4 * n_elems (order 2: 10 * n_elems)
   double *free_mask = nullptr;  // 3 * n_nodes: 1 on free dofs, 0 on Dirichlet dofs
   int64_t *offsets = nullptr;   // n_nodes + 1
-  int32_t *pairs = nullptr;     // 4 * n_elems: 4 * element + corner, grouped by node, ascending
-  double *scratch_k = nullptr, *scratch_m = nullptr;  // 12 * n_elems * cap_columns each
+  int32_t *pairs = nullptr;     // 4 * n_elems: 4 * element + corner, grouped by node, ascending (order 2: 10 *)
+  double *scratch_k = nullptr, *scratch_m = nullptr;  // 12 * n_elems * cap_columns each (order 2: 30 *)
   int32_t cap_k = 0, cap_m = 0;
   double *part_val = nullptr;   // per-workgroup maxima of the element bound
   int32_t *part_idx = nullptr, *part_cnt = nullptr;
@@ -31,6 +32,10 @@ struct ModalOp {
   double *st_part_vm = nullptr;  // [column][workgroup] partial von Mises maxima
   int32_t *st_part_idx = nullptr;
 };
+
+// The node pass of saa_modal.hip on any [column][pair][3] contributions of this handle's CSR: y[j][3v + c] = sum of node
+// v's entries of contrib + j * stride in ascending element order, 0 on Dirichlet dofs.  Enqueued on the op's stream.
+hipError_t modal_node_sum(ModalOp *op, int32_t m, const double *contrib, int64_t stride, double *y, int64_t ldy);
 
 // Gradients of the four shape functions (rows) and detJ; J columns are the edges x_a - x_0 (Shape_function_Deriv.py:60-67).
 __device__ __forceinline__ double element_gradients(const double *__restrict__ xyz, const int32_t *__restrict__ tets,

@@ -131,10 +131,18 @@ def data_prepare(mesh, n_steps=100000, save_every=1, out_dir=".", rank=0, world=
     return path, store
 
 
-def steady_state(mesh, out_dir=".", device=0, tol=1e-12, verbose=False, E=None, nu=None, rho=None, fz=None):
+def _quadratic(mesh):
+    """The mesh with 10-node cells: as read if the file holds ``tetra10``, else elevated (``mesh.to_quadratic``)."""
+    from .mesh import to_quadratic
+
+    return mesh if "tetra10" in mesh.cells_dict else to_quadratic(mesh)
+
+
+def steady_state(mesh, out_dir=".", device=0, tol=1e-12, verbose=False, E=None, nu=None, rho=None, fz=None, order=1):
     """``Data_prepare.py:157-168`` (rank 0 in the reference): the steady solution ``d = K^-1 F`` of the whole mesh
     under the un-ramped load, written as point data of ``Results/Static/steady_distributed.vtk``.  Matrix-free
-    preconditioned CG on one GPU (:mod:`steady`) instead of the dense solve."""
+    preconditioned CG on one GPU (:mod:`steady`) instead of the dense solve.  ``order=2``: quadratic tetrahedra (what the
+    reference's ``p = 2`` gives), clamped on every node of ``x = 0``, written with type-24 cells."""
     from . import fem_setup as fs
     from .mesh import clamp_nodes
     from .solver import HipExplicitSolver
@@ -145,6 +153,20 @@ def steady_state(mesh, out_dir=".", device=0, tol=1e-12, verbose=False, E=None, 
     rho = DEFAULTS["rho"] if rho is None else rho
     fz = DEFAULTS["fz"] if fz is None else fz
     lmd, mu = fs.lame(E, nu)
+    if order == 2:
+        from .mesh import plane_nodes
+        from .modal import ModalOperator
+        from .steady import steady_solve_operator
+
+        mesh = _quadratic(mesh)
+        with ModalOperator(mesh.points, mesh.tets10, fs.node_to_dof(plane_nodes(mesh.points)), lmd, mu, rho, device) as op:
+            d, iters, rel = steady_solve_operator(op, op.load((0.0, -fz, -fz)), tol=tol)
+        d = d.reshape(-1, 1)
+        if verbose:
+            print(f"steady solve (order 2): {iters} CG iterations, relative residual {rel:.2e}, max|d| = {np.abs(d).max():.6e}")
+        return write_vtk_point_data(os.path.join(out_dir, STEADY_PATH), mesh.points, mesh.tets10, d), d
+    if order != 1:
+        raise ValueError("order must be 1 or 2")
     lumped, fpre, min_edge = fs.device_setup_fields(mesh.points, mesh.tets, rho, fz, device)
     dirichlet = fs.node_to_dof(clamp_nodes(mesh))
     sol = HipExplicitSolver(mesh.points, mesh.tets, lumped, fpre, dirichlet, lmd, mu,
@@ -205,14 +227,24 @@ def online_predictor(mesh, n_steps=100000, save_every=1, out_dir=".", rank=0, wo
     return path, store, hist
 
 
-def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None):
+def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
     """Stable time step and lowest ``k`` natural frequencies of the whole mesh, clamped on ``x = 0`` like the other
     drivers (``Data_prepare.py:127-136``), on one GPU (:func:`modal.modal_report`).  Does not change how any other
-    driver picks ``dt``."""
+    driver picks ``dt``.  ``order=2``: the frequencies of the quadratic discretisation (:func:`modal.modal_report_p2`),
+    without the time-step figures of the explicit p = 1 solver."""
     from .mesh import clamp_nodes
     from .modal import modal_report
 
     p = {name: DEFAULTS[name] if v is None else v for name, v in (("E", E), ("nu", nu), ("rho", rho), ("gamma", gamma))}
+    if order == 2:
+        from .mesh import plane_nodes
+        from .modal import modal_report_p2
+
+        mesh = _quadratic(mesh)
+        p.pop("gamma")
+        return modal_report_p2(mesh.points, mesh.tets10, plane_nodes(mesh.points), k=k, device=device, **p)
+    if order != 1:
+        raise ValueError("order must be 1 or 2")
     return modal_report(mesh.points, mesh.tets, clamp_nodes(mesh), k=k, device=device, **p)
 
 
@@ -559,6 +591,8 @@ def main(argv=None):
     ap.add_argument("--modeled", action="store_true", help="stress, estimate: the modelled run too, and its differences")
     ap.add_argument("--history", action="store_true", help="stress: every column's strain energy and von Mises maximum")
     ap.add_argument("--no-vtk", action="store_true", help="stress, estimate: no VTK files")
+    ap.add_argument("--order", type=int, choices=[1, 2], default=1,
+                    help="steady_state, modal: 2 = quadratic tetrahedra (the mesh is elevated unless the file holds tetra10)")
     args = ap.parse_args(argv)
     rank, world, local = _dist_env()
     if args.command in ("modal", "stress", "estimate"):  # one whole mesh on one GPU; prints one JSON object
@@ -571,7 +605,7 @@ def main(argv=None):
         mesh = (delaunay_beam(args.synthetic) if args.delaunay else structured_beam(args.synthetic)) if args.synthetic \
             else read_vtk(args.mesh)
         if args.command == "modal":
-            print(json.dumps(modal(mesh, k=args.k, device=local)))
+            print(json.dumps(modal(mesh, k=args.k, device=local, order=args.order)))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
             print(json.dumps(estimate(mesh, args.out, cols, modeled=args.modeled, vtk=not args.no_vtk, device=local)))
@@ -586,7 +620,7 @@ def main(argv=None):
     elif args.command == "steady_state":
         if rank != 0:
             return
-        path, _ = steady_state(_load_mesh(args), args.out, device=local, verbose=True)
+        path, _ = steady_state(_load_mesh(args), args.out, device=local, verbose=True, order=args.order)
     elif args.command == "shared_extraction":
         path, _ = shared_extraction(args.out, rank)
     elif args.command == "model_training":

@@ -11,6 +11,7 @@ module provides
   ``SURVEY.md`` §8(d): cubes split into 6 positively oriented Kuhn tetrahedra over the
   box of ``Mesh_info/beam_US.geo:2-16``,
 * :func:`delaunay_beam` – the same box meshed without any lattice (Delaunay tetrahedra of random points),
+* :func:`to_quadratic` – the 10-node (``p = 2``) elevation of a 4-node mesh for the steady solve and the modal analysis,
 * :func:`slab_partition` / :func:`rcb_partition` – element partition vectors playing the
   role of ``part_mesh_kway``'s ``epart`` (one part per GPU).
 
@@ -22,7 +23,7 @@ import numpy as np
 
 # VTK cell type ids -> meshio-style names (the reference indexes cells_dict by name,
 # Data_prepare.py:59-60)
-_VTK_TYPES = {1: "vertex", 3: "line", 5: "triangle", 10: "tetra"}
+_VTK_TYPES = {1: "vertex", 3: "line", 5: "triangle", 10: "tetra", 24: "tetra10"}
 
 
 class Mesh:
@@ -35,6 +36,11 @@ class Mesh:
     @property
     def tets(self):
         return self.cells_dict["tetra"]
+
+    @property
+    def tets10(self):
+        """``(ne, 10)`` cells of a quadratic mesh (:func:`to_quadratic`, VTK type 24); KeyError on a linear one."""
+        return self.cells_dict["tetra10"]
 
     @property
     def triangles(self):
@@ -209,6 +215,33 @@ def delaunay_beam(n: int, length: float = 25.0, width: float = 1.0, height: floa
     hull = tri.convex_hull
     hull = hull[np.all(pts[hull, 0] < 1e-12, axis=1) & np.all(remap[hull] >= 0, axis=1)]
     return Mesh(pts[used], {"tetra": remap[tets], "triangle": remap[hull]})
+
+
+#: mid-edge nodes 4..9 of the 10-node tetrahedron sit on these vertex pairs (the reference's Shape_function_Deriv.py:14-23,
+#: VTK cell type 24)
+TET10_EDGES = ((0, 1), (1, 2), (0, 2), (0, 3), (1, 3), (2, 3))
+
+
+def to_quadratic(mesh: Mesh) -> Mesh:
+    """The 10-node elevation of a 4-node mesh.  Vertices keep their ids; one node per unique edge is appended after them,
+    in lexicographic order of ``(min id, max id)``, at the edge's midpoint.  The result carries ``cells_dict["tetra10"]``
+    ``(ne, 10)`` (property ``tets10``) in the local order of :data:`TET10_EDGES`; ``tetra`` and ``triangle`` are kept
+    unchanged.  Deterministic."""
+    tets = mesh.tets
+    n = len(mesh.points)
+    pairs = np.stack([tets[:, [a for a, _ in TET10_EDGES]], tets[:, [b for _, b in TET10_EDGES]]], axis=2)  # (ne, 6, 2)
+    lo, hi = pairs.min(axis=2), pairs.max(axis=2)
+    key = lo * np.int64(n) + hi
+    uniq, inv = np.unique(key.ravel(), return_inverse=True)          # sorted keys = lexicographic (lo, hi)
+    mid = 0.5 * (mesh.points[uniq // n] + mesh.points[uniq % n])
+    cells = dict(mesh.cells_dict)
+    cells["tetra10"] = np.concatenate([tets, n + inv.reshape(-1, 6)], axis=1)
+    return Mesh(np.concatenate([mesh.points, mid]), cells)
+
+
+def plane_nodes(points, tol: float = 1e-9) -> np.ndarray:
+    """Every node on ``x = 0``, ascending - the clamp set of a quadratic mesh (mid-edge nodes included)."""
+    return np.nonzero(np.abs(np.asarray(points)[:, 0]) < tol)[0]
 
 
 def clamp_nodes(mesh: Mesh, tol: float = 1e-9) -> np.ndarray:

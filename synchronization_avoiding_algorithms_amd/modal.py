@@ -75,7 +75,12 @@ def element_omega(points, cells, lmd, mu, rho):
 
 class ModalOperator:
     """One ``saa_operator`` handle: the whole mesh on one GPU in the caller's numbering, the stiffness / consistent-mass
-    block apply with Dirichlet masking, and the element stable-frequency bound.  float64 CUDA tensors in and out."""
+    block apply with Dirichlet masking, and the element stable-frequency bound.  float64 CUDA tensors in and out.
+
+    ``cells`` of shape ``(ne, 10)`` (``mesh.to_quadratic``) make an order-2 handle (``saa_operator_create_p2``): quadratic
+    tetrahedra, ``K`` with the reference's 4-point rule, ``M`` with the 14-point rule.  ``apply``, ``load`` and
+    ``diagonal`` work on either order; ``element_bound`` and the stress recovery are linear-element formulas and raise
+    on an order-2 handle."""
 
     MAX_COLUMNS = 16
 
@@ -85,20 +90,24 @@ class ModalOperator:
         self._lib = _lib.load()
         self._h = C.c_void_p()
         pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1))
-        tets = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1))
+        cells = np.asarray(cells, dtype=np.int32)
+        per_elem = 10 if cells.ndim == 2 and cells.shape[1] == 10 else 4
+        tets = np.ascontiguousarray(cells.reshape(-1))
         dd = np.ascontiguousarray(np.asarray(dirichlet_dofs, dtype=np.int32).reshape(-1))
-        self.n_nodes, self.n_elems = pts.size // 3, tets.size // 4
+        self.n_nodes, self.n_elems = pts.size // 3, tets.size // per_elem
         self.n_dof = 3 * self.n_nodes
         self.device = int(device)
         self.torch_device = torch.device("cuda", self.device)
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        _lib.check(self._lib.saa_operator_create(
+        create = self._lib.saa_operator_create_p2 if per_elem == 10 else self._lib.saa_operator_create
+        _lib.check(create(
             self.device, self.n_nodes, self.n_elems, pts.ctypes.data_as(dp), tets.ctypes.data_as(ip) if tets.size else None,
             dd.ctypes.data_as(ip) if dd.size else None, int(dd.size), float(lmd), float(mu), float(rho), C.byref(self._h)))
         free = torch.ones(self.n_dof, dtype=torch.float64, device=self.torch_device)
         if dd.size:
             free[torch.as_tensor(dd.astype(np.int64), device=self.torch_device)] = 0.0
         self.free = free
+        self.order = int(self._lib.saa_operator_order(self._h))
         self.set_stream(torch.cuda.current_stream(self.torch_device).cuda_stream)
 
     def close(self):
@@ -148,6 +157,26 @@ class ModalOperator:
         if vec:
             return (KX.reshape(-1) if k else None), (MX.reshape(-1) if m else None)
         return KX, MX
+
+    def load(self, f):
+        """The consistent body-force vector of the force density ``f = (fx, fy, fz)`` (``Fe`` of ``Local_MKF`` assembled,
+        0 on Dirichlet dofs) as an ``(n_dof,)`` CUDA tensor."""
+        import torch
+
+        fx, fy, fz = (float(c) for c in np.asarray(f, dtype=np.float64).reshape(-1))
+        out = torch.empty(self.n_dof, dtype=torch.float64, device=self.torch_device)
+        _lib.check(self._lib.saa_operator_load(self._h, fx, fy, fz, C.c_void_p(out.data_ptr())))
+        return out
+
+    def diagonal(self, k=True, m=True):
+        """``(diag K, diag M)`` of the masked operator (0 on Dirichlet dofs; either None when not asked for)."""
+        import torch
+
+        dk = torch.empty(self.n_dof, dtype=torch.float64, device=self.torch_device) if k else None
+        dm = torch.empty(self.n_dof, dtype=torch.float64, device=self.torch_device) if m else None
+        _lib.check(self._lib.saa_operator_diagonal(self._h, C.c_void_p(dk.data_ptr()) if k else None,
+                                                   C.c_void_p(dm.data_ptr()) if m else None))
+        return dk, dm
 
     def element_bound(self, return_omega=False) -> dict:
         """``omega_max`` bound ``max_e omega_e``, its element, the count of elements with signed volume <= 0 and
@@ -367,14 +396,39 @@ def stable_time_step(points, cells, dirichlet_nodes, E, nu, rho, gamma=0.9, devi
 
 
 def device_lowest_modes(op: ModalOperator, points, cells, lmd, mu, k, **kw):
-    """:func:`lowest_modes` on the GPU operator, Jacobi-preconditioned with ``diag(K)``."""
+    """:func:`lowest_modes` on the GPU operator, Jacobi-preconditioned with ``diag(K)`` (order 2: ``op.diagonal()``)."""
     import torch
 
     from .steady import stiffness_diagonal
 
-    diag = torch.as_tensor(stiffness_diagonal(points, cells, lmd, mu), dtype=torch.float64, device=op.torch_device)
+    if op.order == 2:
+        diag = op.diagonal(k=True, m=False)[0]
+    else:
+        diag = torch.as_tensor(stiffness_diagonal(points, cells, lmd, mu), dtype=torch.float64, device=op.torch_device)
     return lowest_modes(lambda X: op.apply(X)[0], lambda X: op.apply(X, k=False, m=True)[1], k, op.free,
                         diag_k=diag * op.free, **kw)
+
+
+def modal_report_p2(points, cells10, dirichlet_nodes, E=1e6, nu=0.3, rho=1.0, k=6, device=0) -> dict:
+    """What ``drivers modal --order 2`` prints: the order, the sizes, the lowest ``k`` frequencies of the quadratic
+    discretisation with their residuals, iteration counts and wall times.  The time-step figures and the critical
+    element of :func:`modal_report` belong to the explicit p = 1 solver and are left out."""
+    from . import fem_setup as fs
+
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    cells10 = np.ascontiguousarray(cells10, dtype=np.int32)
+    lmd, mu = fs.lame(E, nu)
+    dirichlet = fs.node_to_dof(dirichlet_nodes)
+    t0 = time.perf_counter()
+    with ModalOperator(points, cells10, dirichlet, lmd, mu, rho, device) as op:
+        t1 = _sync(op.torch_device)
+        modes = device_lowest_modes(op, points, cells10, lmd, mu, k)
+        t2 = _sync(op.torch_device)
+    return {"order": 2, "n_nodes": len(points), "n_elems": len(cells10), "n_free_dofs": 3 * len(points) - len(dirichlet),
+            "frequencies_hz": modes["frequencies_hz"].tolist(), "residuals": modes["residuals"].tolist(),
+            "modes_converged": modes["converged"], "outer_iterations": modes["outer_iterations"],
+            "inner_iterations": modes["inner_iterations"],
+            "seconds": {"operator_create": t1 - t0, "lowest_modes": t2 - t1}}
 
 
 def modal_report(points, cells, dirichlet_nodes, E=1e6, nu=0.3, rho=1.0, gamma=0.9, k=6, device=0) -> dict:

@@ -76,9 +76,58 @@ def steady_solve(solver, f_ext, dirichlet_dofs, diag=None, tol=1e-12, max_iter=N
     return x.cpu().numpy().reshape(-1, 1), it, rel
 
 
+def steady_solve_operator(op, b, tol=1e-12, max_iter=None, check_every=25):
+    """Jacobi-PCG for ``K d = b`` on an operator handle (:class:`modal.ModalOperator`) of either order, for one right-hand
+    side ``(n_dof,)`` or several ``(m, n_dof)`` (float64 tensors on the operator's device, or arrays).  The loop of
+    :func:`steady_solve`, one independent iteration per right-hand side batched through the block apply and
+    preconditioned with ``op.diagonal()``; Dirichlet dofs are eliminated by the operator's mask.  A right-hand side is
+    converged when ``|r| <= tol |b|``.  Returns ``(d, iterations, relative residual)``: ``d`` a NumPy array of the shape
+    of ``b``, the residual that of the iteration as :func:`steady_solve` reports it, the largest over the right-hand
+    sides."""
+    import torch
+
+    B = b if torch.is_tensor(b) else torch.as_tensor(np.asarray(b, dtype=np.float64))
+    B = B.to(device=op.torch_device, dtype=torch.float64)
+    vec = B.dim() == 1
+    B = B.reshape(-1, op.n_dof) * op.free
+    diag_k, _ = op.diagonal(k=True, m=False)
+    minv = torch.where(diag_k > 0, op.free / torch.where(diag_k > 0, diag_k, 1.0), op.free)
+    X = torch.zeros_like(B)
+    bnorm = torch.linalg.vector_norm(B, dim=1)
+    live = bnorm > 0
+    safe = torch.where(live, bnorm, 1.0)
+    R = B.clone()
+    Z = minv * R
+    P = Z.clone()
+    rz = (R * Z).sum(dim=1)
+    max_iter = max_iter or 20 * op.n_dof
+    it = 0
+    running = bool(live.any())
+    while it < max_iter and running:
+        AP = op.apply(P)[0]
+        pap = (P * AP).sum(dim=1)
+        ok = live & (pap > 0)
+        alpha = torch.where(ok, rz / torch.where(ok, pap, 1.0), 0.0)
+        X += alpha[:, None] * P
+        R -= alpha[:, None] * AP
+        Z = minv * R
+        rz_new = (R * Z).sum(dim=1)
+        beta = torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, 1.0), 0.0)
+        P = Z + beta[:, None] * P
+        rz = rz_new
+        it += 1
+        if it % check_every == 0:                # the only host synchronisation
+            live = live & (torch.linalg.vector_norm(R, dim=1) > tol * bnorm)
+            running = bool(live.any())
+    rel = float((torch.linalg.vector_norm(R, dim=1) / safe).max())
+    d = X.cpu().numpy()
+    return (d[0] if vec else d), it, rel
+
+
 def write_vtk_point_data(path, points, cells, displacement):
     """Legacy-VTK file with the mesh and the point data ``displacement-x/-y/-z`` - the arrays the reference hands to
-    ``meshio.write_points_cells`` at ``Data_prepare.py:165-168`` (ASCII here)."""
+    ``meshio.write_points_cells`` at ``Data_prepare.py:165-168`` (ASCII here).  4-column cells are written as VTK type 10,
+    10-column cells (quadratic tetrahedra) as type 24."""
     import os
 
     points, cells = np.asarray(points, dtype=np.float64), np.asarray(cells)
@@ -88,10 +137,11 @@ def write_vtk_point_data(path, points, cells, displacement):
         fh.write("# vtk DataFile Version 4.2\nsteady solution d = K^-1 F\nASCII\nDATASET UNSTRUCTURED_GRID\n")
         fh.write(f"POINTS {len(points)} double\n")
         np.savetxt(fh, points, fmt="%.17g")
-        fh.write(f"CELLS {len(cells)} {5 * len(cells)}\n")
-        np.savetxt(fh, np.column_stack([np.full(len(cells), 4), cells]), fmt="%d")
+        width = cells.shape[1] if cells.ndim == 2 else 4
+        fh.write(f"CELLS {len(cells)} {(width + 1) * len(cells)}\n")
+        np.savetxt(fh, np.column_stack([np.full(len(cells), width), cells]), fmt="%d")
         fh.write(f"CELL_TYPES {len(cells)}\n")
-        np.savetxt(fh, np.full(len(cells), 10), fmt="%d")
+        np.savetxt(fh, np.full(len(cells), 24 if width == 10 else 10), fmt="%d")
         fh.write(f"POINT_DATA {len(points)}\n")
         for c, name in enumerate(("displacement-x", "displacement-y", "displacement-z")):
             fh.write(f"SCALARS {name} double 1\nLOOKUP_TABLE default\n")
