@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -411,6 +411,53 @@ int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_e
                               double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
                               int32_t *eta2_argmax_dev);
 int saa_operator_destroy(saa_operator *op);
+
+/*
+ * Explicit dynamics on the operator handle, either order: the time loop of Data_prepare.py:215-240 for one whole mesh on one
+ * GPU.  The reference stops before it for its second element ("p=2 only works for steady case, dynamic case requires
+ * advanced lumping method", Data_prepare.py:43; "dynamics problem for p=2 TBD", Mat_construction.py:31).  All pointers are
+ * device pointers; work is enqueued on the operator's stream with no host synchronisation unless stated; no floating-point
+ * atomics, bitwise repeatable.
+ *
+ * saa_operator_lumped_mass: 3*n_nodes doubles, one value on a node's three dofs; the Dirichlet mask is NOT applied (the mass
+ *   stays positive there).  Order 2 is HRZ lumping, because the reference's row sum (lumping_to_vec, commons.py:103-107)
+ *   gives every vertex of a quadratic tetrahedron the negative mass rho integral N_vertex = -rho V/20: per element
+ *   m_a = rho (sum_q w_q detJ_q) I_a / sum_b I_b with I_a = sum_q w_q detJ_q N_a(xi_q)^2 over the 14-point rule (on a straight
+ *   element rho V/36 at a vertex, 4 rho V/27 on an edge), summed over a node's elements in ascending element order.  Order 1
+ *   is the row sum rho V_e / 4 per vertex (V_e = detJ / 6, signed): the lumped mass of saa_setup_fields.
+ * saa_operator_stepper_create: a stepper that BORROWS the operator (which must outlive it, and whose stream it uses) and
+ *   copies the mass and the un-ramped load (3*n_nodes each); state d0 = dn = 0, tn = 0.  SAA_E_ARG on null pointers,
+ *   dt <= 0, alpha < 0, or a mass that is not > 0 at a node that has elements (checked once; synchronises the stream).
+ *   The edge-length rule of Data_prepare.py:147 is NOT a stable dt for the quadratic element (1.56 x 2/omega_max on the
+ *   36-tet beam): take dt from omega_max of M_L^-1 K (modal.stable_time_step_operator).
+ * saa_operator_stepper_step: nsteps (0: nothing) steps of Dynamic_solver.py:12-20 on one rank,
+ *     f_int = K d0 (masked operator),  f_ext = f * (ramp ? min(tn, 1) : 1),
+ *     d1 = (dt^2 (f_ext - f_int) + 2 m d0 - m dn + dt/2 m alpha dn) / (m + alpha m dt / 2),  d1[Dirichlet] = 0,  tn += dt,
+ *   d1 = 0 at a node that has no element (whatever its mass).  Two launches per step: the K element pass for one column
+ *   and a node pass fused with the update, which overwrites dn (the state is two buffers and a swap); f_int is never
+ *   written to memory.  On an order-1 handle this is NOT a rival of saa_step, whose kernel keeps the partition in LDS over
+ *   several steps: it exists so that one stepper serves both orders and saa_step is a second oracle for it.
+ * saa_operator_stepper_set_state: d0 = d^n, dn = d^(n-1) (NULL = zeros), tn.  saa_operator_stepper_get_state: into
+ *   caller buffers (either may be NULL); synchronises the stream.
+ * saa_operator_stepper_set_recorder: exactly saa_set_recorder - row-major (3*n_nodes, n_cols), the d^(n+1) of step index i
+ *   goes to column i / save_every whenever i % save_every == 0 and that column exists; NULL switches it off.
+ * saa_operator_stepper_set_option: "stored_geometry" 0 (default) / 1 - the order-2 element pass rebuilds J^-1 and w detJ at
+ *   its four points from the thirty gathered coordinates every step / reads them from a table built once, 40 doubles per
+ *   element stored component-major (profiles/p2_step_kernel_stats.txt has the comparison).  No effect on order 1.
+ *   "passes" 3 (default) / 1 / 2 is a measurement aid for tools/p2_step_point.py: a step launches both passes / the element
+ *   pass only / the node pass only; the state and tn advance only with 3.
+ */
+int saa_operator_lumped_mass(saa_operator *op, double *mass_dev);
+typedef struct saa_operator_stepper saa_operator_stepper;
+int saa_operator_stepper_create(saa_operator *op, const double *mass_dev, const double *f_ext_dev, double dt, double alpha,
+                                int32_t ramp, saa_operator_stepper **out);
+int saa_operator_stepper_set_state(saa_operator_stepper *st, const double *d0_dev, const double *dn_dev, double tn);
+int saa_operator_stepper_get_state(saa_operator_stepper *st, double *d0_dev, double *dn_dev, double *tn);
+int saa_operator_stepper_set_recorder(saa_operator_stepper *st, double *traj_dev, int64_t n_cols, int32_t save_every,
+                                      int64_t next_step_index);
+int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *name, double value);
+int saa_operator_stepper_step(saa_operator_stepper *st, int32_t nsteps);
+int saa_operator_stepper_destroy(saa_operator_stepper *st);
 
 /*
  * Shared-node predictor: the per-rank LSTM encoder-decoder of Tools/DNN_tools.py:16-98 (2-layer bidirectional encoder of

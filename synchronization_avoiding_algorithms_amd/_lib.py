@@ -18,10 +18,10 @@ LIB_PATH = os.environ.get("SAA_LIB_PATH") or os.path.join(_HERE, "libsaa_hip.so"
 DIAG_LIB_PATH = os.path.join(_HERE, "libsaa_hip_diag.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "saa_hip.h")
 SOURCES = ["saa_plan.cpp", "saa_partition.cpp", "saa_kernels.hip", "saa_setup.hip", "saa_predictor.hip", "saa_topology.hip", "saa_modal.hip",
-           "saa_stress.hip", "saa_p2.hip", "saa_api.cpp"]
+           "saa_stress.hip", "saa_p2.hip", "saa_opstep.hip", "saa_api.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-ldl"]
 
-ABI_VERSION = 15  # what saa_abi_version() of a matching library returns (include/saa_hip.h)
+ABI_VERSION = 16  # what saa_abi_version() of a matching library returns (include/saa_hip.h)
 SAA_OK, SAA_E_ARG, SAA_E_HIP, SAA_E_STATE, SAA_E_CAPACITY = 0, -1, -2, -3, -4
 
 
@@ -144,6 +144,14 @@ SIGNATURES = {
     "saa_operator_stress_error": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "saa_operator_destroy": (C.c_int, [_H]),
+    "saa_operator_lumped_mass": (C.c_int, [_H, C.c_void_p]),
+    "saa_operator_stepper_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.POINTER(_H)]),
+    "saa_operator_stepper_set_state": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double]),
+    "saa_operator_stepper_get_state": (C.c_int, [_H, C.c_void_p, C.c_void_p, _dp]),
+    "saa_operator_stepper_set_recorder": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]),
+    "saa_operator_stepper_set_option": (C.c_int, [_H, C.c_char_p, C.c_double]),
+    "saa_operator_stepper_step": (C.c_int, [_H, C.c_int32]),
+    "saa_operator_stepper_destroy": (C.c_int, [_H]),
 }
 
 _lib = None

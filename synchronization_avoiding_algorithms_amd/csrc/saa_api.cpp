@@ -19,6 +19,7 @@
 #include "../../include/saa_hip.h"
 #include "saa_device.h"
 #include "saa_modal.h"
+#include "saa_opstep.h"
 #include "saa_p2.h"
 #include "saa_partition.h"
 #include "saa_plan.h"
@@ -817,7 +818,7 @@ extern "C" {
 
 const char *saa_last_error(void) { return g_last_error.c_str(); }
 
-int32_t saa_abi_version(void) { return 15; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal
+int32_t saa_abi_version(void) { return 16; }  // 4: saa_part_mesh_kway, saa_setup_fields; 5: saa_set_deterministic; 6: saa_device_copy_bandwidth; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*
 
 int saa_device_copy_bandwidth(int32_t device, int64_t n_bytes, int32_t reps, double *bytes_per_s) {
   if (!bytes_per_s || n_bytes < 16 || reps < 1) return fail(SAA_E_ARG, "saa_device_copy_bandwidth: bad argument");
@@ -2117,6 +2118,95 @@ int saa_operator_destroy(saa_operator *op) {
   if (!op) return SAA_OK;
   saa::modal_destroy(op->impl);
   delete op;
+  return SAA_OK;
+}
+
+// ---- explicit dynamics on the operator handle (saa_opstep.hip) -----------------------------------------------------
+int saa_operator_lumped_mass(saa_operator *op, double *mass_dev) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_lumped_mass: null handle");
+  if (!mass_dev) return fail(SAA_E_ARG, "saa_operator_lumped_mass: null output mass_dev");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_lumped_mass(op->impl, mass_dev);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_lumped_mass: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+struct saa_operator_stepper {
+  saa::OpStepper *impl = nullptr;
+};
+
+int saa_operator_stepper_create(saa_operator *op, const double *mass_dev, const double *f_ext_dev, double dt, double alpha,
+                                int32_t ramp, saa_operator_stepper **out) {
+  if (!out) return fail(SAA_E_ARG, "saa_operator_stepper_create: null output");
+  *out = nullptr;
+  if (!(std::isfinite(dt) && dt > 0.0)) return fail(SAA_E_ARG, "saa_operator_stepper_create: dt must be finite and > 0");
+  if (!(std::isfinite(alpha) && alpha >= 0.0)) return fail(SAA_E_ARG, "saa_operator_stepper_create: alpha must be finite and >= 0");
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stepper_create: null handle");
+  if (!mass_dev || !f_ext_dev) return fail(SAA_E_ARG, "saa_operator_stepper_create: null mass_dev or f_ext_dev");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  saa_operator_stepper *st = new (std::nothrow) saa_operator_stepper;
+  if (!st) return fail(SAA_E_HIP, "saa_operator_stepper_create: out of host memory");
+  std::string err;
+  const hipError_t e = saa::opstep_create(op->impl, mass_dev, f_ext_dev, dt, alpha, ramp != 0, &st->impl, err);
+  if (e != hipSuccess) {
+    delete st;
+    (void)hipGetLastError();
+    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_stepper_create: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+  }
+  *out = st;
+  return SAA_OK;
+}
+
+int saa_operator_stepper_set_state(saa_operator_stepper *st, const double *d0_dev, const double *dn_dev, double tn) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_state: null handle");
+  if (!std::isfinite(tn)) return fail(SAA_E_ARG, "saa_operator_stepper_set_state: tn must be finite");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_set_state(st->impl, d0_dev, dn_dev, tn);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_state: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_get_state(saa_operator_stepper *st, double *d0_dev, double *dn_dev, double *tn) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_get_state: null handle");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_get_state(st->impl, d0_dev, dn_dev, tn);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_get_state: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_set_recorder(saa_operator_stepper *st, double *traj_dev, int64_t n_cols, int32_t save_every,
+                                      int64_t next_step_index) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_recorder: null handle");
+  if (traj_dev && (n_cols <= 0 || save_every <= 0 || next_step_index < 0))
+    return fail(SAA_E_ARG, "saa_operator_stepper_set_recorder: bad argument");
+  saa::opstep_set_recorder(st->impl, traj_dev, traj_dev ? n_cols : 0, traj_dev ? save_every : 1, traj_dev ? next_step_index : 0);
+  return SAA_OK;
+}
+
+int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *name, double value) {
+  if (!st || !st->impl || !name) return fail(SAA_E_ARG, "saa_operator_stepper_set_option: null handle or name");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  hipError_t e = hipSuccess;
+  if (!saa::opstep_set_option(st->impl, name, value, &e))
+    return fail(SAA_E_ARG, std::string("saa_operator_stepper_set_option: unknown option or value: ") + name + " (stored_geometry 0 / 1, passes 1 / 2 / 3)");
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_option: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_step(saa_operator_stepper *st, int32_t nsteps) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step: null handle");
+  if (nsteps < 0) return fail(SAA_E_ARG, "saa_operator_stepper_step: nsteps < 0");
+  if (nsteps == 0) return SAA_OK;
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_step(st->impl, nsteps);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_destroy(saa_operator_stepper *st) {
+  if (!st) return SAA_OK;
+  saa::opstep_destroy(st->impl);
+  delete st;
   return SAA_OK;
 }
 

@@ -421,6 +421,14 @@ hipError_t modal_apply(ModalOp *op, int32_t m, const double *x, int64_t ldx, dou
   return hipGetLastError();
 }
 
+hipError_t modal_elem_pass_k(ModalOp *op, const double *x, double *contrib) {
+  if (op->n_elems == 0) return hipSuccess;
+  const dim3 grid(static_cast<unsigned>((op->n_elems + kThreads - 1) / kThreads));
+  hipLaunchKernelGGL((elem_apply_kernel<true, false>), grid, dim3(kThreads), 0, op->stream, op->n_elems, 1, op->xyz, op->tets,
+                     op->free_mask, op->lam, op->mu, op->rho, x, static_cast<int64_t>(0), contrib, nullptr);
+  return hipGetLastError();
+}
+
 hipError_t modal_node_sum(ModalOp *op, int32_t m, const double *contrib, int64_t stride, double *y, int64_t ldy) {
   const dim3 ngrid(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads));
   hipLaunchKernelGGL(node_sum_kernel, ngrid, dim3(kThreads), 0, op->stream, op->n_nodes, m, op->offsets, op->pairs, op->free_mask,

@@ -37,6 +37,10 @@ struct ModalOp {
 // v's entries of contrib + j * stride in ascending element order, 0 on Dirichlet dofs.  Enqueued on the op's stream.
 hipError_t modal_node_sum(ModalOp *op, int32_t m, const double *contrib, int64_t stride, double *y, int64_t ldy);
 
+// The K element pass of modal_apply alone (order 1), for one column: contrib[12 e + 3 corner + component], to be summed by
+// the caller (the stepper's fused node pass, saa_opstep.hip).  Enqueued on the op's stream.
+hipError_t modal_elem_pass_k(ModalOp *op, const double *x, double *contrib);
+
 // Gradients of the four shape functions (rows) and detJ; J columns are the edges x_a - x_0 (Shape_function_Deriv.py:60-67).
 __device__ __forceinline__ double element_gradients(const double *__restrict__ xyz, const int32_t *__restrict__ tets,
                                                     int64_t e, int32_t v[4], double g[4][3]) {

@@ -2,7 +2,8 @@
 
 ``Data_prepare.py`` -> :func:`data_prepare`, ``Shared_extraction.py`` -> :func:`shared_extraction`,
 ``Online_predictor.py`` -> :func:`online_predictor`, plus :func:`modal` (stable time step and lowest modes, the
-reference's ``Eigen_mode``), :func:`stress` (stress recovery from the saved trajectories) and :func:`estimate` (the
+reference's ``Eigen_mode``), :func:`dynamics` (the explicit run of one whole mesh on one GPU for either element order;
+the reference has none for ``p = 2``), :func:`stress` (stress recovery from the saved trajectories) and :func:`estimate` (the
 Zienkiewicz-Zhu estimate of the stress error of the mesh, the scale for the error of the modelled run; neither has a
 counterpart in the reference); same artefact names under ``Results/`` and
 ``Distributed_save/``, same constants by default.  Launch like the reference's
@@ -36,6 +37,7 @@ PATHS = dict(local_nodes="Results/Rankwised_Data/Rank={r}_local_nodes.csv",
              global_shared="Results/Shared_Data/Global_shared.csv",
              elements="Results/Rankwised_Element/Rank={r}_elements.csv",
              truth="Results/Dynamics/Local-rank-{r}.hdf5",
+             dynamics="Results/Dynamics/Displacement_order{p}.hdf5",
              modeled="Results/Dynamics/Modeled_Local-rank-{r}.hdf5",
              shared_traj="Results/sol_on_shared/rank={r}-shared_dof.hdf5",
              model="Distributed_save/Rank-{r}/nB-{nB}-nH-{nH}-Lr-{lr}-filter={ns}/model.pth",
@@ -246,6 +248,28 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
     if order != 1:
         raise ValueError("order must be 1 or 2")
     return modal_report(mesh.points, mesh.tets, clamp_nodes(mesh), k=k, device=device, **p)
+
+
+def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1, E=None, nu=None, rho=None, fz=None,
+             alpha=None, gamma=None):
+    """The explicit run of the whole mesh on one GPU through the operator handle (:func:`dynamics.run_dynamics`), for
+    linear (``order=1``) or quadratic tetrahedra (``order=2``: the mesh is elevated like ``steady_state --order 2``),
+    clamped on every node of ``x = 0``: lumped mass of the handle (HRZ for order 2), the reference load ``(0, -fz, -fz)``
+    with the ramp, ``alpha`` of ``Data_prepare.py:41`` and ``dt = gamma * 2/omega_max``.  Writes
+    ``Results/Dynamics/Displacement_order{p}.hdf5`` and returns ``(path, report)``."""
+    from .dynamics import run_dynamics
+    from .mesh import plane_nodes
+
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    p = {name: DEFAULTS[name] if v is None else v
+         for name, v in (("E", E), ("nu", nu), ("rho", rho), ("fz", fz), ("alpha", alpha), ("gamma", gamma))}
+    if order == 2:
+        mesh = _quadratic(mesh)
+    cells = mesh.tets10 if order == 2 else mesh.tets
+    store, report = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device, **p)
+    path = rio.save_displacement(os.path.join(out_dir, PATHS["dynamics"].format(p=order)), store)
+    return path, report
 
 
 def _device_recovery(device=0):
@@ -568,7 +592,7 @@ def _load_mesh(args):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="synchronization_avoiding_algorithms_amd.drivers")
     ap.add_argument("command", choices=["data_prepare", "steady_state", "shared_extraction", "model_training",
-                                        "online_predictor", "modal", "stress", "estimate"])
+                                        "online_predictor", "modal", "stress", "estimate", "dynamics"])
     ap.add_argument("--epochs", type=int, default=None, help="model_training: override the epoch count")
     ap.add_argument("--mesh", default="Mesh_info/beam_coarse.vtk")
     ap.add_argument("--synthetic", type=int, default=0, help="use the 25n x n x n synthetic beam instead")
@@ -592,10 +616,11 @@ def main(argv=None):
     ap.add_argument("--history", action="store_true", help="stress: every column's strain energy and von Mises maximum")
     ap.add_argument("--no-vtk", action="store_true", help="stress, estimate: no VTK files")
     ap.add_argument("--order", type=int, choices=[1, 2], default=1,
-                    help="steady_state, modal: 2 = quadratic tetrahedra (the mesh is elevated unless the file holds tetra10)")
+                    help="steady_state, modal, dynamics: 2 = quadratic tetrahedra (the mesh is elevated unless the file holds "
+                         "tetra10)")
     args = ap.parse_args(argv)
     rank, world, local = _dist_env()
-    if args.command in ("modal", "stress", "estimate"):  # one whole mesh on one GPU; prints one JSON object
+    if args.command in ("modal", "stress", "estimate", "dynamics"):  # one whole mesh on one GPU; prints one JSON object
         if rank != 0:
             return
         import json
@@ -606,6 +631,9 @@ def main(argv=None):
             else read_vtk(args.mesh)
         if args.command == "modal":
             print(json.dumps(modal(mesh, k=args.k, device=local, order=args.order)))
+        elif args.command == "dynamics":
+            path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order)
+            print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
             print(json.dumps(estimate(mesh, args.out, cols, modeled=args.modeled, vtk=not args.no_vtk, device=local)))

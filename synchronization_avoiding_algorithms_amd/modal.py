@@ -178,6 +178,16 @@ class ModalOperator:
                                                    C.c_void_p(dm.data_ptr()) if m else None))
         return dk, dm
 
+    def lumped_mass(self):
+        """The lumped mass as an ``(n_dof,)`` CUDA tensor, one value on a node's three dofs, Dirichlet dofs included
+        (``saa_operator_lumped_mass``).  Order 2: HRZ lumping with the 14-point rule (the reference's row sum gives every
+        vertex of a quadratic tetrahedron a negative mass); order 1: the row sum ``rho V/4``."""
+        import torch
+
+        out = torch.empty(self.n_dof, dtype=torch.float64, device=self.torch_device)
+        _lib.check(self._lib.saa_operator_lumped_mass(self._h, C.c_void_p(out.data_ptr())))
+        return out
+
     def element_bound(self, return_omega=False) -> dict:
         """``omega_max`` bound ``max_e omega_e``, its element, the count of elements with signed volume <= 0 and
         whether the bound is certified (that count is 0); ``omega_e`` (a CUDA tensor) on request."""
@@ -393,6 +403,21 @@ def stable_time_step(points, cells, dirichlet_nodes, E, nu, rho, gamma=0.9, devi
             "ratio": dt_reference / dt_crit, "omega_max": omega_max, "omega_bound": bound["omega_max"],
             "lanczos_residual": res, "lanczos_iterations": its,
             "seconds": {"setup": t1 - t0, "element_bound": t2 - t1, "lanczos": t3 - t2}}
+
+
+def stable_time_step_operator(op: ModalOperator, mass, gamma=0.9, lanczos_tol=1e-10) -> dict:
+    """``{"omega_max", "dt_crit", "dt"}`` of the central-difference update on an operator handle of either order with the
+    lumped mass ``mass`` (``(n_dof,)``, e.g. :meth:`ModalOperator.lumped_mass`): ``omega_max`` of ``M_L^-1 K`` on the free
+    dofs by :func:`lanczos_max` on the handle's ``K`` apply, ``dt_crit = 2/omega_max`` and ``dt = gamma * dt_crit``.  The
+    step of :class:`dynamics.OperatorStepper`; nothing else picks its ``dt`` from it."""
+    import torch
+
+    m = mass if torch.is_tensor(mass) else torch.as_tensor(np.asarray(mass, dtype=np.float64))
+    m = m.to(device=op.torch_device, dtype=torch.float64).reshape(-1)
+    s = torch.where(m > 0, op.free / torch.sqrt(torch.where(m > 0, m, 1.0)), 0.0)  # (a node without elements has no mass)
+    omega_max, _, _ = lanczos_max(lambda X: op.apply(X)[0], s, tol=lanczos_tol)
+    dt_crit = 2.0 / omega_max
+    return {"omega_max": omega_max, "dt_crit": dt_crit, "dt": gamma * dt_crit}
 
 
 def device_lowest_modes(op: ModalOperator, points, cells, lmd, mu, k, **kw):
