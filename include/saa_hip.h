@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -355,7 +355,9 @@ int saa_topology_destroy(saa_topology *t);
  *   doubles each on the device, either may be NULL - what a Jacobi preconditioner needs.  Order 1: the closed form of
  *   Local_K_coronary's diagonal and rho V / 10.
  * saa_operator_element_bound, saa_operator_stress, saa_operator_nodal_average and saa_operator_stress_error are formulas of
- *   the linear element: on an order-2 handle they return SAA_E_ARG, say so in saa_last_error and launch nothing.
+ *   the linear element: on an order-2 handle they return SAA_E_ARG, say so in saa_last_error and launch nothing.  The
+ *   stress of an order-2 handle comes from saa_operator_stress_p2, saa_operator_nodal_stress_p2 and
+ *   saa_operator_stress_error_p2 (below, after the linear ones), which in turn refuse an order-1 handle.
  */
 typedef struct saa_operator saa_operator;
 int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
@@ -410,6 +412,44 @@ int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_e
                               const double *sigma_node_dev, int64_t ld_node, const double *sigma_other_dev, int64_t ld_other,
                               double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
                               int32_t *eta2_argmax_dev);
+/*
+ * Stress recovery and error estimate of the quadratic element, on an order-2 handle (saa_operator_create_p2).  Voigt rows,
+ * D, fp64, repeatability and the stream as above; the Dirichlet mask is not applied.  The Gauss points q = 0..3 are those
+ * of the K rule, Gauss_Legendre(2): point q has barycentric weight a = 0.5854101966249685 on vertex v(q) = 1, 2, 3, 0 and
+ * b = 0.1381966011250105 on the others (q(v) = 3, 0, 1, 2 is the inverse).  All three take m in 1..16 column-major columns;
+ * any output may be NULL, and with every output NULL nothing is launched.  On an order-1 handle they return SAA_E_ARG, name
+ * themselves and "order-1" in saa_last_error and launch nothing.  No counterpart in the reference.
+ *
+ * saa_operator_stress_p2: eps_q = sum_a B_a(xi_q) u_a with the isoparametric gradients of the K apply, sigma_q = D eps_q,
+ *   its von Mises value, W_e = 1/2 sum_q w_q |detJ_q| sigma_q . eps_q (where every detJ_q > 0, sum_e W_e = x^T K x / 2 of a
+ *   handle without Dirichlet dofs).  x: 3*n_nodes per column, ldx >= 3*n_nodes.  sigma: 24*n_elems per column, 24e+6q+c,
+ *   ld_sigma >= 24*n_elems; von_mises: 4*n_elems per column, 4e+q, ld_vm >= 4*n_elems; energy: n_elems per column,
+ *   ld_elem >= n_elems; energy_total, von_mises_max (m doubles), von_mises_argmax (m int32: the point index 4e+q, the
+ *   lowest on ties).
+ * saa_operator_nodal_stress_p2: the recovered nodal stress.  The field that is linear in the barycentric coordinates and
+ *   takes the four Gauss values has the vertex values c_v = sqrt(5) (sigma_q(v) - b S), S = sum_q sigma_q; an edge node
+ *   takes the mean of its two vertices.  On a straight element this field is the finite-element stress itself; on a curved
+ *   one it is the definition of the element stress sigma_h used here and below (a DELIBERATE simplification: the
+ *   finite-element stress of a curved element is rational in xi).  sigma_node[6n+c] = sum_{e at n} |V_e| c_{e,corner(n)} /
+ *   sum_{e at n} |V_e| with |V_e| = sum_q w_q |detJ_q|, ascending element order, 0 at a node with no element; 6*n_nodes
+ *   per column, ld_node >= 6*n_nodes.
+ * saa_operator_stress_error_p2: eta_e^2 = integral_e d^T C d dV, C = D^-1 (needs mu > 0 and 3 lambda + 2 mu > 0), against
+ *   exactly one of sigma_node (6*n_nodes per column: d = sum_a N_a sigma_node_a - sigma_h with the ten quadratic shape
+ *   functions, integrated with the 14-point rule Gauss_Legendre(4) and |detJ| at its points, exact on straight elements;
+ *   with saa_operator_nodal_stress_p2 of sigma this is the Zienkiewicz-Zhu estimate) and sigma_other (a second Gauss-point
+ *   field, 24*n_elems per column, ld_other >= 24*n_elems: d_q = sigma_other_q - sigma_q with the 4-point rule, exact on
+ *   straight elements).  The other one is NULL.  eta2: n_elems per column, ld_eta >= n_elems; eta2_total, eta2_max (m
+ *   doubles), eta2_argmax (m int32: the lowest element index on ties; -1 and 0.0 on a mesh without elements).
+ */
+int saa_operator_stress_p2(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *sigma_dev, int64_t ld_sigma,
+                           double *von_mises_dev, int64_t ld_vm, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
+                           double *von_mises_max_dev, int32_t *von_mises_argmax_dev);
+int saa_operator_nodal_stress_p2(saa_operator *op, int32_t m, const double *sigma_dev, int64_t ld_sigma, double *sigma_node_dev,
+                                 int64_t ld_node);
+int saa_operator_stress_error_p2(saa_operator *op, int32_t m, const double *sigma_dev, int64_t ld_sigma,
+                                 const double *sigma_node_dev, int64_t ld_node, const double *sigma_other_dev, int64_t ld_other,
+                                 double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
+                                 int32_t *eta2_argmax_dev);
 int saa_operator_destroy(saa_operator *op);
 
 /*

@@ -25,6 +25,7 @@
 #include "saa_plan.h"
 #include "saa_predictor.h"
 #include "saa_stress.h"
+#include "saa_stress_p2.h"
 #include "saa_setup.h"
 #include "saa_topology.h"
 
@@ -2111,6 +2112,93 @@ int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_e
   const hipError_t e = saa::stress_error(op->impl, m, sigma_elem_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev,
                                          ld_other, eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stress_error: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+// ---- stress recovery of the quadratic element (saa_stress_p2.hip) ---------------------------------------------------
+namespace {
+
+// What the three order-2 entry points check first, before the handle is read: the handle and the column count.
+int p2_stress_front(const saa_operator *op, int32_t m, const char *name) {
+  if (!op) return fail(SAA_E_ARG, std::string(name) + ": null handle");
+  if (m < 1 || m > saa::kModalMaxColumns)
+    return fail(SAA_E_ARG, std::string(name) + ": m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+  if (!op->impl) return fail(SAA_E_ARG, std::string(name) + ": null handle");
+  if (saa::modal_order(op->impl) != 2)
+    return fail(SAA_E_ARG, std::string(name) + ": a quadratic-element formula, not available on an order-1 handle "
+                                               "(saa_operator_create)");
+  return SAA_OK;
+}
+
+int p2_stress_ld(const char *name, const char *what, int64_t ld, const char *bound, int64_t need) {
+  if (ld >= need) return SAA_OK;
+  return fail(SAA_E_ARG, std::string(name) + ": " + what + " = " + std::to_string(ld) + " below " + bound + " = " +
+                             std::to_string(need));
+}
+
+}  // namespace
+
+int saa_operator_stress_p2(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *sigma_dev, int64_t ld_sigma,
+                           double *von_mises_dev, int64_t ld_vm, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
+                           double *von_mises_max_dev, int32_t *von_mises_argmax_dev) {
+  static const char *const name = "saa_operator_stress_p2";
+  if (const int rc = p2_stress_front(op, m, name)) return rc;
+  if (!x_dev) return fail(SAA_E_ARG, std::string(name) + ": null displacement x_dev");
+  const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
+  const int64_t n_elems = saa::modal_n_elems(op->impl);
+  if (const int rc = p2_stress_ld(name, "ldx", ldx, "3 * n_nodes", n_dof)) return rc;
+  if (sigma_dev)
+    if (const int rc = p2_stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
+  if (von_mises_dev)
+    if (const int rc = p2_stress_ld(name, "ld_vm", ld_vm, "4 * n_elems", 4 * n_elems)) return rc;
+  if (energy_dev)
+    if (const int rc = p2_stress_ld(name, "ld_elem", ld_elem, "n_elems", n_elems)) return rc;
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::p2_stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, ld_vm, energy_dev,
+                                              ld_elem, energy_total_dev, von_mises_max_dev, von_mises_argmax_dev);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_nodal_stress_p2(saa_operator *op, int32_t m, const double *sigma_dev, int64_t ld_sigma, double *sigma_node_dev,
+                                 int64_t ld_node) {
+  static const char *const name = "saa_operator_nodal_stress_p2";
+  if (const int rc = p2_stress_front(op, m, name)) return rc;
+  if (!sigma_dev) return fail(SAA_E_ARG, std::string(name) + ": null Gauss-point stress sigma_dev");
+  const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
+  if (const int rc = p2_stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
+  if (!sigma_node_dev) return SAA_OK;  // (the only output: nothing is launched)
+  if (const int rc = p2_stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::p2_stress_nodal(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stress_error_p2(saa_operator *op, int32_t m, const double *sigma_dev, int64_t ld_sigma,
+                                 const double *sigma_node_dev, int64_t ld_node, const double *sigma_other_dev, int64_t ld_other,
+                                 double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
+                                 int32_t *eta2_argmax_dev) {
+  static const char *const name = "saa_operator_stress_error_p2";
+  if (const int rc = p2_stress_front(op, m, name)) return rc;
+  if (!sigma_dev) return fail(SAA_E_ARG, std::string(name) + ": null Gauss-point stress sigma_dev");
+  if (!sigma_node_dev == !sigma_other_dev)
+    return fail(SAA_E_ARG, std::string(name) + ": " + (sigma_node_dev ? "both" : "neither") +
+                               " of sigma_node_dev and sigma_other_dev given, exactly one is needed");
+  const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
+  if (const int rc = p2_stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
+  if (sigma_node_dev)
+    if (const int rc = p2_stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
+  if (sigma_other_dev)
+    if (const int rc = p2_stress_ld(name, "ld_other", ld_other, "24 * n_elems", 24 * n_elems)) return rc;
+  if (eta2_dev)
+    if (const int rc = p2_stress_ld(name, "ld_eta", ld_eta, "n_elems", n_elems)) return rc;
+  if (!saa::stress_has_compliance(op->impl))
+    return fail(SAA_E_ARG, std::string(name) + ": the compliance D^-1 needs mu > 0 and 3 lambda + 2 mu > 0");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::p2_stress_error(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
+                                            eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
   return SAA_OK;
 }
 

@@ -330,6 +330,27 @@ int32_t n_parts_of(const ModalOp *op) { return (op->n_elems + kThreads - 1) / kT
 
 // |V_e|, the node weight sums and the partial buffers, once per handle (freed by modal_destroy)
 hipError_t stress_prepare(ModalOp *op) {
+  bool fresh = false;
+  hipError_t e = stress_buffers(op, &fresh);
+  if (e != hipSuccess || !fresh) return e;
+  if (op->n_elems > 0)
+    hipLaunchKernelGGL(stress_vol_kernel, dim3(static_cast<unsigned>(n_parts_of(op))), dim3(kThreads), 0, op->stream,
+                       op->n_elems, op->xyz, op->tets, op->abs_vol);
+  e = hipGetLastError();
+  if (e == hipSuccess)
+    hipLaunchKernelGGL(stress_node_weight_kernel, dim3(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs, op->abs_vol, op->node_wsum);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) stress_buffers_free(op);
+  return e;
+}
+
+}  // namespace
+
+int32_t modal_n_elems(const ModalOp *op) { return op->n_elems; }
+
+hipError_t stress_buffers(ModalOp *op, bool *fresh) {
+  *fresh = false;
   if (op->st_part_idx) return hipSuccess;
   const size_t parts = static_cast<size_t>(n_parts_of(op)) * kModalMaxColumns;
   hipError_t e = dev_alloc(&op->abs_vol, static_cast<size_t>(op->n_elems));
@@ -337,28 +358,25 @@ hipError_t stress_prepare(ModalOp *op) {
   if (e == hipSuccess) e = dev_alloc(&op->st_part_w, parts);
   if (e == hipSuccess) e = dev_alloc(&op->st_part_vm, parts);
   if (e == hipSuccess) e = dev_alloc(&op->st_part_idx, parts);
-  if (e == hipSuccess && op->n_elems > 0)
-    hipLaunchKernelGGL(stress_vol_kernel, dim3(static_cast<unsigned>(n_parts_of(op))), dim3(kThreads), 0, op->stream,
-                       op->n_elems, op->xyz, op->tets, op->abs_vol);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess)
-    hipLaunchKernelGGL(stress_node_weight_kernel, dim3(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs, op->abs_vol, op->node_wsum);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) {
-    for (void **b : {reinterpret_cast<void **>(&op->abs_vol), reinterpret_cast<void **>(&op->node_wsum),
-                     reinterpret_cast<void **>(&op->st_part_w), reinterpret_cast<void **>(&op->st_part_vm),
-                     reinterpret_cast<void **>(&op->st_part_idx)}) {
-      if (*b) (void)hipFree(*b);
-      *b = nullptr;
-    }
-  }
+  if (e != hipSuccess) stress_buffers_free(op);
+  *fresh = e == hipSuccess;
   return e;
 }
 
-}  // namespace
+void stress_buffers_free(ModalOp *op) {
+  for (void **b : {reinterpret_cast<void **>(&op->abs_vol), reinterpret_cast<void **>(&op->node_wsum),
+                   reinterpret_cast<void **>(&op->st_part_w), reinterpret_cast<void **>(&op->st_part_vm),
+                   reinterpret_cast<void **>(&op->st_part_idx)}) {
+    if (*b) (void)hipFree(*b);
+    *b = nullptr;
+  }
+}
 
-int32_t modal_n_elems(const ModalOp *op) { return op->n_elems; }
+hipError_t stress_reduce_partials(ModalOp *op, int32_t m, double *total, double *best, int32_t *argbest) {
+  hipLaunchKernelGGL(stress_final_kernel, dim3(static_cast<unsigned>(m)), dim3(kThreads), 0, op->stream, n_parts_of(op),
+                     op->st_part_w, op->st_part_vm, op->st_part_idx, total, best, argbest);
+  return hipGetLastError();
+}
 
 hipError_t stress_element(ModalOp *op, int32_t m, const double *x, int64_t ldx, double *sigma, int64_t ld_sigma,
                           double *von_mises, double *energy, int64_t ld_elem, double *energy_total, double *von_mises_max,

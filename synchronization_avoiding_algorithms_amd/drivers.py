@@ -44,7 +44,10 @@ PATHS = dict(local_nodes="Results/Rankwised_Data/Rank={r}_local_nodes.csv",
              stress_vtk="Results/Stress/Stress-col-{j}.vtk",
              modeled_stress_vtk="Results/Stress/Modeled_Stress-col-{j}.vtk",
              stress_history="Results/Stress/history.npz",
-             estimate_vtk="Results/Stress/Estimate-col-{j}.vtk")
+             estimate_vtk="Results/Stress/Estimate-col-{j}.vtk",
+             stress_vtk_p2="Results/Stress/Stress-order2-col-{j}.vtk",
+             stress_history_p2="Results/Stress/history-order2.npz",
+             estimate_vtk_p2="Results/Stress/Estimate-order2-col-{j}.vtk")
 
 
 def _dist_env():
@@ -579,6 +582,168 @@ def estimate(mesh, out_dir=".", columns=(-1,), modeled=False, vtk=True, device=0
     return report
 
 
+def _device_recovery_p2(device=0):
+    """The GPU side of :func:`stress_p2` and :func:`estimate_p2`: a factory ``make(points, cells10, lmd, mu)`` of objects
+    with NumPy-in / NumPy-out ``element``, ``nodal``, ``error``, ``history`` and ``close()`` on
+    :class:`stress.QuadraticStressRecovery`.  Tests pass a NumPy stand-in with the same methods."""
+    import torch
+
+    from .stress import QuadraticStressRecovery
+
+    class _Host:
+        def __init__(self, points, cells10, lmd, mu):
+            self.rec = QuadraticStressRecovery(points, cells10, lmd, mu, device=device)
+
+        def _dev(self, a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.rec.torch_device)
+
+        def element(self, X):
+            return {k: v.cpu().numpy() for k, v in self.rec.element(self._dev(X)).items()}
+
+        def nodal(self, sigma):
+            return self.rec.nodal(self._dev(sigma)).cpu().numpy()
+
+        def error(self, sigma, nodal=None, other=None):
+            res = self.rec.error(self._dev(sigma), nodal=None if nodal is None else self._dev(nodal),
+                                 other=None if other is None else self._dev(other))
+            return {k: v.cpu().numpy() for k, v in res.items()}
+
+        def history(self, traj):
+            return {k: v.cpu().numpy() for k, v in self.rec.history(traj).items()}
+
+        def close(self):
+            self.rec.close()
+
+    return _Host
+
+
+def _load_p2_run(mesh, out_dir, columns):
+    """What :func:`stress_p2` and :func:`estimate_p2` read: the mesh with 10-node cells (elevated like ``dynamics --order
+    2``), the trajectory ``Results/Dynamics/Displacement_order2.hdf5`` under ``out_dir`` with 3 rows per node, and
+    ``columns`` resolved against its saved columns (negative = from the end)."""
+    mesh = _quadratic(mesh)
+    points = np.asarray(mesh.points, dtype=np.float64)
+    cells = np.asarray(mesh.tets10, dtype=np.int64)
+    path = os.path.join(out_dir, PATHS["dynamics"].format(p=2))
+    try:
+        traj = np.asarray(rio.load_displacement(path), dtype=np.float64)
+    except FileNotFoundError as exc:
+        raise FileNotFoundError(f"{exc}: run dynamics --order 2 first") from None
+    if traj.ndim != 2 or traj.shape[0] != 3 * len(points):
+        raise ValueError(f"{path}: {traj.shape[0] if traj.ndim else 0} rows, expected 3 * {len(points)} = {3 * len(points)} "
+                         "(3 per node of the elevated mesh)")
+    n_cols = traj.shape[1]
+    cols = []
+    for j in columns:
+        jj = int(j) + n_cols if int(j) < 0 else int(j)
+        if not 0 <= jj < n_cols:
+            raise ValueError(f"column {j} out of range for {n_cols} saved columns")
+        cols.append(jj)
+    return points, cells, traj, n_cols, cols
+
+
+def _p2_point_data(traj_cols, nodal):
+    """Point data of one column: the displacement, the recovered stress ``sigma*`` and its von Mises value."""
+    from .stress import VOIGT, von_mises
+
+    pd = {f"displacement-{c}": traj_cols.reshape(-1, 3)[:, a] for a, c in enumerate("xyz")}
+    pd.update({f"sigma-{c}": nodal[:, a] for a, c in enumerate(VOIGT)})
+    pd["von-mises"] = von_mises(nodal)
+    return pd
+
+
+def stress_p2(mesh, out_dir=".", columns=(-1,), history=False, vtk=True, device=0, E=None, nu=None, recovery=None):
+    """:func:`stress` for quadratic tetrahedra: the whole mesh on one GPU, the displacement of ``dynamics --order 2``
+    (``Results/Dynamics/Displacement_order2.hdf5`` under ``out_dir``).  For every saved column in ``columns`` reports the
+    strain energy, the largest Gauss-point von Mises stress, its element, Gauss point and position, and writes
+    ``Results/Stress/Stress-order2-col-{j}.vtk`` (type-24 cells; point data: displacement, the recovered stress ``sigma*``
+    and its von Mises; cell data: the largest Gauss-point von Mises and ``W_e``) unless ``vtk`` is False; ``history`` writes
+    every column's strain energy and von Mises maximum to ``Results/Stress/history-order2.npz``.  Returns the report that
+    the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery_p2` (default: the GPU)."""
+    from . import fem_setup as fs
+    from .Tools.Qudrature import Gauss_Legendre
+    from .Tools.Shape_function_Deriv import Shape_Function
+
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    make = _device_recovery_p2(device) if recovery is None else recovery
+    points, cells, traj, n_cols, cols = _load_p2_run(mesh, out_dir, columns)
+    ne, nn, m = len(cells), len(points), len(cols)
+    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+    shape4 = np.array([Shape_Function(2, x) for x in Gauss_Legendre(2)[0]])      # (4, 10): N_a at the Gauss points
+    centroid = points[cells[:, :4]].mean(axis=1)
+
+    report = {"order": 2, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "columns": [], "files": [],
+              "history": None}
+    rec = make(points, cells, lmd, mu)
+    try:
+        if m:
+            X = np.ascontiguousarray(traj[:, cols].T)
+            res = rec.element(X)
+            nodal = rec.nodal(res["sigma"]) if vtk else None
+            for i, j in enumerate(cols):
+                e, q = divmod(int(res["von_mises_argmax"][i]), 4)
+                report["columns"].append({"column": j, "strain_energy": float(res["energy_total"][i]),
+                                          "von_mises_max": float(res["von_mises_max"][i]), "element": e, "gauss_point": q,
+                                          "position": [float(c) for c in shape4[q] @ points[cells[e]]],
+                                          "centroid": [float(c) for c in centroid[e]]})
+                if vtk:
+                    cd = {"von-mises-max": res["von_mises"][i].max(axis=1), "energy": res["energy"][i]}
+                    report["files"].append(rio.write_vtk_fields(p["stress_vtk_p2"].format(j=j), points, cells,
+                                                                _p2_point_data(X[i], nodal[i]), cd,
+                                                                title=f"stress, quadratic tetrahedra, saved column {j}"))
+        if history:
+            h = rec.history(traj)
+            arg = np.asarray(h["von_mises_argmax"], dtype=np.int64)
+            os.makedirs(os.path.dirname(p["stress_history_p2"]), exist_ok=True)
+            np.savez(p["stress_history_p2"], columns=np.arange(n_cols), strain_energy=h["energy_total"],
+                     von_mises_max=h["von_mises_max"], von_mises_element=arg // 4, von_mises_gauss_point=arg % 4)
+            report["history"] = p["stress_history_p2"]
+    finally:
+        rec.close()
+    return report
+
+
+def estimate_p2(mesh, out_dir=".", columns=(-1,), vtk=True, device=0, E=None, nu=None, recovery=None):
+    """:func:`estimate` for quadratic tetrahedra, on the run that :func:`stress_p2` reads: the Zienkiewicz-Zhu estimate
+    ``eta_e^2 = integral_e (sigma* - sigma_h)^T D^-1 (sigma* - sigma_h) dV`` with the element-linear stress ``sigma_h`` and
+    the quadratic field ``sigma*`` of its recovered nodal values.  For every saved column in ``columns`` reports ``eta``,
+    ``energy_norm``, ``relative`` and the element of the largest ``eta_e^2`` with its centroid, and writes
+    ``Results/Stress/Estimate-order2-col-{j}.vtk`` (type-24 cells; point data as :func:`stress_p2`; cell data: the largest
+    Gauss-point von Mises, ``W_e`` and ``eta2``) unless ``vtk`` is False.  ``recovery``: see :func:`_device_recovery_p2`."""
+    from . import fem_setup as fs
+
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    make = _device_recovery_p2(device) if recovery is None else recovery
+    points, cells, traj, n_cols, cols = _load_p2_run(mesh, out_dir, columns)
+    ne, nn, m = len(cells), len(points), len(cols)
+    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+    centroid = points[cells[:, :4]].mean(axis=1)
+
+    report = {"order": 2, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "columns": [], "files": []}
+    if not m:
+        return report
+    rec = make(points, cells, lmd, mu)
+    try:
+        X = np.ascontiguousarray(traj[:, cols].T)
+        res = rec.element(X)
+        nodal = rec.nodal(res["sigma"])
+        zz = rec.error(res["sigma"], nodal=nodal)
+    finally:
+        rec.close()
+    for i, j in enumerate(cols):
+        eta2, w2 = float(zz["eta2_total"][i]), 2.0 * float(res["energy_total"][i])
+        e = int(zz["eta2_argmax"][i])
+        report["columns"].append({"column": j, "eta": float(np.sqrt(eta2)), "energy_norm": float(np.sqrt(w2)),
+                                  "relative": float(np.sqrt(eta2 / (w2 + eta2))) if w2 + eta2 > 0 else 0.0, "element": e,
+                                  "eta2_max": float(zz["eta2_max"][i]), "centroid": [float(c) for c in centroid[e]]})
+        if vtk:
+            cd = {"von-mises-max": res["von_mises"][i].max(axis=1), "energy": res["energy"][i], "eta2": zz["eta2"][i]}
+            report["files"].append(rio.write_vtk_fields(p["estimate_vtk_p2"].format(j=j), points, cells,
+                                                        _p2_point_data(X[i], nodal[i]), cd,
+                                                        title=f"stress error estimate, quadratic tetrahedra, saved column {j}"))
+    return report
+
+
 def _has_gpu():
     import torch
 
@@ -616,9 +781,11 @@ def main(argv=None):
     ap.add_argument("--history", action="store_true", help="stress: every column's strain energy and von Mises maximum")
     ap.add_argument("--no-vtk", action="store_true", help="stress, estimate: no VTK files")
     ap.add_argument("--order", type=int, choices=[1, 2], default=1,
-                    help="steady_state, modal, dynamics: 2 = quadratic tetrahedra (the mesh is elevated unless the file holds "
-                         "tetra10)")
+                    help="steady_state, modal, dynamics, stress, estimate: 2 = quadratic tetrahedra (the mesh is elevated "
+                         "unless the file holds tetra10); stress and estimate then read the run of dynamics --order 2")
     args = ap.parse_args(argv)
+    if args.command in ("stress", "estimate") and args.order == 2 and args.modeled:
+        ap.error(f"{args.command} --order 2 --modeled: there is no modelled p = 2 run (the predictor drives linear elements)")
     rank, world, local = _dist_env()
     if args.command in ("modal", "stress", "estimate", "dynamics"):  # one whole mesh on one GPU; prints one JSON object
         if rank != 0:
@@ -636,9 +803,15 @@ def main(argv=None):
             print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
+            if args.order == 2:
+                print(json.dumps(estimate_p2(mesh, args.out, cols, vtk=not args.no_vtk, device=local)))
+                return
             print(json.dumps(estimate(mesh, args.out, cols, modeled=args.modeled, vtk=not args.no_vtk, device=local)))
         else:
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
+            if args.order == 2:
+                print(json.dumps(stress_p2(mesh, args.out, cols, history=args.history, vtk=not args.no_vtk, device=local)))
+                return
             print(json.dumps(stress(mesh, args.out, cols, modeled=args.modeled, history=args.history, vtk=not args.no_vtk,
                                     device=local)))
         return

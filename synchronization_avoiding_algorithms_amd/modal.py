@@ -79,8 +79,9 @@ class ModalOperator:
 
     ``cells`` of shape ``(ne, 10)`` (``mesh.to_quadratic``) make an order-2 handle (``saa_operator_create_p2``): quadratic
     tetrahedra, ``K`` with the reference's 4-point rule, ``M`` with the 14-point rule.  ``apply``, ``load`` and
-    ``diagonal`` work on either order; ``element_bound`` and the stress recovery are linear-element formulas and raise
-    on an order-2 handle."""
+    ``diagonal`` work on either order; ``element_bound`` and the linear stress recovery (:class:`stress.StressRecovery`)
+    are linear-element formulas and raise on an order-2 handle, whose stress comes from
+    :class:`stress.QuadraticStressRecovery`."""
 
     MAX_COLUMNS = 16
 

@@ -69,7 +69,8 @@ def load_int_list(path: str) -> np.ndarray:
 
 def write_vtk_fields(path, points, cells, point_data=None, cell_data=None, title="fields"):
     """Legacy ASCII VTK of a tetrahedral mesh with named scalar ``POINT_DATA`` and ``CELL_DATA`` arrays
-    (``{name: (n,) array}``, written in order), in the ``%.17g`` format of ``steady.write_vtk_point_data``."""
+    (``{name: (n,) array}``, written in order), in the ``%.17g`` format of ``steady.write_vtk_point_data``.  Cells of ten
+    nodes are written as quadratic tetrahedra (type 24), cells of four as type 10."""
     points, cells = np.asarray(points, dtype=np.float64), np.asarray(cells)
     for section, data, n in (("point", point_data, len(points)), ("cell", cell_data, len(cells))):
         for name, a in (data or {}).items():
@@ -81,10 +82,11 @@ def write_vtk_fields(path, points, cells, point_data=None, cell_data=None, title
         fh.write(f"# vtk DataFile Version 4.2\n{title}\nASCII\nDATASET UNSTRUCTURED_GRID\n")
         fh.write(f"POINTS {len(points)} double\n")
         np.savetxt(fh, points, fmt="%.17g")
-        fh.write(f"CELLS {len(cells)} {5 * len(cells)}\n")
-        np.savetxt(fh, np.column_stack([np.full(len(cells), 4), cells]), fmt="%d")
+        per = cells.shape[1] if cells.ndim == 2 and cells.shape[1] == 10 else 4
+        fh.write(f"CELLS {len(cells)} {(per + 1) * len(cells)}\n")
+        np.savetxt(fh, np.column_stack([np.full(len(cells), per), cells]), fmt="%d")
         fh.write(f"CELL_TYPES {len(cells)}\n")
-        np.savetxt(fh, np.full(len(cells), 10), fmt="%d")
+        np.savetxt(fh, np.full(len(cells), 24 if per == 10 else 10), fmt="%d")
         for section, data, n in (("POINT_DATA", point_data, len(points)), ("CELL_DATA", cell_data, len(cells))):
             if not data:
                 continue

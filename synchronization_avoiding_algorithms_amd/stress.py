@@ -18,6 +18,10 @@ The kernels (``saa_operator_stress``, ``saa_operator_nodal_average``, ``saa_oper
 :class:`modal.ModalOperator`, i.e. with the geometry of the K apply.  Its Dirichlet mask is not applied: the displacement
 is read as given (recorded trajectories are already 0 on clamped dofs).  Blocks of vectors are ``(m, n)`` tensors, one
 column per row, as in :mod:`modal`.  The reference has no counterpart: it stores displacement only.
+
+:class:`QuadraticStressRecovery` is the same for quadratic tetrahedra on an order-2 handle: stress at the four Gauss points
+of every element, the recovered nodal stress and the error estimate (``saa_operator_stress_p2``,
+``saa_operator_nodal_stress_p2``, ``saa_operator_stress_error_p2``).
 """
 from __future__ import annotations
 
@@ -180,6 +184,186 @@ class StressRecovery:
     def estimate(self, X) -> dict:
         """Zienkiewicz-Zhu estimate of the stress error of displacement columns ``(m, n_dof)`` (or one ``(n_dof,)``
         vector): element stress -> nodal average -> :meth:`error`.  Returns the dict of :meth:`error` plus
+        ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish)."""
+        import torch
+
+        el = self.element(X, von_mises=False, energy=False)
+        out = self.error(el["sigma"], nodal=self.nodal(el["sigma"]))
+        out["energy_total"] = el["energy_total"]
+        den = 2.0 * el["energy_total"] + out["eta2_total"]
+        out["relative"] = torch.where(den > 0, out["eta2_total"] / den, torch.zeros_like(den)).sqrt()
+        return out
+
+    def history(self, traj) -> dict:
+        """``energy_total``, ``von_mises_max`` and ``von_mises_argmax`` of every column of a row-major
+        ``(n_dof, n_cols)`` trajectory (the recorder's and the HDF5 layout), host array or device tensor.  Only the
+        reductions are computed; no per-element field is written."""
+        import torch
+
+        if traj.shape[0] != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} rows, got {traj.shape[0]}")
+        n = traj.shape[1]
+        dev = self.torch_device
+        out = {"energy_total": torch.empty(n, dtype=torch.float64, device=dev),
+               "von_mises_max": torch.empty(n, dtype=torch.float64, device=dev),
+               "von_mises_argmax": torch.empty(n, dtype=torch.int32, device=dev)}
+        for j in range(0, n, self.MAX_COLUMNS):
+            c = min(self.MAX_COLUMNS, n - j)
+            if isinstance(traj, torch.Tensor):
+                blk = traj[:, j:j + c].to(device=dev, dtype=torch.float64).T.contiguous()
+            else:
+                blk = torch.from_numpy(np.ascontiguousarray(np.asarray(traj[:, j:j + c], dtype=np.float64).T)).to(dev)
+            self.stress_raw(c, blk, self.n_dof, energy_total=out["energy_total"][j:], von_mises_max=out["von_mises_max"][j:],
+                            von_mises_argmax=out["von_mises_argmax"][j:])
+        return out
+
+
+class QuadraticStressRecovery:
+    """Stress recovery and error estimate of quadratic (10-node) tetrahedra, one whole mesh on one GPU, on an order-2
+    handle (``saa_operator_stress_p2``, ``saa_operator_nodal_stress_p2``, ``saa_operator_stress_error_p2``; the
+    definitions are in ``include/saa_hip.h``).  Wraps ``operator`` (an order-2 :class:`modal.ModalOperator`, whose mesh and
+    material are then used) or builds one with no Dirichlet dofs.  float64 CUDA tensors in and out.
+
+    The element stress lives at the four Gauss points of the K rule: ``sigma (m, n_elems, 4, 6)``.  ``sigma_h`` is the field
+    linear in the barycentric coordinates through these four values, the recovered stress ``sigma*`` the quadratic field of
+    the ``|V_e|``-weighted nodal means of ``sigma_h``, and ``eta_e^2`` the energy norm of ``sigma* - sigma_h`` over the
+    element (14-point rule), or of the difference to a second Gauss-point field (4-point rule)."""
+
+    MAX_COLUMNS = 16
+
+    def __init__(self, points, cells10, lmd, mu, device=0, operator=None):
+        from .modal import ModalOperator
+
+        self._own = operator is None
+        if operator is None:
+            cells10 = np.asarray(cells10)
+            if cells10.ndim != 2 or cells10.shape[1] != 10:
+                raise ValueError(f"expected (n_elems, 10) cells, got {cells10.shape}")
+            operator = ModalOperator(points, cells10, (), lmd, mu, 1.0, device=device)
+        elif operator.order != 2:
+            raise ValueError("QuadraticStressRecovery needs an order-2 operator; StressRecovery serves order 1")
+        self.op = operator
+        self._lib = self.op._lib
+        self.n_nodes, self.n_elems, self.n_dof = self.op.n_nodes, self.op.n_elems, self.op.n_dof
+        self.torch_device = self.op.torch_device
+
+    def close(self):
+        if self._own and getattr(self, "op", None) is not None:
+            self.op.close()
+        self.op = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- raw calls (any m and leading dimension: the library checks them) --------------------------------------------
+    def stress_raw(self, m, x, ldx, sigma=None, ld_sigma=0, von_mises=None, ld_vm=0, energy=None, ld_elem=0, energy_total=None,
+                   von_mises_max=None, von_mises_argmax=None):
+        _lib.check(self._lib.saa_operator_stress_p2(self.op._h, int(m), _ptr(x), int(ldx), _ptr(sigma), int(ld_sigma),
+                                                    _ptr(von_mises), int(ld_vm), _ptr(energy), int(ld_elem),
+                                                    _ptr(energy_total), _ptr(von_mises_max), _ptr(von_mises_argmax)))
+
+    def nodal_raw(self, m, sigma, ld_sigma, sigma_node, ld_node):
+        _lib.check(self._lib.saa_operator_nodal_stress_p2(self.op._h, int(m), _ptr(sigma), int(ld_sigma), _ptr(sigma_node),
+                                                          int(ld_node)))
+
+    def error_raw(self, m, sigma, ld_sigma, sigma_node=None, ld_node=0, sigma_other=None, ld_other=0, eta2=None, ld_eta=0,
+                  eta2_total=None, eta2_max=None, eta2_argmax=None):
+        _lib.check(self._lib.saa_operator_stress_error_p2(self.op._h, int(m), _ptr(sigma), int(ld_sigma), _ptr(sigma_node),
+                                                          int(ld_node), _ptr(sigma_other), int(ld_other), _ptr(eta2),
+                                                          int(ld_eta), _ptr(eta2_total), _ptr(eta2_max), _ptr(eta2_argmax)))
+
+    # ---- tensors -------------------------------------------------------------------------------------------------
+    _check = StressRecovery._check
+
+    def _gauss(self, S, name):
+        """``(m, n_elems, 4, 6)`` contiguous from that or ``(n_elems, 4, 6)``; the second value says which."""
+        self._check(S, name)
+        vec = S.dim() == 3
+        S = (S.reshape(1, *S.shape) if vec else S).contiguous()
+        if S.dim() != 4 or tuple(S.shape[1:]) != (self.n_elems, 4, 6):
+            raise ValueError(f"expected {name} of shape (m, {self.n_elems}, 4, 6), got {tuple(S.shape)}")
+        return S, vec
+
+    def element(self, X, sigma=True, von_mises=True, energy=True) -> dict:
+        """Gauss-point fields of a ``(n_dof,)`` vector or an ``(m, n_dof)`` block, in launches of at most 16 columns:
+        ``sigma (m, n_elems, 4, 6)``, ``von_mises (m, n_elems, 4)``, ``energy (m, n_elems)`` (those asked for) and
+        ``energy_total``, ``von_mises_max``, ``von_mises_argmax (m,)`` (a point index ``4 e + q``).  A vector input drops
+        the leading ``m``."""
+        import torch
+
+        self._check(X, "X")
+        vec = X.dim() == 1
+        X = (X.reshape(1, -1) if vec else X).contiguous()
+        if X.shape[1] != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} dofs per column, got {X.shape[1]}")
+        m, ne, dev = X.shape[0], self.n_elems, self.torch_device
+        out = {}
+        if sigma:
+            out["sigma"] = torch.empty((m, ne, 4, 6), dtype=torch.float64, device=dev)
+        if von_mises:
+            out["von_mises"] = torch.empty((m, ne, 4), dtype=torch.float64, device=dev)
+        if energy:
+            out["energy"] = torch.empty((m, ne), dtype=torch.float64, device=dev)
+        out["energy_total"] = torch.empty(m, dtype=torch.float64, device=dev)
+        out["von_mises_max"] = torch.empty(m, dtype=torch.float64, device=dev)
+        out["von_mises_argmax"] = torch.empty(m, dtype=torch.int32, device=dev)
+        for j in range(0, m, self.MAX_COLUMNS):
+            c = min(self.MAX_COLUMNS, m - j)
+            g = {k: v[j] for k, v in out.items()}
+            self.stress_raw(c, X[j], self.n_dof, g.get("sigma"), 24 * ne, g.get("von_mises"), 4 * ne, g.get("energy"), ne,
+                            g["energy_total"], g["von_mises_max"], g["von_mises_argmax"])
+        return {k: v[0] for k, v in out.items()} if vec else out
+
+    def nodal(self, sigma):
+        """Recovered nodal stress of Gauss-point stresses ``(m, n_elems, 4, 6)`` (or ``(n_elems, 4, 6)``) ->
+        ``(m, n_nodes, 6)``."""
+        import torch
+
+        S, vec = self._gauss(sigma, "sigma")
+        m = S.shape[0]
+        out = torch.empty((m, self.n_nodes, 6), dtype=torch.float64, device=self.torch_device)
+        for j in range(0, m, self.MAX_COLUMNS):
+            self.nodal_raw(min(self.MAX_COLUMNS, m - j), S[j], 24 * self.n_elems, out[j], 6 * self.n_nodes)
+        return out[0] if vec else out
+
+    def error(self, sigma, nodal=None, other=None) -> dict:
+        """Stress error per element in the energy norm: Gauss-point stresses ``(m, n_elems, 4, 6)`` against exactly one of
+        ``nodal (m, n_nodes, 6)`` (interpolated quadratically; with :meth:`nodal` of ``sigma`` this is the Zienkiewicz-Zhu
+        estimate) and ``other (m, n_elems, 4, 6)`` (a second Gauss-point field).  Returns ``eta2 (m, n_elems)`` and
+        ``eta2_total``, ``eta2_max``, ``eta2_argmax (m,)``, in launches of at most 16 columns.  Inputs without the leading
+        ``m`` drop it."""
+        import torch
+
+        if (nodal is None) == (other is None):
+            raise ValueError("exactly one of nodal and other is needed")
+        S, vec = self._gauss(sigma, "sigma")
+        m, ne, nn, dev = S.shape[0], self.n_elems, self.n_nodes, self.torch_device
+        if nodal is not None:
+            self._check(nodal, "nodal")
+            O = (nodal.reshape(1, *nodal.shape) if nodal.dim() == 2 else nodal).contiguous()
+            if tuple(O.shape) != (m, nn, 6):
+                raise ValueError(f"expected nodal of shape ({m}, {nn}, 6), got {tuple(nodal.shape)}")
+        else:
+            O, _ = self._gauss(other, "other")
+            if O.shape[0] != m:
+                raise ValueError(f"expected other of {m} columns, got {O.shape[0]}")
+        out = {"eta2": torch.empty((m, ne), dtype=torch.float64, device=dev),
+               "eta2_total": torch.empty(m, dtype=torch.float64, device=dev),
+               "eta2_max": torch.empty(m, dtype=torch.float64, device=dev),
+               "eta2_argmax": torch.empty(m, dtype=torch.int32, device=dev)}
+        for j in range(0, m, self.MAX_COLUMNS):
+            c = min(self.MAX_COLUMNS, m - j)
+            node, oth = (O[j], None) if nodal is not None else (None, O[j])
+            self.error_raw(c, S[j], 24 * ne, node, 6 * nn, oth, 24 * ne, out["eta2"][j], ne, out["eta2_total"][j:],
+                           out["eta2_max"][j:], out["eta2_argmax"][j:])
+        return {k: v[0] for k, v in out.items()} if vec else out
+
+    def estimate(self, X) -> dict:
+        """Zienkiewicz-Zhu estimate of the stress error of displacement columns ``(m, n_dof)`` (or one ``(n_dof,)``
+        vector): Gauss-point stress -> recovered nodal stress -> :meth:`error`.  Returns the dict of :meth:`error` plus
         ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish)."""
         import torch
 
