@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration; so did the partition entry points of the operator stepper, saa_operator_stepper_set_shared, _set_interface_buffer, _step_begin, _step_finish, _step_predicted, _halo_gather and _halo_scatter). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -498,6 +498,50 @@ int saa_operator_stepper_set_recorder(saa_operator_stepper *st, double *traj_dev
 int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *name, double value);
 int saa_operator_stepper_step(saa_operator_stepper *st, int32_t nsteps);
 int saa_operator_stepper_destroy(saa_operator_stepper *st);
+
+/*
+ * The operator stepper on one rank of a partition, either order: the synchronised step (MODEL=False, Dynamic_solver.py:22-32)
+ * split around the caller's reduction of the shared-node forces, the predicted step with the shared-dof overwrite
+ * (Online_predictor.py:287-316) and the gather / scatter of the shared dofs.  The meaning is that of saa_step_begin,
+ * saa_step_finish, saa_step_predicted, saa_halo_gather and saa_halo_scatter on the linear solver handle.  Device pointers
+ * except where marked host; enqueued on the operator's stream with no host synchronisation (set_shared synchronises); no
+ * floating-point atomics, bitwise repeatable.
+ *
+ * saa_operator_stepper_set_shared: shared_local_host[k] is the local node id of this rank's k-th shared node,
+ *   shared_slots_host[k] its position in the sorted Global_shared of n_global_shared nodes; a table or history row is
+ *   3*n_shared doubles in that order (loc_dof_shared).  SAA_E_ARG on ids or slots out of range or repeated, or
+ *   n_shared > n_global_shared.  n_shared = 0 clears the rank's shared set (with n_global_shared > 0 every slot is foreign).
+ *   Builds on the device the map node -> k (-1 for a node that is not shared), the lists of nodes and slots, and the list
+ *   of foreign slots: those of Global_shared that this rank does not hold.
+ * saa_operator_stepper_set_interface_buffer: 3*n_global_shared doubles, caller-owned, zero when handed over.
+ * saa_operator_stepper_step_begin: the K element pass for d0 (the variant "stored_geometry" selects) and one node pass.  A
+ *   node that is not shared is updated and recorded as saa_operator_stepper_step does it.  A shared node's contributions,
+ *   summed in ascending element order, go to iface[3*slot + c]; its dn entry is left alone: d1 overwrites dn in place in
+ *   this stepper, so unlike the linear kernel there is no provisional update of shared nodes.  The stepper is then pending.
+ * saa_operator_stepper_step_finish: one launch over the shared dofs and the foreign slots.  d1 from iface[3*slot + c] - by
+ *   now the sum over the ranks -, the stepper's mass and load, d0, dn and the step's ramp, by the same device function as the
+ *   node pass; 0 on a Dirichlet dof; written over dn, into the recorder column and into
+ *   hist_dev[hist_row*3*n_shared + 3k + c] when hist_dev is not NULL.  Foreign slots are zeroed again.  Then the buffers
+ *   swap, tn += dt and the step index advances.
+ * saa_operator_stepper_step_predicted: nsteps steps of two launches each.  Shared dofs take
+ *   table_dev[(table_row0 + k)*3*n_shared + ...] unconditionally, on a Dirichlet dof too (Online_predictor.py:298); the value
+ *   also goes to row hist_row0 + k of hist_dev (NULL: none) and to the recorder.  Other nodes as saa_operator_stepper_step.
+ * saa_operator_stepper_halo_gather / _halo_scatter: row_dev[3k + c] <-> the current d0 at the shared dofs.
+ * saa_operator_stepper_step is unchanged: with a shared set it is the local step without overwrite (MODEL=True).  The
+ *   begin / finish / predicted steps ignore the "passes" measurement option.
+ * SAA_E_STATE: step_finish without step_begin; step, step_predicted, step_begin, set_state, set_recorder, set_option,
+ *   set_shared, set_interface_buffer, halo_scatter while pending; step_begin with n_global_shared > 0 and no interface
+ *   buffer.  SAA_E_ARG: null handle, negative nsteps or rows, a null table or row with n_shared > 0.
+ */
+int saa_operator_stepper_set_shared(saa_operator_stepper *st, int32_t n_shared, const int32_t *shared_local_host,
+                                    const int32_t *shared_slots_host, int32_t n_global_shared);
+int saa_operator_stepper_set_interface_buffer(saa_operator_stepper *st, double *iface_dev);
+int saa_operator_stepper_step_begin(saa_operator_stepper *st);
+int saa_operator_stepper_step_finish(saa_operator_stepper *st, double *hist_dev, int64_t hist_row);
+int saa_operator_stepper_step_predicted(saa_operator_stepper *st, int32_t nsteps, const double *table_dev, int64_t table_row0,
+                                        double *hist_dev, int64_t hist_row0);
+int saa_operator_stepper_halo_gather(saa_operator_stepper *st, double *row_dev);
+int saa_operator_stepper_halo_scatter(saa_operator_stepper *st, const double *row_dev);
 
 /*
  * Shared-node predictor: the per-rank LSTM encoder-decoder of Tools/DNN_tools.py:16-98 (2-layer bidirectional encoder of

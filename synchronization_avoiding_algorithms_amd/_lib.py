@@ -157,6 +157,13 @@ SIGNATURES = {
     "saa_operator_stepper_set_option": (C.c_int, [_H, C.c_char_p, C.c_double]),
     "saa_operator_stepper_step": (C.c_int, [_H, C.c_int32]),
     "saa_operator_stepper_destroy": (C.c_int, [_H]),
+    "saa_operator_stepper_set_shared": (C.c_int, [_H, C.c_int32, _ip, _ip, C.c_int32]),
+    "saa_operator_stepper_set_interface_buffer": (C.c_int, [_H, C.c_void_p]),
+    "saa_operator_stepper_step_begin": (C.c_int, [_H]),
+    "saa_operator_stepper_step_finish": (C.c_int, [_H, C.c_void_p, C.c_int64]),
+    "saa_operator_stepper_step_predicted": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "saa_operator_stepper_halo_gather": (C.c_int, [_H, C.c_void_p]),
+    "saa_operator_stepper_halo_scatter": (C.c_int, [_H, C.c_void_p]),
 }
 
 _lib = None

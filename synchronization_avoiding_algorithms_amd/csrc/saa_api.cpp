@@ -2248,6 +2248,7 @@ int saa_operator_stepper_create(saa_operator *op, const double *mass_dev, const 
 int saa_operator_stepper_set_state(saa_operator_stepper *st, const double *d0_dev, const double *dn_dev, double tn) {
   if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_state: null handle");
   if (!std::isfinite(tn)) return fail(SAA_E_ARG, "saa_operator_stepper_set_state: tn must be finite");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_state: a synchronised step is in flight");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   const hipError_t e = saa::opstep_set_state(st->impl, d0_dev, dn_dev, tn);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_state: ") + hipGetErrorString(e));
@@ -2267,12 +2268,14 @@ int saa_operator_stepper_set_recorder(saa_operator_stepper *st, double *traj_dev
   if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_recorder: null handle");
   if (traj_dev && (n_cols <= 0 || save_every <= 0 || next_step_index < 0))
     return fail(SAA_E_ARG, "saa_operator_stepper_set_recorder: bad argument");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_recorder: a synchronised step is in flight");
   saa::opstep_set_recorder(st->impl, traj_dev, traj_dev ? n_cols : 0, traj_dev ? save_every : 1, traj_dev ? next_step_index : 0);
   return SAA_OK;
 }
 
 int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *name, double value) {
   if (!st || !st->impl || !name) return fail(SAA_E_ARG, "saa_operator_stepper_set_option: null handle or name");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_option: a synchronised step is in flight");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   hipError_t e = hipSuccess;
   if (!saa::opstep_set_option(st->impl, name, value, &e))
@@ -2284,10 +2287,91 @@ int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *name, 
 int saa_operator_stepper_step(saa_operator_stepper *st, int32_t nsteps) {
   if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step: null handle");
   if (nsteps < 0) return fail(SAA_E_ARG, "saa_operator_stepper_step: nsteps < 0");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step: a synchronised step is in flight");
   if (nsteps == 0) return SAA_OK;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   const hipError_t e = saa::opstep_step(st->impl, nsteps);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_set_shared(saa_operator_stepper *st, int32_t n_shared, const int32_t *shared_local_host,
+                                    const int32_t *shared_slots_host, int32_t n_global_shared) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_shared: null handle");
+  if (n_shared < 0 || n_global_shared < n_shared)
+    return fail(SAA_E_ARG, "saa_operator_stepper_set_shared: need 0 <= n_shared <= n_global_shared");
+  if (n_shared > 0 && (!shared_local_host || !shared_slots_host))
+    return fail(SAA_E_ARG, "saa_operator_stepper_set_shared: null shared_local_host or shared_slots_host");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_shared: a synchronised step is in flight");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  std::string err;
+  const hipError_t e = saa::opstep_set_shared(st->impl, n_shared, shared_local_host, shared_slots_host, n_global_shared, err);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_stepper_set_shared: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+  }
+  return SAA_OK;
+}
+
+int saa_operator_stepper_set_interface_buffer(saa_operator_stepper *st, double *iface_dev) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_interface_buffer: null handle");
+  if (saa::opstep_pending(st->impl))
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_interface_buffer: a synchronised step is in flight");
+  saa::opstep_set_interface_buffer(st->impl, iface_dev);
+  return SAA_OK;
+}
+
+int saa_operator_stepper_step_begin(saa_operator_stepper *st) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step_begin: null handle");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step_begin: previous step not finished");
+  if (saa::opstep_lacks_interface_buffer(st->impl))
+    return fail(SAA_E_STATE, "saa_operator_stepper_step_begin: no interface buffer set");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_step_begin(st->impl);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step_begin: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_step_finish(saa_operator_stepper *st, double *hist_dev, int64_t hist_row) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step_finish: null handle");
+  if (hist_dev && hist_row < 0) return fail(SAA_E_ARG, "saa_operator_stepper_step_finish: negative history row");
+  if (!saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step_finish: no step in flight");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_step_finish(st->impl, hist_dev, hist_row);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step_finish: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_step_predicted(saa_operator_stepper *st, int32_t nsteps, const double *table_dev, int64_t table_row0,
+                                        double *hist_dev, int64_t hist_row0) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step_predicted: null handle");
+  if (nsteps < 0 || table_row0 < 0 || (hist_dev && hist_row0 < 0))
+    return fail(SAA_E_ARG, "saa_operator_stepper_step_predicted: negative nsteps or row");
+  if (saa::opstep_n_shared(st->impl) > 0 && !table_dev) return fail(SAA_E_ARG, "saa_operator_stepper_step_predicted: null table");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step_predicted: a synchronised step is in flight");
+  if (nsteps == 0) return SAA_OK;
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_step_predicted(st->impl, nsteps, table_dev, table_row0, hist_dev, hist_row0);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step_predicted: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_halo_gather(saa_operator_stepper *st, double *row_dev) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_halo_gather: null handle");
+  if (saa::opstep_n_shared(st->impl) > 0 && !row_dev) return fail(SAA_E_ARG, "saa_operator_stepper_halo_gather: null row");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_halo(st->impl, row_dev, true);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_halo_gather: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_halo_scatter(saa_operator_stepper *st, const double *row_dev) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_halo_scatter: null handle");
+  if (saa::opstep_n_shared(st->impl) > 0 && !row_dev) return fail(SAA_E_ARG, "saa_operator_stepper_halo_scatter: null row");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_halo_scatter: a synchronised step is in flight");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_halo(st->impl, const_cast<double *>(row_dev), false);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_halo_scatter: ") + hipGetErrorString(e));
   return SAA_OK;
 }
 

@@ -42,4 +42,29 @@ void opstep_set_recorder(OpStepper *st, double *traj, int64_t n_cols, int32_t sa
 bool opstep_set_option(OpStepper *st, const char *name, double value, hipError_t *e);
 hipError_t opstep_step(OpStepper *st, int32_t nsteps);
 
+// One rank of a partition.  shared_local[k] = local node id of the rank's k-th shared node, shared_slots[k] = its place in the
+// sorted Global_shared (both host arrays, n_shared entries); a table or history row is 3 * n_shared doubles in that order.
+// Builds on the device the map node -> k (-1: not shared), the two lists and the list of foreign slots (those of the
+// n_global_shared that this rank does not hold).  Ids out of range or repeated: err is set, hipErrorInvalidValue.
+// n_shared = n_global_shared = 0 clears the set.  Synchronises the stream.
+hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *shared_local, const int32_t *shared_slots,
+                             int32_t n_global_shared, std::string &err);
+void opstep_set_interface_buffer(OpStepper *st, double *iface);  // 3 * n_global_shared device doubles, caller-owned
+bool opstep_pending(const OpStepper *st);                        // between step_begin and step_finish
+int32_t opstep_n_shared(const OpStepper *st);
+bool opstep_lacks_interface_buffer(const OpStepper *st);         // there are global shared slots and no buffer
+// The synchronised step around the caller's reduction of the interface buffer.  begin: element pass of d0 and the node pass
+// in which a shared node's summed contributions go to iface[3 slot + c] and its dn entry is left alone (d1 overwrites dn in
+// place, so there is no provisional update).  finish: one launch over the shared dofs and foreign slots - d1 from the
+// summed iface over dn, into the recorder column and row hist_row of hist (3 * n_shared wide, NULL: none); foreign slots
+// zeroed; then swap, tn += dt, step index + 1.  Both ignore the "passes" option.
+hipError_t opstep_step_begin(OpStepper *st);
+hipError_t opstep_step_finish(OpStepper *st, double *hist, int64_t hist_row);
+// nsteps steps of two launches: shared dofs take table[(table_row0 + k) * 3 n_shared + ...] unconditionally (Dirichlet dofs
+// too), which also goes to row hist_row0 + k of hist and to the recorder; other nodes as opstep_step.
+hipError_t opstep_step_predicted(OpStepper *st, int32_t nsteps, const double *table, int64_t table_row0, double *hist,
+                                 int64_t hist_row0);
+// gather: row[3 k + c] = d0[3 node_k + c]; else the reverse.
+hipError_t opstep_halo(OpStepper *st, double *row, bool gather);
+
 }  // namespace saa

@@ -14,11 +14,17 @@
 //    CSR in ascending element order, forms d1 and writes it over dn (a lane touches its own node only, so two buffers and a
 //    pointer swap are the whole state), and writes the recorder column.  f_int never exists in memory.  No floating-point
 //    atomics; every result is bitwise repeatable.  The loop is not captured in a HIP graph.
+//  * The same step on one rank of a partition (saa_operator_stepper_set_shared).  Synchronised: opstep_shared_node_kernel
+//    <false> is the node pass that sends a shared node's sum to the interface buffer instead of updating it, and after the
+//    caller's reduction over the ranks opstep_shared_finish_kernel, one lane per shared or foreign dof, updates the shared
+//    dofs.  Predicted: opstep_shared_node_kernel<true> writes the table row over the shared dofs and into the history in the
+//    node pass itself, so a predicted step stays at two launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "saa_modal_op.h"
 #include "saa_opstep.h"
@@ -240,6 +246,108 @@ __global__ void __launch_bounds__(kThreads) opstep_node_update_kernel(
   }
 }
 
+// ---- a partition of the mesh: shared nodes (saa_operator_stepper_set_shared) ---------------------------------------------
+// The update of one dof, Dynamic_solver.py:13-20: the text of opstep_node_update_kernel's loop body, shared by every kernel
+// below so that a shared node is rounded by the finish kernel exactly as the node pass would have rounded it.
+__device__ __forceinline__ double opstep_update_dof(bool live, double s, double fi, double m, double x0, double xn, double dt,
+                                                    double alpha, double scale) {
+  const double num = dt * dt * (scale * fi - s) + 2.0 * m * x0 - m * xn + 0.5 * dt * m * alpha * xn;
+  const double den = m + alpha * m * 0.5 * dt;
+  return live ? num / den : 0.0;
+}
+
+// The node pass of a partition, one lane per node.  A node that is not shared (shared_of[v] < 0) is updated as by
+// opstep_node_update_kernel.  A shared node, k = shared_of[v] its place in the rank's shared list:
+//   PREDICTED = false (step_begin): its summed contributions go to iface[3 slot[k] + c]; dn and the recorder are left
+//     alone, because d1 overwrites dn in place and the true d1 needs the other ranks' sums (opstep_shared_finish_kernel);
+//   PREDICTED = true: d1 = table_row[3 k + c] unconditionally, a Dirichlet dof included (halo_overwrite_kernel,
+//     Online_predictor.py:298), recorded in hist_row (:301) and in the recorder column.
+template <bool PREDICTED>
+__global__ void __launch_bounds__(kThreads) opstep_shared_node_kernel(
+    int32_t n_nodes, const int64_t *__restrict__ offsets, const int32_t *__restrict__ pairs, const double *__restrict__ free_mask,
+    const double *__restrict__ contrib, const double *__restrict__ mass, const double *__restrict__ f, const double *__restrict__ d0,
+    double *__restrict__ dn, double dt, double alpha, double scale, double *__restrict__ traj, int64_t n_cols, int64_t col,
+    const int32_t *__restrict__ shared_of, const int32_t *__restrict__ slot, double *__restrict__ iface,
+    const double *__restrict__ table_row, double *__restrict__ hist_row) {
+  const int64_t v = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+  if (v >= n_nodes) return;
+  const int32_t k = shared_of[v];
+  if (PREDICTED && k >= 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int64_t i = 3 * v + c;
+      const double d1 = table_row[3 * (int64_t)k + c];
+      dn[i] = d1;
+      if (hist_row) hist_row[3 * (int64_t)k + c] = d1;
+      if (col >= 0) traj[i * n_cols + col] = d1;
+    }
+    return;
+  }
+  const int64_t b = offsets[v], end = offsets[v + 1];
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = b; i < end; ++i) {
+    const double *q = contrib + 3 * (int64_t)pairs[i];
+    s[0] += q[0];
+    s[1] += q[1];
+    s[2] += q[2];
+  }
+  if (!PREDICTED && k >= 0) {
+    double *o = iface + 3 * (int64_t)slot[k];
+    o[0] = s[0];
+    o[1] = s[1];
+    o[2] = s[2];
+    return;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int64_t i = 3 * v + c;
+    const double d1 = opstep_update_dof(end > b && free_mask[i] != 0.0, s[c], f[i], mass[i], d0[i], dn[i], dt, alpha, scale);
+    dn[i] = d1;
+    if (col >= 0) traj[i * n_cols + col] = d1;
+  }
+}
+
+// After the reduction of iface over the ranks, one lane per shared dof and per foreign dof: d1 of shared dof 3 k + c from
+// the summed force iface[3 slot[k] + c] (0 on a Dirichlet dof) over dn, into the recorder column and into hist_row; the
+// slots of shared nodes this rank does not hold are zeroed, so that the next sum sees fresh partial forces only
+// (iface_finish_kernel of saa_kernels.hip).
+__global__ void __launch_bounds__(kThreads) opstep_shared_finish_kernel(
+    int32_t n_shared, int32_t n_foreign, const int32_t *__restrict__ node, const int32_t *__restrict__ slot,
+    const int32_t *__restrict__ foreign, const int64_t *__restrict__ offsets, const double *__restrict__ free_mask,
+    const double *__restrict__ mass, const double *__restrict__ f, const double *__restrict__ d0, double *__restrict__ dn, double dt,
+    double alpha, double scale, double *__restrict__ traj, int64_t n_cols, int64_t col, double *__restrict__ iface,
+    double *__restrict__ hist_row) {
+  const int64_t j = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+  const int64_t n_local = 3 * (int64_t)n_shared;
+  if (j < n_local) {
+    const int64_t k = j / 3;
+    const int c = (int)(j - 3 * k);
+    const int64_t v = node[k], i = 3 * v + c;
+    const double s = iface[3 * (int64_t)slot[k] + c];
+    const double d1 =
+        opstep_update_dof(offsets[v + 1] > offsets[v] && free_mask[i] != 0.0, s, f[i], mass[i], d0[i], dn[i], dt, alpha, scale);
+    dn[i] = d1;
+    if (col >= 0) traj[i * n_cols + col] = d1;
+    if (hist_row) hist_row[j] = d1;
+  } else if (j < n_local + 3 * (int64_t)n_foreign) {
+    const int64_t r = j - n_local;
+    iface[3 * (int64_t)foreign[r / 3] + (r % 3)] = 0.0;
+  }
+}
+
+// row[3 k + c] = d[3 node[k] + c] (GATHER) or the reverse, one lane per shared dof.
+template <bool GATHER>
+__global__ void __launch_bounds__(kThreads) opstep_halo_kernel(int32_t n_shared, const int32_t *__restrict__ node, double *d,
+                                                               double *row) {
+  const int64_t j = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+  if (j >= 3 * (int64_t)n_shared) return;
+  const int64_t i = 3 * (int64_t)node[j / 3] + (j % 3);
+  if (GATHER)
+    row[j] = d[i];
+  else
+    d[i] = row[j];
+}
+
 #define OPSTEP_TRY(expr)             \
   do {                               \
     const hipError_t e_ = (expr);    \
@@ -260,6 +368,12 @@ struct OpStepper {
   double *traj = nullptr;
   int64_t n_cols = 0, step_index = 0;
   int32_t save_every = 1;
+  // the partition: shared_of[v] = k for the rank's k-th shared node (else -1), node[k], slot[k] its place in Global_shared,
+  // foreign[] the slots of Global_shared this rank does not hold
+  int32_t n_shared = 0, n_foreign = 0, n_global_shared = 0;
+  int32_t *shared_of = nullptr, *node = nullptr, *slot = nullptr, *foreign = nullptr;
+  double *iface = nullptr;  // caller-owned, 3 * n_global_shared
+  bool pending = false;     // between step_begin and step_finish
 };
 
 namespace {
@@ -318,7 +432,7 @@ hipError_t operator_lumped_mass(ModalOp *op, double *mass) {
 void opstep_destroy(OpStepper *st) {
   if (!st) return;
   (void)hipSetDevice(st->op->device);
-  void *bufs[] = {st->mass, st->f, st->buf[0], st->buf[1], st->geom, st->bits};
+  void *bufs[] = {st->mass, st->f, st->buf[0], st->buf[1], st->geom, st->bits, st->shared_of, st->node, st->slot, st->foreign};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   delete st;
@@ -434,6 +548,148 @@ hipError_t opstep_step(OpStepper *st, int32_t nsteps) {
     ++st->step_index;
   }
   return hipSuccess;
+}
+
+namespace {
+
+double ramp_scale(const OpStepper *st) { return st->ramp ? (st->tn < 1.0 ? st->tn : 1.0) : 1.0; }  // min(tn, 1)
+
+int64_t recorder_column(const OpStepper *st) {
+  if (st->traj && st->step_index % st->save_every == 0 && st->step_index / st->save_every < st->n_cols)
+    return st->step_index / st->save_every;
+  return -1;
+}
+
+void advance(OpStepper *st) {
+  st->cur = 1 - st->cur;
+  st->tn += st->dt;
+  ++st->step_index;
+}
+
+// shared_of of a stepper without a shared set: all -1, built on first need
+hipError_t ensure_shared_map(OpStepper *st) {
+  if (st->shared_of) return hipSuccess;
+  const size_t n = static_cast<size_t>(st->op->n_nodes);
+  OPSTEP_TRY(dev_alloc(&st->shared_of, n));
+  return hipMemsetAsync(st->shared_of, 0xff, (n ? n : 1) * sizeof(int32_t), st->op->stream);
+}
+
+}  // namespace
+
+bool opstep_pending(const OpStepper *st) { return st->pending; }
+int32_t opstep_n_shared(const OpStepper *st) { return st->n_shared; }
+bool opstep_lacks_interface_buffer(const OpStepper *st) { return st->n_global_shared > 0 && !st->iface; }
+void opstep_set_interface_buffer(OpStepper *st, double *iface) { st->iface = iface; }
+
+hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *shared_local, const int32_t *shared_slots,
+                             int32_t n_global_shared, std::string &err) {
+  ModalOp *op = st->op;
+  const int32_t n_nodes = op->n_nodes;
+  std::vector<int32_t> of(static_cast<size_t>(n_nodes), -1), foreign;
+  std::vector<char> held(static_cast<size_t>(n_global_shared), 0);
+  for (int32_t k = 0; k < n_shared; ++k) {
+    const int32_t v = shared_local[k], s = shared_slots[k];
+    if (v < 0 || v >= n_nodes || s < 0 || s >= n_global_shared) {
+      err = "saa_operator_stepper_set_shared: shared node " + std::to_string(k) + " has node id " + std::to_string(v) +
+            " or slot " + std::to_string(s) + " out of range";
+      return hipErrorInvalidValue;
+    }
+    if (of[v] >= 0 || held[s]) {
+      err = "saa_operator_stepper_set_shared: node id " + std::to_string(v) + " or slot " + std::to_string(s) + " is repeated";
+      return hipErrorInvalidValue;
+    }
+    of[v] = k;
+    held[s] = 1;
+  }
+  for (int32_t s = 0; s < n_global_shared; ++s)
+    if (!held[s]) foreign.push_back(s);
+  // the old lists may still be read by work in flight
+  OPSTEP_TRY(hipStreamSynchronize(op->stream));
+  void *old[] = {st->shared_of, st->node, st->slot, st->foreign};
+  for (void *b : old)
+    if (b) (void)hipFree(b);
+  st->shared_of = st->node = st->slot = st->foreign = nullptr;
+  st->n_shared = st->n_foreign = st->n_global_shared = 0;
+  if (n_shared == 0 && n_global_shared == 0) return hipSuccess;
+  const int32_t n_foreign = static_cast<int32_t>(foreign.size());
+  OPSTEP_TRY(dev_alloc(&st->shared_of, of.size()));
+  OPSTEP_TRY(dev_alloc(&st->node, static_cast<size_t>(n_shared)));
+  OPSTEP_TRY(dev_alloc(&st->slot, static_cast<size_t>(n_shared)));
+  OPSTEP_TRY(dev_alloc(&st->foreign, foreign.size()));
+  if (n_nodes > 0) OPSTEP_TRY(hipMemcpy(st->shared_of, of.data(), of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (n_shared > 0) {
+    OPSTEP_TRY(hipMemcpy(st->node, shared_local, static_cast<size_t>(n_shared) * sizeof(int32_t), hipMemcpyHostToDevice));
+    OPSTEP_TRY(hipMemcpy(st->slot, shared_slots, static_cast<size_t>(n_shared) * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  if (n_foreign > 0) OPSTEP_TRY(hipMemcpy(st->foreign, foreign.data(), foreign.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  st->n_shared = n_shared;
+  st->n_foreign = n_foreign;
+  st->n_global_shared = n_global_shared;
+  return hipSuccess;
+}
+
+hipError_t opstep_step_begin(OpStepper *st) {
+  ModalOp *op = st->op;
+  double *contrib = nullptr;
+  OPSTEP_TRY(operator_scratch(op, 1, &contrib));
+  OPSTEP_TRY(ensure_shared_map(st));
+  const double *d0 = st->buf[st->cur];
+  OPSTEP_TRY(element_pass(st, d0, contrib));
+  hipLaunchKernelGGL(opstep_shared_node_kernel<false>, grid_for(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets,
+                     op->pairs, op->free_mask, contrib, st->mass, st->f, d0, st->buf[1 - st->cur], st->dt, st->alpha, ramp_scale(st),
+                     st->traj, st->n_cols, recorder_column(st), st->shared_of, st->slot, st->iface, nullptr, nullptr);
+  OPSTEP_TRY(hipGetLastError());
+  st->pending = true;
+  return hipSuccess;
+}
+
+hipError_t opstep_step_finish(OpStepper *st, double *hist, int64_t hist_row) {
+  ModalOp *op = st->op;
+  const int64_t lanes = 3 * (static_cast<int64_t>(st->n_shared) + st->n_foreign);
+  if (lanes > 0) {
+    double *row = hist ? hist + hist_row * 3 * static_cast<int64_t>(st->n_shared) : nullptr;
+    hipLaunchKernelGGL(opstep_shared_finish_kernel, grid_for(lanes), dim3(kThreads), 0, op->stream, st->n_shared, st->n_foreign,
+                       st->node, st->slot, st->foreign, op->offsets, op->free_mask, st->mass, st->f, st->buf[st->cur],
+                       st->buf[1 - st->cur], st->dt, st->alpha, ramp_scale(st), st->traj, st->n_cols, recorder_column(st), st->iface,
+                       row);
+    OPSTEP_TRY(hipGetLastError());
+  }
+  st->pending = false;
+  advance(st);
+  return hipSuccess;
+}
+
+hipError_t opstep_step_predicted(OpStepper *st, int32_t nsteps, const double *table, int64_t table_row0, double *hist,
+                                 int64_t hist_row0) {
+  ModalOp *op = st->op;
+  if (nsteps <= 0) return hipSuccess;
+  double *contrib = nullptr;
+  OPSTEP_TRY(operator_scratch(op, 1, &contrib));
+  OPSTEP_TRY(ensure_shared_map(st));
+  const int64_t width = 3 * static_cast<int64_t>(st->n_shared);
+  for (int32_t k = 0; k < nsteps; ++k) {
+    const double *d0 = st->buf[st->cur];
+    OPSTEP_TRY(element_pass(st, d0, contrib));
+    hipLaunchKernelGGL(opstep_shared_node_kernel<true>, grid_for(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets,
+                       op->pairs, op->free_mask, contrib, st->mass, st->f, d0, st->buf[1 - st->cur], st->dt, st->alpha, ramp_scale(st),
+                       st->traj, st->n_cols, recorder_column(st), st->shared_of, st->slot, nullptr,
+                       width > 0 ? table + (table_row0 + k) * width : nullptr, hist ? hist + (hist_row0 + k) * width : nullptr);
+    OPSTEP_TRY(hipGetLastError());
+    advance(st);
+  }
+  return hipSuccess;
+}
+
+hipError_t opstep_halo(OpStepper *st, double *row, bool gather) {
+  const int64_t lanes = 3 * static_cast<int64_t>(st->n_shared);
+  if (lanes == 0) return hipSuccess;
+  if (gather)
+    hipLaunchKernelGGL(opstep_halo_kernel<true>, grid_for(lanes), dim3(kThreads), 0, st->op->stream, st->n_shared, st->node,
+                       st->buf[st->cur], row);
+  else
+    hipLaunchKernelGGL(opstep_halo_kernel<false>, grid_for(lanes), dim3(kThreads), 0, st->op->stream, st->n_shared, st->node,
+                       st->buf[st->cur], row);
+  return hipGetLastError();
 }
 
 }  // namespace saa

@@ -69,6 +69,10 @@ def _dist_env():
 def make_partition(mesh, world, how="slab"):
     if world == 1:
         return np.zeros(len(mesh.tets), dtype=np.int64)
+    if how == "graph":
+        from .mesh import graph_partition
+
+        return graph_partition(mesh, world)
     return slab_partition(mesh, world) if how == "slab" else rcb_partition(mesh, world)
 
 
@@ -254,12 +258,14 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
 
 
 def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1, E=None, nu=None, rho=None, fz=None,
-             alpha=None, gamma=None):
+             alpha=None, gamma=None, parts=0, partition="slab"):
     """The explicit run of the whole mesh on one GPU through the operator handle (:func:`dynamics.run_dynamics`), for
     linear (``order=1``) or quadratic tetrahedra (``order=2``: the mesh is elevated like ``steady_state --order 2``),
     clamped on every node of ``x = 0``: lumped mass of the handle (HRZ for order 2), the reference load ``(0, -fz, -fz)``
     with the ramp, ``alpha`` of ``Data_prepare.py:41`` and ``dt = gamma * 2/omega_max``.  Writes
-    ``Results/Dynamics/Displacement_order{p}.hdf5`` and returns ``(path, report)``."""
+    ``Results/Dynamics/Displacement_order{p}.hdf5`` and returns ``(path, report)``.  ``parts = P > 0``: the same run on
+    the mesh cut into ``P`` parts (``partition``: slab, graph or rcb, on the vertex tetrahedra), every synchronised step
+    split around the sum of the shared-node forces (:class:`dynamics.OperatorPartition`); same file."""
     from .dynamics import run_dynamics
     from .mesh import plane_nodes
 
@@ -270,7 +276,8 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     if order == 2:
         mesh = _quadratic(mesh)
     cells = mesh.tets10 if order == 2 else mesh.tets
-    store, report = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device, **p)
+    epart = make_partition(mesh, int(parts), partition) if parts and int(parts) > 0 else None
+    store, report = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device, epart=epart, **p)
     path = rio.save_displacement(os.path.join(out_dir, PATHS["dynamics"].format(p=order)), store)
     return path, report
 
@@ -764,7 +771,9 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=100000)      # test_num, Data_prepare.py:49
     ap.add_argument("--save-every", type=int, default=1)      # Data_prepare.py:50
     ap.add_argument("--out", default=".")
-    ap.add_argument("--partition", choices=["slab", "rcb"], default="slab")
+    ap.add_argument("--partition", choices=["slab", "graph", "rcb"], default="slab")
+    ap.add_argument("--parts", type=int, default=0,
+                    help="dynamics: cut the mesh into this many parts and run them as ranks of a partition on one GPU")
     ap.add_argument("--n-past", type=int, default=20)
     ap.add_argument("--n-future", type=int, default=20)
     ap.add_argument("--filter-size", type=int, default=150)
@@ -799,7 +808,8 @@ def main(argv=None):
         if args.command == "modal":
             print(json.dumps(modal(mesh, k=args.k, device=local, order=args.order)))
         elif args.command == "dynamics":
-            path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order)
+            path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order,
+                                    parts=args.parts, partition=args.partition)
             print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]

@@ -8,7 +8,11 @@ on the handle (:func:`modal.stable_time_step_operator`), because the reference's
 (``Data_prepare.py:147``) lies 1.56 times above the stability limit for this element.  :class:`OperatorStepper` is
 the Python face of ``saa_operator_stepper_*``: two launches per step, state on the GPU.  On an order-1 handle it is not a
 rival of :class:`solver.HipExplicitSolver` (the LDS-resident step kernel); it serves both orders so that the production
-kernel is a second oracle for it."""
+kernel is a second oracle for it.
+
+The partitioned loop the project is named after runs on the same stepper: :class:`OperatorRank` is one rank of a partition
+of a replicated mesh of either order (synchronised steps split around a reduction of the shared-node forces, predicted
+steps with the shared-dof overwrite), :class:`OperatorPartition` all ranks in one process on one GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -31,6 +35,8 @@ class OperatorStepper:
         self.n_dof = op.n_dof
         self.dt = float(dt)
         self._traj = None
+        self._iface = None
+        self.n_shared = self.n_global_shared = 0
         m, f = self._vector(mass), self._vector(load)
         _lib.check(self._lib.saa_operator_stepper_create(op._h, _dev(m), _dev(f), float(dt), float(alpha), 1 if ramp else 0,
                                                          C.byref(self._h)))
@@ -105,6 +111,225 @@ class OperatorStepper:
         """``stored_geometry`` 0 / 1: the order-2 element pass recomputes its Jacobians / reads them from a table."""
         _lib.check(self._lib.saa_operator_stepper_set_option(self._h, name.encode(), float(value)))
 
+    # -- one rank of a partition -----------------------------------------------------------------------------------------
+    def set_shared(self, shared_local, shared_slots, n_global_shared):
+        """This rank's shared nodes (``RankLayout.shared_local`` / ``shared_slots``) among ``n_global_shared``; a table or
+        history row is ``3 * len(shared_local)`` values in that order.  Empty lists and 0 clear the set."""
+        a = np.ascontiguousarray(np.asarray(shared_local, dtype=np.int32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(shared_slots, dtype=np.int32).reshape(-1))
+        if a.size != b.size:
+            raise ValueError("shared_local and shared_slots differ in length")
+        ip = C.POINTER(C.c_int32)
+        _lib.check(self._lib.saa_operator_stepper_set_shared(self._h, int(a.size), a.ctypes.data_as(ip) if a.size else None,
+                                                             b.ctypes.data_as(ip) if b.size else None, int(n_global_shared)))
+        self.n_shared, self.n_global_shared = int(a.size), int(n_global_shared)
+
+    def set_interface_buffer(self, iface):
+        """``iface``: float64 CUDA tensor of ``3 * n_global_shared`` zeros, kept alive here; ``None`` takes it away."""
+        if iface is not None and (iface.numel() != 3 * self.n_global_shared or not iface.is_contiguous()):
+            raise ValueError("the interface buffer must hold 3 * n_global_shared contiguous doubles")
+        _lib.check(self._lib.saa_operator_stepper_set_interface_buffer(self._h, _dev(iface)))
+        self._iface = iface
+
+    def _rows(self, t, name, row0, n):
+        if t is not None and self.n_shared and (int(row0) < 0 or t.numel() < (int(row0) + int(n)) * 3 * self.n_shared):
+            raise ValueError(f"{name} must hold rows {int(row0)} .. {int(row0) + int(n) - 1} of {3 * self.n_shared} values")
+
+    def step_begin(self):
+        _lib.check(self._lib.saa_operator_stepper_step_begin(self._h))
+
+    def step_finish(self, hist=None, hist_row=0):
+        self._rows(hist, "hist", hist_row, 1)
+        _lib.check(self._lib.saa_operator_stepper_step_finish(self._h, _dev(hist), int(hist_row)))
+
+    def step_predicted(self, n, table, table_row0=0, hist=None, hist_row0=0):
+        self._rows(table, "table", table_row0, n)
+        self._rows(hist, "hist", hist_row0, n)
+        _lib.check(self._lib.saa_operator_stepper_step_predicted(self._h, int(n), _dev(table), int(table_row0), _dev(hist),
+                                                                 int(hist_row0)))
+
+    def halo_gather(self, row):
+        self._rows(row, "row", 0, 1)
+        _lib.check(self._lib.saa_operator_stepper_halo_gather(self._h, _dev(row)))
+
+    def halo_scatter(self, row):
+        self._rows(row, "row", 0, 1)
+        _lib.check(self._lib.saa_operator_stepper_halo_scatter(self._h, _dev(row)))
+
+
+class OperatorRank:
+    """One rank of a partition of a replicated mesh of either order (``Data_prepare.py:104-209`` for one rank): its
+    :class:`fem_setup.RankLayout` (from ``build_layouts`` on the 4- or 10-column cells), a :class:`modal.ModalOperator` on
+    its own elements, an :class:`OperatorStepper` with the rank's shared set, and its interface buffer ``iface``.
+
+    ``mass`` and ``load`` are the GLOBAL ``(3 n,)`` vectors; they are restricted with ``layout.local_dof`` as the reference
+    does (``Data_prepare.py:175-202``), so a shared node carries the other ranks' contributions too.  ``reduce(iface)``
+    sums the interface buffer over the ranks in place between the two halves of a synchronised step:
+    ``torch.distributed.all_reduce`` makes this a rank of a multi-process run; ``None`` is a world of one.  The object
+    presents what :func:`distributed.run_hybrid` uses."""
+
+    def __init__(self, points, layout, global_shared, mass, load, lmd, mu, rho, dt, alpha, reduce=None, ramp=True, device=0,
+                 stored_geometry=None):
+        import torch
+
+        from .modal import ModalOperator
+
+        self.layout, self.rank, self.reduce = layout, int(layout.rank), reduce
+        self.n_global_shared = len(global_shared)
+        points = np.asarray(points, dtype=np.float64)
+        self.op = ModalOperator(points[layout.nodes], layout.cells_local, layout.dirichlet_dofs, lmd, mu, rho, device)
+        self.tensor_device = self.op.torch_device
+        dof = torch.as_tensor(np.asarray(layout.local_dof, dtype=np.int64), device=self.tensor_device)
+
+        def local(a):
+            t = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+            return t.to(device=self.tensor_device, dtype=torch.float64).reshape(-1)[dof]
+
+        self.global_dof = dof
+        self.stepper = OperatorStepper(self.op, local(mass), local(load), dt, alpha, ramp=ramp)
+        if stored_geometry is not None:
+            self.stepper.set_option("stored_geometry", stored_geometry)
+        self.stepper.set_shared(layout.shared_local, layout.shared_slots, self.n_global_shared)
+        self.iface = torch.zeros(3 * self.n_global_shared, dtype=torch.float64, device=self.tensor_device)
+        self.stepper.set_interface_buffer(self.iface)
+        self.input_size = 3 * len(layout.shared_local)              # Online_predictor.py:126
+        self.dt = float(dt)
+        self.steps_done = 0
+
+    def step_synced(self, nsteps=1, hist=None, hist_row0=0):
+        """``MODEL=False`` steps: node pass, ``reduce(iface)``, shared-node update; ``hist`` row ``hist_row0 + k``."""
+        for k in range(int(nsteps)):
+            self.stepper.step_begin()
+            if self.reduce is not None:
+                self.reduce(self.iface)
+            self.stepper.step_finish(hist, hist_row0 + k)
+        self.steps_done += int(nsteps)
+
+    def step_local(self, nsteps=1):
+        """``MODEL=True`` steps without overwrite: the rank advances on its own partial forces."""
+        self.stepper.step(nsteps)
+        self.steps_done += int(nsteps)
+
+    def step_predicted(self, nsteps, table, table_row0=0, hist=None, hist_row0=0):
+        self.stepper.step_predicted(nsteps, table, table_row0, hist, hist_row0)
+        self.steps_done += int(nsteps)
+
+    def get_state(self):
+        return self.stepper.state()
+
+    def close(self):
+        self.stepper.close()
+        self.op.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def sum_interfaces(ranks, total):
+    """The reduction of a one-process partition: the ranks' interface buffers summed in rank order into ``total``, which is
+    copied back to every rank."""
+    total.copy_(ranks[0].iface)
+    for r in ranks[1:]:
+        total += r.iface
+    for r in ranks:
+        r.iface.copy_(total)
+
+
+class OperatorPartition:
+    """All ``P`` ranks of a partition in one process on one GPU: the one-GPU rehearsal of the partitioned loop.  The
+    whole-mesh operator is built once for the lumped mass (HRZ for order 2), the load ``(0, -fz, -fz)`` and ``dt = gamma *
+    2/omega_max`` (``dt`` given: taken as is; ``lame = (lambda, mu)`` given: instead of ``E``, ``nu``); then one
+    :class:`OperatorRank` per part of ``epart``."""
+
+    def __init__(self, points, cells, dirichlet_nodes, epart, n_parts=None, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5, gamma=0.9,
+                 ramp=True, device=0, stored_geometry=None, dt=None, lame=None):
+        import torch
+
+        from . import fem_setup as fs
+        from .modal import ModalOperator, stable_time_step_operator
+
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        epart = np.asarray(epart)
+        self.n_parts = int(n_parts) if n_parts is not None else int(epart.max()) + 1
+        self.n_dof = 3 * len(points)
+        dirichlet_nodes = np.asarray(dirichlet_nodes, dtype=np.int64)
+        lmd, mu = lame if lame is not None else fs.lame(E, nu)
+        with ModalOperator(points, cells, fs.node_to_dof(dirichlet_nodes), lmd, mu, rho, device) as op:
+            self.order, self.tensor_device = op.order, op.torch_device
+            mass, load = op.lumped_mass(), op.load((0.0, -fz, -fz))
+            self.time_step = {"dt": float(dt)} if dt is not None else stable_time_step_operator(op, mass, gamma)
+            torch.cuda.synchronize(device)
+        self.dt = self.time_step["dt"]
+        layouts, self.global_shared = fs.build_layouts(cells, epart, self.n_parts, len(points), dirichlet_nodes)
+        self.ranks = [OperatorRank(points, lay, self.global_shared, mass, load, lmd, mu, rho, self.dt, alpha, None, ramp, device,
+                                   stored_geometry) for lay in layouts]
+        self._sum = torch.zeros(3 * len(self.global_shared), dtype=torch.float64, device=self.tensor_device)
+
+    def reduce_in_rank_order(self):
+        sum_interfaces(self.ranks, self._sum)
+
+    def step_synced(self, n=1, hists=None, row0=0):
+        """``n`` synchronised steps of every rank in lockstep: all ``begin``, the sum, all ``finish``.  ``hists``: one
+        history tensor per rank (or None), row ``row0 + k`` written by step ``k``."""
+        for k in range(int(n)):
+            for r in self.ranks:
+                r.stepper.step_begin()
+            self.reduce_in_rank_order()
+            for i, r in enumerate(self.ranks):
+                r.stepper.step_finish(None if hists is None else hists[i], row0 + k)
+        for r in self.ranks:
+            r.steps_done += int(n)
+
+    def step_predicted(self, n, tables, table_row0=0, hists=None, hist_row0=0):
+        for i, r in enumerate(self.ranks):
+            r.step_predicted(n, tables[i], table_row0, None if hists is None else hists[i], hist_row0)
+
+    def run_hybrid(self, n_steps, predictors, n_past, n_future, filter_size):
+        """The schedule of :func:`distributed.run_hybrid` without resync, all ranks in lockstep: ``n_past * filter_size``
+        synchronised steps, then windows of ``n_future * filter_size`` predicted steps from ``predictors[r](i, hist_r)``.
+        Returns the per-rank ``(n_steps, input_size)`` histories."""
+        import torch
+
+        hists = [torch.zeros((int(n_steps), r.input_size), dtype=torch.float64, device=self.tensor_device) for r in self.ranks]
+        warm, window = int(n_past) * int(filter_size), int(n_future) * int(filter_size)
+        i = min(warm, int(n_steps))
+        self.step_synced(i, hists, 0)
+        while i < n_steps:
+            tables = [predictors[k](i, hists[k]) for k in range(self.n_parts)]
+            todo = min(window, int(n_steps) - i)
+            self.step_predicted(todo, tables, 0, hists, i)
+            i += todo
+        return hists
+
+    def gather(self, which="d0"):
+        """The global ``(3 n,)`` CUDA vector of ``d0`` or ``dn``; a shared node comes from its lowest holder."""
+        import torch
+
+        if which not in ("d0", "dn"):
+            raise ValueError("which must be d0 or dn")
+        out = torch.zeros(self.n_dof, dtype=torch.float64, device=self.tensor_device)
+        for r in reversed(self.ranks):
+            out[r.global_dof] = r.get_state()[0 if which == "d0" else 1]
+        return out
+
+    @property
+    def tn(self):
+        return self.ranks[0].get_state()[2]
+
+    def close(self):
+        for r in self.ranks:
+            r.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
 
 def reference_rule_dt(points, cells, E, nu, rho, gamma=0.9) -> float:
     """The reference's edge-length time step (``commons.py:79-90``, ``Data_prepare.py:147``) on the vertex tetrahedra of
@@ -115,11 +340,12 @@ def reference_rule_dt(points, cells, E, nu, rho, gamma=0.9) -> float:
 
 
 def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5,
-                 gamma=0.9, device=0):
+                 gamma=0.9, device=0, epart=None):
     """What ``drivers dynamics`` computes: the operator of ``cells`` (4 columns: order 1, 10: order 2) clamped on
     ``dirichlet_nodes``, its lumped mass, the reference load ``(0, -fz, -fz)`` ramped over ``t < 1``, ``dt = gamma *
     2/omega_max`` and ``n_steps`` steps recorded every ``save_every``.  Returns ``(trajectory (n_dof, n_cols) array,
-    report dict)``."""
+    report dict)``.  ``epart`` (element -> part): the same run through :class:`OperatorPartition`, every rank recording
+    its own nodes; the report gains ``parts``, ``n_global_shared`` and ``shared_per_rank``."""
     import torch
 
     from . import fem_setup as fs
@@ -127,6 +353,8 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
 
     points = np.ascontiguousarray(points, dtype=np.float64)
     cells = np.ascontiguousarray(cells, dtype=np.int32)
+    if epart is not None:
+        return _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device)
     lmd, mu = fs.lame(E, nu)
     with ModalOperator(points, cells, fs.node_to_dof(dirichlet_nodes), lmd, mu, rho, device) as op:
         mass = op.lumped_mass()
@@ -145,5 +373,37 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
                   "n_free_dofs": int(op.free.sum().item()), "dt": ts["dt"], "dt_crit": ts["dt_crit"],
                   "dt_reference_rule": rule, "ratio": rule / ts["dt_crit"], "omega_max": ts["omega_max"], "steps": int(n_steps),
                   "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean())}
+    torch.cuda.synchronize(device)
+    return store, report
+
+
+def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device):
+    import torch
+
+    from . import fem_setup as fs
+    from .modal import ModalOperator
+
+    n_cols = int(n_steps / save_every)
+    with OperatorPartition(points, cells, dirichlet_nodes, epart, None, E, nu, rho, fz, alpha, gamma, True, device) as part:
+        trajs = [r.stepper.record(n_cols, save_every) if n_cols > 0 else None for r in part.ranks]
+        part.step_synced(n_steps)
+        d = part.gather("d0").cpu().numpy().reshape(-1, 3)
+        tn = part.tn
+        store = np.zeros((part.n_dof, n_cols))
+        for r, traj in reversed(list(zip(part.ranks, trajs))):
+            if traj is not None:
+                store[r.global_dof.cpu().numpy()] = traj.cpu().numpy()
+        ts, order = part.time_step, part.order
+        shared = [len(r.layout.shared_local) for r in part.ranks]
+        n_global_shared, parts = len(part.global_shared), part.n_parts
+    with ModalOperator(points, cells, fs.node_to_dof(dirichlet_nodes), *fs.lame(E, nu), rho, device) as op:
+        n_free = int(op.free.sum().item())
+    n_vert = int(cells[:, :4].max()) + 1 if len(cells) else 0
+    tip = np.nonzero(np.abs(points[:n_vert, 0] - points[:, 0].max()) < 1e-9)[0]
+    rule = reference_rule_dt(points, cells, E, nu, rho, gamma)
+    report = {"order": order, "n_nodes": len(points), "n_elems": len(cells), "n_free_dofs": n_free, "dt": ts["dt"],
+              "dt_crit": ts["dt_crit"], "dt_reference_rule": rule, "ratio": rule / ts["dt_crit"], "omega_max": ts["omega_max"],
+              "steps": int(n_steps), "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean()),
+              "parts": parts, "n_global_shared": n_global_shared, "shared_per_rank": shared}
     torch.cuda.synchronize(device)
     return store, report
