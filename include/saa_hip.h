@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration; so did the partition entry points of the operator stepper, saa_operator_stepper_set_shared, _set_interface_buffer, _step_begin, _step_finish, _step_predicted, _halo_gather and _halo_scatter). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration; so did the partition entry points of the operator stepper, saa_operator_stepper_set_shared, _set_interface_buffer, _step_begin, _step_finish, _step_predicted, _halo_gather and _halo_scatter, and then saa_operator_stepper_set_energy). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -512,7 +512,8 @@ int saa_operator_stepper_destroy(saa_operator_stepper *st);
  *   3*n_shared doubles in that order (loc_dof_shared).  SAA_E_ARG on ids or slots out of range or repeated, or
  *   n_shared > n_global_shared.  n_shared = 0 clears the rank's shared set (with n_global_shared > 0 every slot is foreign).
  *   Builds on the device the map node -> k (-1 for a node that is not shared), the lists of nodes and slots, and the list
- *   of foreign slots: those of Global_shared that this rank does not hold.
+ *   of foreign slots: those of Global_shared that this rank does not hold.  Switches the energy balance off
+ *   (saa_operator_stepper_set_energy, below): call that after this.
  * saa_operator_stepper_set_interface_buffer: 3*n_global_shared doubles, caller-owned, zero when handed over.
  * saa_operator_stepper_step_begin: the K element pass for d0 (the variant "stored_geometry" selects) and one node pass.  A
  *   node that is not shared is updated and recorded as saa_operator_stepper_step does it.  A shared node's contributions,
@@ -542,6 +543,49 @@ int saa_operator_stepper_step_predicted(saa_operator_stepper *st, int32_t nsteps
                                         double *hist_dev, int64_t hist_row0);
 int saa_operator_stepper_halo_gather(saa_operator_stepper *st, double *row_dev);
 int saa_operator_stepper_halo_scatter(saa_operator_stepper *st, const double *row_dev);
+
+/*
+ * The energy balance of the operator stepper: what says whether a run is healthy.  Write d1 = d^(n+1), d0 = d^n, dn = d^(n-1),
+ * s = K d0 (the internal force, which the node pass holds in registers and never writes) and lambda_n = ramp ? min(t_n, 1) : 1.
+ * The update of saa_operator_stepper_step is  m (d1 - 2 d0 + dn)/dt^2 + alpha m (d1 - dn)/(2 dt) + s = lambda_n f.  Multiplied
+ * by (d1 - dn)/2 and summed over the dofs it gives, with the symmetry of K and exactly in the discrete sense,
+ *     (T + U)_{n+1/2} - (T + U)_{n-1/2} = dW_n - dD_n,   where
+ *     T_{n+1/2} = 1/2 sum_i m_i ((d1_i - d0_i)/dt)^2          kinetic energy of the half step
+ *     U_{n+1/2} = 1/2 sum_i d1_i s_i                          strain energy in cross form, 1/2 d^(n+1) . K d^n
+ *     U_n       = 1/2 sum_i d0_i s_i                          strain energy at t_n
+ *     dW_n      = lambda_n sum_i f_i (d1_i - dn_i)/2          work of the ramped load
+ *     dD_n      = alpha/(4 dt) sum_i m_i (d1_i - dn_i)^2      loss to the mass-proportional damping
+ * so that with the running sums W_{n+1} = sum_{j<=n} dW_j and D_{n+1} = sum_{j<=n} dD_j
+ *     B_n = T_{n+1/2} + U_{n+1/2} - W_{n+1} + D_{n+1}
+ * is constant to round-off over whole-mesh and synchronised steps from the step at which recording began.  B measures the
+ * CONSISTENCY of the run, not its stability: above the stability limit T + U grows without bound while B stays constant,
+ * so watch both.  In a predicted window the shared dofs are overwritten and the drift of B is the work done through the
+ * interface - the energy the predictor injects -, an error figure that needs no synchronised run to compare with.
+ * A Dirichlet dof and a node without elements contribute 0 to every sum.
+ *
+ * saa_operator_stepper_set_energy: energy_dev is a row-major (n_rows, 5) device buffer with the columns T_{n+1/2}, U_{n+1/2},
+ *   U_n, W_{n+1}, D_{n+1}; by the recorder's rule the step with energy step index i (next_step_index at this call, + 1 per
+ *   step, a counter of its own) writes row i / every when i % every == 0 and that row exists.  W and D are summed on the
+ *   device over EVERY step since this call, which zeroes them.  energy_dev = NULL switches the balance off.  While it is on,
+ *   step, step_begin / step_finish and step_predicted launch energy variants of the node and finish passes - the same
+ *   update by the same device function, the state bit-equal to a run with the balance off - which reduce the five sums per
+ *   block, and one more one-block launch per step that sums the blocks' partials in a fixed order.  No floating-point
+ *   atomics: every figure is bitwise repeatable and independent of how a run is split into calls.  While it is off exactly
+ *   the kernels of a stepper that never had it are launched.
+ *   One rank of a partition records its SHARE: the rows of all ranks add up to the row of the whole mesh.  The terms with m
+ *   or f (T, dW, dD) carry the global mass and load, which every holder of a shared node has in full, so a shared node
+ *   counts only on the rank with shared_owned_host[k] != 0 (n_shared host bytes in the order of shared_local_host; NULL:
+ *   all owned; give every shared node to exactly one of its holders, e.g. the lowest).  U_n is formed on every holder from
+ *   its partial s, and the partial s add up.  U_{n+1/2} of a shared node is formed in a synchronised step by the owner from
+ *   the summed s of the interface buffer, in a predicted step by every holder from its partial s and the d1 of its own
+ *   table.  saa_operator_stepper_step on a stepper with a shared set counts every node of the rank as owned.
+ *   SAA_E_ARG, before the handle or the device is looked at: n_rows < 0, every < 1, next_step_index < 0; then a null handle.
+ *   SAA_E_STATE: between step_begin and step_finish; with the "passes" option at 1 or 2 (and that option is refused while
+ *   the balance is on).  Synchronises the stream.  saa_operator_stepper_set_shared switches the balance OFF, because the
+ *   ownership flags and the partial sums are sized by the shared set: call set_energy after it.
+ */
+int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev, int64_t n_rows, int32_t every,
+                                    int64_t next_step_index, const uint8_t *shared_owned_host);
 
 /*
  * Shared-node predictor: the per-rank LSTM encoder-decoder of Tools/DNN_tools.py:16-98 (2-layer bidirectional encoder of

@@ -2276,6 +2276,8 @@ int saa_operator_stepper_set_recorder(saa_operator_stepper *st, double *traj_dev
 int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *name, double value) {
   if (!st || !st->impl || !name) return fail(SAA_E_ARG, "saa_operator_stepper_set_option: null handle or name");
   if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_option: a synchronised step is in flight");
+  if (saa::opstep_energy_on(st->impl) && std::strcmp(name, "passes") == 0 && value != 3.0)
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_option: passes 1 / 2 while the energy balance is recorded");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   hipError_t e = hipSuccess;
   if (!saa::opstep_set_option(st->impl, name, value, &e))
@@ -2372,6 +2374,22 @@ int saa_operator_stepper_halo_scatter(saa_operator_stepper *st, const double *ro
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   const hipError_t e = saa::opstep_halo(st->impl, const_cast<double *>(row_dev), false);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_halo_scatter: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev, int64_t n_rows, int32_t every,
+                                    int64_t next_step_index, const uint8_t *shared_owned_host) {
+  if (n_rows < 0) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: n_rows < 0");
+  if (every < 1) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: every < 1");
+  if (next_step_index < 0) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: next_step_index < 0");
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: null handle");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: a synchronised step is in flight");
+  if (energy_dev && saa::opstep_passes(st->impl) != 3)
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: the passes option is 1 or 2 (a measurement aid that does not advance the state)");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_set_energy(st->impl, energy_dev, energy_dev ? n_rows : 0, energy_dev ? every : 1,
+                                              energy_dev ? next_step_index : 0, shared_owned_host);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_energy: ") + hipGetErrorString(e));
   return SAA_OK;
 }
 

@@ -28,6 +28,7 @@
 
 #include "saa_modal_op.h"
 #include "saa_opstep.h"
+#include "saa_opstep_impl.h"
 #include "saa_p2.h"
 #include "saa_p2_elem.h"
 
@@ -247,14 +248,8 @@ __global__ void __launch_bounds__(kThreads) opstep_node_update_kernel(
 }
 
 // ---- a partition of the mesh: shared nodes (saa_operator_stepper_set_shared) ---------------------------------------------
-// The update of one dof, Dynamic_solver.py:13-20: the text of opstep_node_update_kernel's loop body, shared by every kernel
-// below so that a shared node is rounded by the finish kernel exactly as the node pass would have rounded it.
-__device__ __forceinline__ double opstep_update_dof(bool live, double s, double fi, double m, double x0, double xn, double dt,
-                                                    double alpha, double scale) {
-  const double num = dt * dt * (scale * fi - s) + 2.0 * m * x0 - m * xn + 0.5 * dt * m * alpha * xn;
-  const double den = m + alpha * m * 0.5 * dt;
-  return live ? num / den : 0.0;
-}
+// The update of one dof is opstep_update_dof (saa_opstep_impl.h): the text of opstep_node_update_kernel's loop body, shared
+// by every kernel below so that a shared node is rounded by the finish kernel exactly as the node pass would have rounded it.
 
 // The node pass of a partition, one lane per node.  A node that is not shared (shared_of[v] < 0) is updated as by
 // opstep_node_update_kernel.  A shared node, k = shared_of[v] its place in the rank's shared list:
@@ -354,28 +349,6 @@ __global__ void __launch_bounds__(kThreads) opstep_halo_kernel(int32_t n_shared,
     if (e_ != hipSuccess) return e_; \
   } while (0)
 
-struct OpStepper {
-  ModalOp *op = nullptr;  // borrowed: must outlive the stepper
-  double *mass = nullptr, *f = nullptr;
-  double *buf[2] = {nullptr, nullptr};  // buf[cur] = d0, buf[1 - cur] = dn
-  int cur = 0;
-  double *geom = nullptr;               // order 2, stored geometry: [40][n_elems]
-  uint32_t *bits = nullptr;             // n_elems
-  bool stored = false;
-  int passes = 3;                       // measurement aid: 1 = element pass only, 2 = node pass only (state not advanced)
-  double dt = 0.0, alpha = 0.0, tn = 0.0;
-  int ramp = 1;
-  double *traj = nullptr;
-  int64_t n_cols = 0, step_index = 0;
-  int32_t save_every = 1;
-  // the partition: shared_of[v] = k for the rank's k-th shared node (else -1), node[k], slot[k] its place in Global_shared,
-  // foreign[] the slots of Global_shared this rank does not hold
-  int32_t n_shared = 0, n_foreign = 0, n_global_shared = 0;
-  int32_t *shared_of = nullptr, *node = nullptr, *slot = nullptr, *foreign = nullptr;
-  double *iface = nullptr;  // caller-owned, 3 * n_global_shared
-  bool pending = false;     // between step_begin and step_finish
-};
-
 namespace {
 
 dim3 grid_for(int64_t n) { return dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)); }
@@ -432,6 +405,7 @@ hipError_t operator_lumped_mass(ModalOp *op, double *mass) {
 void opstep_destroy(OpStepper *st) {
   if (!st) return;
   (void)hipSetDevice(st->op->device);
+  openergy_clear(st);
   void *bufs[] = {st->mass, st->f, st->buf[0], st->buf[1], st->geom, st->bits, st->shared_of, st->node, st->slot, st->foreign};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
@@ -528,6 +502,7 @@ bool opstep_set_option(OpStepper *st, const char *name, double value, hipError_t
 hipError_t opstep_step(OpStepper *st, int32_t nsteps) {
   ModalOp *op = st->op;
   if (nsteps <= 0) return hipSuccess;
+  if (st->energy) return openergy_step(st, nsteps);
   double *contrib = nullptr;
   OPSTEP_TRY(operator_scratch(op, 1, &contrib));
   for (int32_t k = 0; k < nsteps; ++k) {
@@ -546,6 +521,7 @@ hipError_t opstep_step(OpStepper *st, int32_t nsteps) {
     st->cur = 1 - st->cur;
     st->tn += st->dt;
     ++st->step_index;
+    ++st->energy_index;
   }
   return hipSuccess;
 }
@@ -564,6 +540,7 @@ void advance(OpStepper *st) {
   st->cur = 1 - st->cur;
   st->tn += st->dt;
   ++st->step_index;
+  ++st->energy_index;
 }
 
 // shared_of of a stepper without a shared set: all -1, built on first need
@@ -575,6 +552,11 @@ hipError_t ensure_shared_map(OpStepper *st) {
 }
 
 }  // namespace
+
+hipError_t opstep_element_pass(OpStepper *st, const double *x, double *contrib) { return element_pass(st, x, contrib); }
+int64_t opstep_recorder_column(const OpStepper *st) { return recorder_column(st); }
+hipError_t opstep_ensure_shared_map(OpStepper *st) { return ensure_shared_map(st); }
+void opstep_advance(OpStepper *st) { advance(st); }
 
 bool opstep_pending(const OpStepper *st) { return st->pending; }
 int32_t opstep_n_shared(const OpStepper *st) { return st->n_shared; }
@@ -605,6 +587,7 @@ hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *sha
     if (!held[s]) foreign.push_back(s);
   // the old lists may still be read by work in flight
   OPSTEP_TRY(hipStreamSynchronize(op->stream));
+  openergy_clear(st);  // its ownership flags and partial sums are sized by the old lists
   void *old[] = {st->shared_of, st->node, st->slot, st->foreign};
   for (void *b : old)
     if (b) (void)hipFree(b);
@@ -630,6 +613,7 @@ hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *sha
 
 hipError_t opstep_step_begin(OpStepper *st) {
   ModalOp *op = st->op;
+  if (st->energy) return openergy_step_begin(st);
   double *contrib = nullptr;
   OPSTEP_TRY(operator_scratch(op, 1, &contrib));
   OPSTEP_TRY(ensure_shared_map(st));
@@ -645,6 +629,7 @@ hipError_t opstep_step_begin(OpStepper *st) {
 
 hipError_t opstep_step_finish(OpStepper *st, double *hist, int64_t hist_row) {
   ModalOp *op = st->op;
+  if (st->energy) return openergy_step_finish(st, hist, hist_row);
   const int64_t lanes = 3 * (static_cast<int64_t>(st->n_shared) + st->n_foreign);
   if (lanes > 0) {
     double *row = hist ? hist + hist_row * 3 * static_cast<int64_t>(st->n_shared) : nullptr;
@@ -663,6 +648,7 @@ hipError_t opstep_step_predicted(OpStepper *st, int32_t nsteps, const double *ta
                                  int64_t hist_row0) {
   ModalOp *op = st->op;
   if (nsteps <= 0) return hipSuccess;
+  if (st->energy) return openergy_step_predicted(st, nsteps, table, table_row0, hist, hist_row0);
   double *contrib = nullptr;
   OPSTEP_TRY(operator_scratch(op, 1, &contrib));
   OPSTEP_TRY(ensure_shared_map(st));

@@ -38,6 +38,7 @@ PATHS = dict(local_nodes="Results/Rankwised_Data/Rank={r}_local_nodes.csv",
              elements="Results/Rankwised_Element/Rank={r}_elements.csv",
              truth="Results/Dynamics/Local-rank-{r}.hdf5",
              dynamics="Results/Dynamics/Displacement_order{p}.hdf5",
+             energy="Results/Dynamics/Energy_order{p}.hdf5",
              modeled="Results/Dynamics/Modeled_Local-rank-{r}.hdf5",
              shared_traj="Results/sol_on_shared/rank={r}-shared_dof.hdf5",
              model="Distributed_save/Rank-{r}/nB-{nB}-nH-{nH}-Lr-{lr}-filter={ns}/model.pth",
@@ -258,14 +259,16 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
 
 
 def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1, E=None, nu=None, rho=None, fz=None,
-             alpha=None, gamma=None, parts=0, partition="slab"):
+             alpha=None, gamma=None, parts=0, partition="slab", energy_every=0):
     """The explicit run of the whole mesh on one GPU through the operator handle (:func:`dynamics.run_dynamics`), for
     linear (``order=1``) or quadratic tetrahedra (``order=2``: the mesh is elevated like ``steady_state --order 2``),
     clamped on every node of ``x = 0``: lumped mass of the handle (HRZ for order 2), the reference load ``(0, -fz, -fz)``
     with the ramp, ``alpha`` of ``Data_prepare.py:41`` and ``dt = gamma * 2/omega_max``.  Writes
     ``Results/Dynamics/Displacement_order{p}.hdf5`` and returns ``(path, report)``.  ``parts = P > 0``: the same run on
     the mesh cut into ``P`` parts (``partition``: slab, graph or rcb, on the vertex tetrahedra), every synchronised step
-    split around the sum of the shared-node forces (:class:`dynamics.OperatorPartition`); same file."""
+    split around the sum of the shared-node forces (:class:`dynamics.OperatorPartition`); same file.  ``energy_every = S >
+    0``: the energy balance of every ``S``-th step (``T, U_{n+1/2}, U_n, W, D``, ``include/saa_hip.h``) goes to dataset
+    ``Energy`` of ``Results/Dynamics/Energy_order{p}.hdf5``, and the report gains ``energy`` and ``energy_path``."""
     from .dynamics import run_dynamics
     from .mesh import plane_nodes
 
@@ -277,8 +280,12 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
         mesh = _quadratic(mesh)
     cells = mesh.tets10 if order == 2 else mesh.tets
     epart = make_partition(mesh, int(parts), partition) if parts and int(parts) > 0 else None
-    store, report = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device, epart=epart, **p)
+    store, report, *table = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device,
+                                         epart=epart, energy_every=int(energy_every or 0), **p)
     path = rio.save_displacement(os.path.join(out_dir, PATHS["dynamics"].format(p=order)), store)
+    if table:
+        report["energy_path"] = rio.save_displacement(os.path.join(out_dir, PATHS["energy"].format(p=order)), table[0],
+                                                      dataset=rio.ENERGY_DATASET)
     return path, report
 
 
@@ -774,6 +781,9 @@ def main(argv=None):
     ap.add_argument("--partition", choices=["slab", "graph", "rcb"], default="slab")
     ap.add_argument("--parts", type=int, default=0,
                     help="dynamics: cut the mesh into this many parts and run them as ranks of a partition on one GPU")
+    ap.add_argument("--energy", action="store_true",
+                    help="dynamics: record the energy balance (kinetic, strain, work, damping loss) and store the table")
+    ap.add_argument("--energy-every", type=int, default=1, help="dynamics --energy: every so many steps")
     ap.add_argument("--n-past", type=int, default=20)
     ap.add_argument("--n-future", type=int, default=20)
     ap.add_argument("--filter-size", type=int, default=150)
@@ -809,7 +819,8 @@ def main(argv=None):
             print(json.dumps(modal(mesh, k=args.k, device=local, order=args.order)))
         elif args.command == "dynamics":
             path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order,
-                                    parts=args.parts, partition=args.partition)
+                                    parts=args.parts, partition=args.partition,
+                                    energy_every=max(args.energy_every, 1) if args.energy else 0)
             print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]

@@ -12,7 +12,12 @@ kernel is a second oracle for it.
 
 The partitioned loop the project is named after runs on the same stepper: :class:`OperatorRank` is one rank of a partition
 of a replicated mesh of either order (synchronised steps split around a reduction of the shared-node forces, predicted
-steps with the shared-dof overwrite), :class:`OperatorPartition` all ranks in one process on one GPU."""
+steps with the shared-dof overwrite), :class:`OperatorPartition` all ranks in one process on one GPU.
+
+``record_energy`` on any of the three switches the energy balance on (``saa_operator_stepper_set_energy``): per step the
+kinetic energy ``T`` of the half step, the strain energy in cross form ``U`` and at ``t_n``, the work ``W`` of the load and
+the damping loss ``D``.  :func:`energy_balance` turns the rows into ``B_n - B_0``, which stays at round-off over whole-mesh
+and synchronised steps and in a predicted window drifts by the energy the predictor injects through the interface."""
 from __future__ import annotations
 
 import ctypes as C
@@ -36,6 +41,7 @@ class OperatorStepper:
         self.dt = float(dt)
         self._traj = None
         self._iface = None
+        self._energy = None
         self.n_shared = self.n_global_shared = 0
         m, f = self._vector(mass), self._vector(load)
         _lib.check(self._lib.saa_operator_stepper_create(op._h, _dev(m), _dev(f), float(dt), float(alpha), 1 if ramp else 0,
@@ -55,6 +61,7 @@ class OperatorStepper:
             self._lib.saa_operator_stepper_destroy(self._h)
             self._h = C.c_void_p()
         self._traj = None
+        self._energy = None
 
     def __del__(self):
         try:
@@ -107,6 +114,31 @@ class OperatorStepper:
         self._traj = out
         return out.reshape(-1)[: self.n_dof * int(n_cols)].view(self.n_dof, int(n_cols))
 
+    def record_energy(self, n_rows, every=1, next_step_index=0, owned=None):
+        """Switches the energy balance on and returns its ``(n_rows, 5)`` CUDA matrix of zeros, columns ``T_{n+1/2},
+        U_{n+1/2}, U_n, W, D`` (``include/saa_hip.h`` has the definitions and the identity): the step with energy step
+        index ``i`` fills row ``i / every`` when ``i % every == 0`` and the row exists; ``W`` and ``D`` run over every step
+        from this call on.  ``owned``: one flag per shared node of :meth:`set_shared` - this rank counts the node's mass
+        and load terms (None: all).  ``n_rows = 0`` switches it off.  :meth:`set_shared` switches it off too: call this
+        after it."""
+        import torch
+
+        if not n_rows:
+            _lib.check(self._lib.saa_operator_stepper_set_energy(self._h, None, 0, 1, 0, None))
+            self._energy = None
+            return None
+        flags = None
+        if owned is not None:
+            flags = np.ascontiguousarray(np.asarray(owned).reshape(-1) != 0, dtype=np.uint8)
+            if flags.size != self.n_shared:
+                raise ValueError(f"owned must hold {self.n_shared} flags, got {flags.size}")
+        rows = max(int(n_rows), 0)
+        out = torch.zeros((rows, 5), dtype=torch.float64, device=self.op.torch_device)
+        _lib.check(self._lib.saa_operator_stepper_set_energy(self._h, _dev(out), int(n_rows), int(every), int(next_step_index),
+                                                             flags.ctypes.data if flags is not None and flags.size else None))
+        self._energy = out
+        return out
+
     def set_option(self, name: str, value: float):
         """``stored_geometry`` 0 / 1: the order-2 element pass recomputes its Jacobians / reads them from a table."""
         _lib.check(self._lib.saa_operator_stepper_set_option(self._h, name.encode(), float(value)))
@@ -123,6 +155,7 @@ class OperatorStepper:
         _lib.check(self._lib.saa_operator_stepper_set_shared(self._h, int(a.size), a.ctypes.data_as(ip) if a.size else None,
                                                              b.ctypes.data_as(ip) if b.size else None, int(n_global_shared)))
         self.n_shared, self.n_global_shared = int(a.size), int(n_global_shared)
+        self._energy = None
 
     def set_interface_buffer(self, iface):
         """``iface``: float64 CUDA tensor of ``3 * n_global_shared`` zeros, kept alive here; ``None`` takes it away."""
@@ -157,6 +190,23 @@ class OperatorStepper:
         _lib.check(self._lib.saa_operator_stepper_halo_scatter(self._h, _dev(row)))
 
 
+def energy_balance(rows):
+    """``B_n - B_0`` of ``(n, 5)`` energy rows ``T, U_{n+1/2}, U_n, W, D``, ``B = T + U_{n+1/2} - W + D``: round-off over
+    whole-mesh and synchronised steps; in a predicted window the energy injected through the interface.  NumPy array or
+    tensor in, the same out."""
+    b = rows[:, 0] + rows[:, 1] - rows[:, 3] + rows[:, 4]
+    return b - b[0] if len(b) else b
+
+
+def shared_ownership(layouts, n_global_shared):
+    """Per rank, one flag per entry of its ``shared_local``: the rank is the lowest holder of that shared node."""
+    owner = np.full(int(n_global_shared), len(layouts), dtype=np.int64)
+    for lay in layouts:
+        slots = np.asarray(lay.shared_slots, dtype=np.int64)
+        owner[slots] = np.minimum(owner[slots], int(lay.rank))
+    return [owner[np.asarray(lay.shared_slots, dtype=np.int64)] == int(lay.rank) for lay in layouts]
+
+
 class OperatorRank:
     """One rank of a partition of a replicated mesh of either order (``Data_prepare.py:104-209`` for one rank): its
     :class:`fem_setup.RankLayout` (from ``build_layouts`` on the 4- or 10-column cells), a :class:`modal.ModalOperator` on
@@ -166,10 +216,14 @@ class OperatorRank:
     does (``Data_prepare.py:175-202``), so a shared node carries the other ranks' contributions too.  ``reduce(iface)``
     sums the interface buffer over the ranks in place between the two halves of a synchronised step:
     ``torch.distributed.all_reduce`` makes this a rank of a multi-process run; ``None`` is a world of one.  The object
-    presents what :func:`distributed.run_hybrid` uses."""
+    presents what :func:`distributed.run_hybrid` uses.
+
+    ``layouts`` (all ranks', as ``build_layouts`` returns them) settles which shared nodes this rank owns for the energy
+    balance: those of which it is the lowest holder.  Without it :meth:`record_energy` counts every shared node as owned,
+    which is right for a world of one only."""
 
     def __init__(self, points, layout, global_shared, mass, load, lmd, mu, rho, dt, alpha, reduce=None, ramp=True, device=0,
-                 stored_geometry=None):
+                 stored_geometry=None, layouts=None):
         import torch
 
         from .modal import ModalOperator
@@ -193,6 +247,8 @@ class OperatorRank:
         self.iface = torch.zeros(3 * self.n_global_shared, dtype=torch.float64, device=self.tensor_device)
         self.stepper.set_interface_buffer(self.iface)
         self.input_size = 3 * len(layout.shared_local)              # Online_predictor.py:126
+        self.owned = None if layouts is None else shared_ownership(layouts, self.n_global_shared)[
+            [int(lay.rank) for lay in layouts].index(self.rank)]
         self.dt = float(dt)
         self.steps_done = 0
 
@@ -216,6 +272,11 @@ class OperatorRank:
 
     def get_state(self):
         return self.stepper.state()
+
+    def record_energy(self, n_rows, every=1, next_step_index=0):
+        """This rank's share of the energy rows (:meth:`OperatorStepper.record_energy` with the rank's ownership flags):
+        the shares of all ranks add up to the rows of the whole mesh."""
+        return self.stepper.record_energy(n_rows, every, next_step_index, self.owned)
 
     def close(self):
         self.stepper.close()
@@ -266,7 +327,8 @@ class OperatorPartition:
         self.dt = self.time_step["dt"]
         layouts, self.global_shared = fs.build_layouts(cells, epart, self.n_parts, len(points), dirichlet_nodes)
         self.ranks = [OperatorRank(points, lay, self.global_shared, mass, load, lmd, mu, rho, self.dt, alpha, None, ramp, device,
-                                   stored_geometry) for lay in layouts]
+                                   stored_geometry, layouts) for lay in layouts]
+        self._energy = None
         self._sum = torch.zeros(3 * len(self.global_shared), dtype=torch.float64, device=self.tensor_device)
 
     def reduce_in_rank_order(self):
@@ -305,6 +367,22 @@ class OperatorPartition:
             i += todo
         return hists
 
+    def record_energy(self, n_rows, every=1, next_step_index=0):
+        """Switches the energy balance on on every rank; returns the per-rank ``(n_rows, 5)`` tensors (each rank's share)."""
+        self._energy = [r.record_energy(n_rows, every, next_step_index) for r in self.ranks]
+        if not n_rows:
+            self._energy = None
+        return self._energy
+
+    def energy(self):
+        """The sum of the ranks' energy rows in rank order, a new ``(n_rows, 5)`` tensor: the rows of the whole mesh."""
+        if self._energy is None:
+            raise RuntimeError("record_energy has not been called")
+        total = self._energy[0].clone()
+        for e in self._energy[1:]:
+            total += e
+        return total
+
     def gather(self, which="d0"):
         """The global ``(3 n,)`` CUDA vector of ``d0`` or ``dn``; a shared node comes from its lowest holder."""
         import torch
@@ -339,13 +417,27 @@ def reference_rule_dt(points, cells, E, nu, rho, gamma=0.9) -> float:
     return float(fs.cfl_dt(np.asarray(points, dtype=np.float64), np.asarray(cells)[:, :4], E, nu, rho, gamma))
 
 
+def energy_report(rows):
+    """What ``drivers dynamics --energy`` prints of ``(n, 5)`` energy rows (NumPy): the last ``T, U (cross form), W, D``,
+    the largest ``|B_n - B_0|`` and the scale it is relative to, ``max_n(W_n, (T + U)_n)``."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 5)
+    if not len(rows):
+        return {"rows": 0}
+    last = rows[-1]
+    return {"rows": len(rows), "T": float(last[0]), "U": float(last[1]), "W": float(last[3]), "D": float(last[4]),
+            "max_abs_balance": float(np.abs(energy_balance(rows)).max()),
+            "scale": float(max(rows[:, 3].max(), (rows[:, 0] + rows[:, 1]).max()))}
+
+
 def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5,
-                 gamma=0.9, device=0, epart=None):
+                 gamma=0.9, device=0, epart=None, energy_every=0):
     """What ``drivers dynamics`` computes: the operator of ``cells`` (4 columns: order 1, 10: order 2) clamped on
     ``dirichlet_nodes``, its lumped mass, the reference load ``(0, -fz, -fz)`` ramped over ``t < 1``, ``dt = gamma *
     2/omega_max`` and ``n_steps`` steps recorded every ``save_every``.  Returns ``(trajectory (n_dof, n_cols) array,
     report dict)``.  ``epart`` (element -> part): the same run through :class:`OperatorPartition`, every rank recording
-    its own nodes; the report gains ``parts``, ``n_global_shared`` and ``shared_per_rank``."""
+    its own nodes; the report gains ``parts``, ``n_global_shared`` and ``shared_per_rank``.  ``energy_every = S > 0``: the
+    energy balance is recorded every ``S`` steps, the report gains ``energy`` (:func:`energy_report`) and the return value
+    a third member, the ``(ceil(n_steps / S), 5)`` table (of a partition: the sum of the ranks' shares)."""
     import torch
 
     from . import fem_setup as fs
@@ -354,7 +446,9 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
     points = np.ascontiguousarray(points, dtype=np.float64)
     cells = np.ascontiguousarray(cells, dtype=np.int32)
     if epart is not None:
-        return _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device)
+        return _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device,
+                                   energy_every)
+    n_rows = -(-int(n_steps) // int(energy_every)) if energy_every else 0
     lmd, mu = fs.lame(E, nu)
     with ModalOperator(points, cells, fs.node_to_dof(dirichlet_nodes), lmd, mu, rho, device) as op:
         mass = op.lumped_mass()
@@ -362,9 +456,11 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
         n_cols = int(n_steps / save_every)
         with OperatorStepper(op, mass, op.load((0.0, -fz, -fz)), ts["dt"], alpha, ramp=True) as st:
             traj = st.record(n_cols, save_every) if n_cols > 0 else None
+            rows = st.record_energy(n_rows, energy_every) if n_rows > 0 else None
             st.step(n_steps)
             d0, _, tn = st.state()
             store = traj.cpu().numpy() if traj is not None else np.zeros((op.n_dof, 0))
+            table = rows.cpu().numpy() if rows is not None else np.zeros((0, 5))
         d = d0.cpu().numpy().reshape(-1, 3)
         n_vert = int(cells[:, :4].max()) + 1 if len(cells) else 0
         tip = np.nonzero(np.abs(points[:n_vert, 0] - points[:, 0].max()) < 1e-9)[0]
@@ -374,10 +470,14 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
                   "dt_reference_rule": rule, "ratio": rule / ts["dt_crit"], "omega_max": ts["omega_max"], "steps": int(n_steps),
                   "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean())}
     torch.cuda.synchronize(device)
+    if energy_every:
+        report["energy"] = energy_report(table)
+        return store, report, table
     return store, report
 
 
-def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device):
+def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device,
+                        energy_every=0):
     import torch
 
     from . import fem_setup as fs
@@ -386,7 +486,11 @@ def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_eve
     n_cols = int(n_steps / save_every)
     with OperatorPartition(points, cells, dirichlet_nodes, epart, None, E, nu, rho, fz, alpha, gamma, True, device) as part:
         trajs = [r.stepper.record(n_cols, save_every) if n_cols > 0 else None for r in part.ranks]
+        n_rows = -(-int(n_steps) // int(energy_every)) if energy_every else 0
+        if n_rows > 0:
+            part.record_energy(n_rows, energy_every)
         part.step_synced(n_steps)
+        table = part.energy().cpu().numpy() if n_rows > 0 else np.zeros((0, 5))
         d = part.gather("d0").cpu().numpy().reshape(-1, 3)
         tn = part.tn
         store = np.zeros((part.n_dof, n_cols))
@@ -406,4 +510,7 @@ def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_eve
               "steps": int(n_steps), "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean()),
               "parts": parts, "n_global_shared": n_global_shared, "shared_per_rank": shared}
     torch.cuda.synchronize(device)
+    if energy_every:
+        report["energy"] = energy_report(table)
+        return store, report, table
     return store, report

@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 DATASET = "Displacement"
+ENERGY_DATASET = "Energy"  # the (n_rows, 5) table of drivers dynamics --energy: T, U_{n+1/2}, U_n, W, D
 
 
 def _h5py():
@@ -23,37 +24,37 @@ def _h5py():
         return None
 
 
-def save_displacement(path_hdf5: str, data: np.ndarray, compress: bool = True) -> str:
-    """Write ``data`` under ``Displacement``; returns the path actually written."""
+def save_displacement(path_hdf5: str, data: np.ndarray, compress: bool = True, dataset: str = DATASET) -> str:
+    """Write ``data`` under ``Displacement`` (or ``dataset``); returns the path actually written."""
     os.makedirs(os.path.dirname(path_hdf5) or ".", exist_ok=True)
     h5 = _h5py()
     if h5 is not None:
         with h5.File(path_hdf5, "w") as f:
-            f.create_dataset(DATASET, data=data, compression="gzip" if compress else None)
+            f.create_dataset(dataset, data=data, compression="gzip" if compress else None)
         return path_hdf5
     from . import hdf5_c
 
     if hdf5_c.available():
-        return hdf5_c.write_dataset(path_hdf5, DATASET, data, gzip=compress)
+        return hdf5_c.write_dataset(path_hdf5, dataset, data, gzip=compress)
     alt = os.path.splitext(path_hdf5)[0] + ".npz"
-    (np.savez_compressed if compress else np.savez)(alt, **{DATASET: data})
+    (np.savez_compressed if compress else np.savez)(alt, **{dataset: data})
     return alt
 
 
-def load_displacement(path_hdf5: str) -> np.ndarray:
+def load_displacement(path_hdf5: str, dataset: str = DATASET) -> np.ndarray:
     h5 = _h5py()
     if os.path.exists(path_hdf5) and h5 is not None:
         with h5.File(path_hdf5, "r") as f:
-            return np.array(f[DATASET])
+            return np.array(f[dataset])
     if os.path.exists(path_hdf5):
         from . import hdf5_c
 
         if hdf5_c.available():
-            return hdf5_c.read_dataset(path_hdf5, DATASET)
+            return hdf5_c.read_dataset(path_hdf5, dataset)
     alt = os.path.splitext(path_hdf5)[0] + ".npz"
     if os.path.exists(alt):
         with np.load(alt, allow_pickle=False) as z:
-            return z[DATASET]
+            return z[dataset]
     raise FileNotFoundError(f"neither {path_hdf5} (needs h5py or libhdf5) nor {alt} exists")
 
 
