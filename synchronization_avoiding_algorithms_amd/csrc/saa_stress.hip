@@ -102,7 +102,8 @@ __global__ void __launch_bounds__(kThreads) stress_elem_kernel(int32_t n_elems, 
       const double ltr = lam * (eps[0] + eps[1] + eps[2]);
       const double s[6] = {ltr + 2.0 * mu * eps[0], ltr + 2.0 * mu * eps[1], ltr + 2.0 * mu * eps[2],
                            mu * eps[3],             mu * eps[4],             mu * eps[5]};
-      const double d01 = s[0] - s[1], d12 = s[1] - s[2], d20 = s[2] - s[0];
+      // the differences of the normal stresses from the strains: lambda tr(eps) drops out before it can round them
+      const double d01 = 2.0 * mu * (eps[0] - eps[1]), d12 = 2.0 * mu * (eps[1] - eps[2]), d20 = 2.0 * mu * (eps[2] - eps[0]);
       vm = sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20) + 3.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]));
       w = half_vol * (s[0] * eps[0] + s[1] * eps[1] + s[2] * eps[2] + s[3] * eps[3] + s[4] * eps[4] + s[5] * eps[5]);
       if (sigma) {
@@ -189,10 +190,15 @@ __device__ __forceinline__ void load6(const double *__restrict__ p, bool wide, d
   }
 }
 
-// t^T C t with C = D^-1 (commons.py:25-31, engineering shear): half_imu = 1 / (2 mu), ctr = lambda / (3 lambda + 2 mu)
-__device__ __forceinline__ double compliance_form(const double t[6], double half_imu, double ctr) {
+// t^T C t with C = D^-1 (commons.py:25-31, engineering shear), split as |dev t|^2 / (2 mu) + tr(t)^2 / (3 (3 lambda + 2 mu)):
+// half_imu = 1 / (2 mu), cvol = 1 / (3 (3 lambda + 2 mu)).  A sum of squares: the one-bracket form t.t - lambda / (3 lambda +
+// 2 mu) tr^2 cancels on a pressure-dominated t and loses lambda / mu times the rounding (4e-10 at nu = 0.499999).  The normal
+// part of |dev t|^2 is ((t0 - t1)^2 + (t1 - t2)^2 + (t2 - t0)^2) / 3.
+__device__ __forceinline__ double compliance_form(const double t[6], double half_imu, double cvol) {
   const double tr = t[0] + t[1] + t[2];
-  return half_imu * ((t[0] * t[0] + t[1] * t[1] + t[2] * t[2] - ctr * (tr * tr)) + 2.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5]));
+  const double d01 = t[0] - t[1], d12 = t[1] - t[2], d20 = t[2] - t[0];
+  return half_imu * ((1.0 / 3.0) * (d01 * d01 + d12 * d12 + d20 * d20) + 2.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5])) +
+         cvol * (tr * tr);
 }
 
 }  // namespace
@@ -204,7 +210,7 @@ __device__ __forceinline__ double compliance_form(const double t[6], double half
 // reads that do not stream; each is a 48-byte row.  Partials as in stress_elem_kernel (sum, max, lowest argmax).
 template <bool kNodal>
 __global__ void __launch_bounds__(kThreads) stress_error_kernel(int32_t n_elems, int32_t m, const int32_t *__restrict__ tets,
-                                                                const double *__restrict__ abs_vol, double half_imu, double ctr,
+                                                                const double *__restrict__ abs_vol, double half_imu, double cvol,
                                                                 const double *__restrict__ sigma, int64_t ld_sigma,
                                                                 const double *__restrict__ other, int64_t ld_other,
                                                                 bool wide_sigma, bool wide_other, double *__restrict__ eta2,
@@ -242,15 +248,15 @@ __global__ void __launch_bounds__(kThreads) stress_error_kernel(int32_t n_elems,
             d[c] -= se[c];
             s[c] += d[c];
           }
-          q += compliance_form(d, half_imu, ctr);
+          q += compliance_form(d, half_imu, cvol);
         }
-        q += compliance_form(s, half_imu, ctr);
+        q += compliance_form(s, half_imu, cvol);
       } else {
         double d[6];
         load6(oj + 6 * e, wide_other, d);
 #pragma unroll
         for (int c = 0; c < 6; ++c) d[c] -= se[c];
-        q = compliance_form(d, half_imu, ctr);
+        q = compliance_form(d, half_imu, cvol);
       }
       w = scale * q;
       best = w;
@@ -409,14 +415,14 @@ hipError_t stress_error(ModalOp *op, int32_t m, const double *sigma, int64_t ld_
   STRESS_TRY(stress_prepare(op));
   const int32_t n_parts = n_parts_of(op);
   if (n_parts > 0) {
-    const double half_imu = 0.5 / op->mu, ctr = op->lam / (3.0 * op->lam + 2.0 * op->mu);
+    const double half_imu = 0.5 / op->mu, cvol = 1.0 / (3.0 * (3.0 * op->lam + 2.0 * op->mu));
     const double *other = sigma_node ? sigma_node : sigma_other;
     const int64_t ldo = sigma_node ? ld_node : ld_other;
     const auto wide = [m](const double *p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (m == 1 || ld % 2 == 0); };
     double *pw = reduce ? op->st_part_w : nullptr;
 #define STRESS_ERROR(NODAL)                                                                                                    \
   hipLaunchKernelGGL(stress_error_kernel<NODAL>, dim3(static_cast<unsigned>(n_parts)), dim3(kThreads), 0, op->stream,          \
-                     op->n_elems, m, op->tets, op->abs_vol, half_imu, ctr, sigma, ld_sigma, other, ldo, wide(sigma, ld_sigma), \
+                     op->n_elems, m, op->tets, op->abs_vol, half_imu, cvol, sigma, ld_sigma, other, ldo, wide(sigma, ld_sigma), \
                      wide(other, ldo), eta2, ld_eta, pw, op->st_part_vm, op->st_part_idx)
     if (sigma_node)
       STRESS_ERROR(true);

@@ -19,9 +19,10 @@
 //    fourteen points of make_rule14 from the ten coordinates, which are then dropped; per column the components are the
 //    outer loop: ten nodal and four Gauss values give the ten nodal differences d_a = sigma*_a - sigma_h(node a), and
 //    d(xi_p) = sum_a N_a(xi_p) d_a (the quadratic interpolant reproduces the linear sigma_h) updates two accumulators per
-//    point, the weighted d:d and tr d, so the six components never live together at fourteen points.  Element form: the
+//    point, the deviatoric part of d:d and tr d, so the six components never live together at fourteen points.  Element form: the
 //    four w_q |detJ_q| and the difference of the two fields at the Gauss points.
-//    eta_e^2 = sum_p w_p |detJ_p| (1 / 2 mu) (d:d - lambda / (3 lambda + 2 mu) tr(d)^2).
+//    eta_e^2 = sum_p w_p |detJ_p| (|dev d|^2 / (2 mu) + tr(d)^2 / (3 (3 lambda + 2 mu))), the compliance form d^T C d split
+//    into two squares.
 //  * p2_stress_vol_kernel, p2_stress_node_weight_kernel - |V_e| = sum_q w_q |detJ_q| and its nodal sums, once per handle.
 //
 // Register note.  The element pass holds J^-1 (36 fp64), w |detJ| (4), the gradients (36) and ten node ids: 162 of the 256
@@ -131,10 +132,14 @@ __device__ __forceinline__ void store6(double *__restrict__ p, bool wide, const 
   }
 }
 
-// t^T C t with C = D^-1 (engineering shear): half_imu = 1 / (2 mu), ctr = lambda / (3 lambda + 2 mu)
-__device__ __forceinline__ double compliance_form(const double t[6], double half_imu, double ctr) {
+// t^T C t with C = D^-1 (engineering shear), split as |dev t|^2 / (2 mu) + tr(t)^2 / (3 (3 lambda + 2 mu)) as in saa_stress.hip
+// (a sum of squares; the one-bracket form cancels on a pressure-dominated t): half_imu = 1 / (2 mu), cvol = 1 / (3 (3 lambda +
+// 2 mu))
+__device__ __forceinline__ double compliance_form(const double t[6], double half_imu, double cvol) {
   const double tr = t[0] + t[1] + t[2];
-  return half_imu * ((t[0] * t[0] + t[1] * t[1] + t[2] * t[2] - ctr * (tr * tr)) + 2.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5]));
+  const double d01 = t[0] - t[1], d12 = t[1] - t[2], d20 = t[2] - t[0];
+  return half_imu * ((1.0 / 3.0) * (d01 * d01 + d12 * d12 + d20 * d20) + 2.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5])) +
+         cvol * (tr * tr);
 }
 
 // w_q |detJ_q| at the points of rule R from the element's ten coordinates
@@ -241,7 +246,8 @@ __global__ void __launch_bounds__(kThreads, 2) p2_stress_elem_kernel(int32_t n_e
       const double ltr = lam * (eps[0] + eps[1] + eps[2]);
       const double s[6] = {ltr + 2.0 * mu * eps[0], ltr + 2.0 * mu * eps[1], ltr + 2.0 * mu * eps[2],
                            mu * eps[3],             mu * eps[4],             mu * eps[5]};
-      const double d01 = s[0] - s[1], d12 = s[1] - s[2], d20 = s[2] - s[0];
+      // the differences of the normal stresses from the strains: lambda tr(eps) drops out before it can round them
+      const double d01 = 2.0 * mu * (eps[0] - eps[1]), d12 = 2.0 * mu * (eps[1] - eps[2]), d20 = 2.0 * mu * (eps[2] - eps[0]);
       const double vm = sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20) + 3.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]));
       w += hwd[q] * (s[0] * eps[0] + s[1] * eps[1] + s[2] * eps[2] + s[3] * eps[3] + s[4] * eps[4] + s[5] * eps[5]);
       if (valid) {
@@ -302,7 +308,7 @@ __global__ void __launch_bounds__(kThreads, 8) p2_stress_nodal_kernel(int32_t n_
 template <bool kNodal>
 __global__ void __launch_bounds__(kThreads, 2) p2_stress_error_kernel(int32_t n_elems, int32_t m, const double *__restrict__ xyz,
                                                                    const int32_t *__restrict__ cells, double half_imu,
-                                                                   double ctr, const double *__restrict__ sigma,
+                                                                   double cvol, const double *__restrict__ sigma,
                                                                    int64_t ld_sigma, const double *__restrict__ other,
                                                                    int64_t ld_other, bool wide, double *__restrict__ eta2,
                                                                    int64_t ld_eta, double *__restrict__ part_w,
@@ -336,8 +342,10 @@ __global__ void __launch_bounds__(kThreads, 2) p2_stress_error_kernel(int32_t n_
 #pragma unroll
       for (int c = 0; c < 6; ++c) {
         int co = c;  // (register note: one component's fourteen loads in flight, not six components')
-        if (c > 0)
+        if (c > 3)
           asm volatile("" : "+v"(co) : "v"(dd[13]));
+        else if (c > 0)
+          asm volatile("" : "+v"(co) : "v"(tr[13]));  // (components 0 to 2 end in tr, see below)
         else
           asm volatile("" : "+v"(co));
         const double g0 = sj[co], g1 = sj[6 + co], g2 = sj[12 + co], g3 = sj[18 + co];
@@ -356,12 +364,26 @@ __global__ void __launch_bounds__(kThreads, 2) p2_stress_error_kernel(int32_t n_
 #pragma unroll
           for (int a = 0; a < 10; ++a)
             if (R.N[p][a] != 0.0) dp += R.N[p][a] * d[a];
-          dd[p] += (c < 3 ? 1.0 : 2.0) * (dp * dp);
-          if (c < 3) tr[p] += dp;
+          // dd: 2 mu times the deviatoric density, tr: the sum of the normal components so far.  The three normal values
+          // x0, x1, x2 arrive one component at a time: sum_i (x_i - tr / 3)^2 = (x0 - x1)^2 / 2 + 2 / 3 (x2 - (x0 + x1) / 2)^2,
+          // each bracket a difference of neighbours, so that a common pressure drops out of dd before it is squared
+          if (c == 0) {
+            tr[p] = dp;
+          } else if (c == 1) {
+            const double d = tr[p] - dp;
+            dd[p] = 0.5 * (d * d);
+            tr[p] += dp;
+          } else if (c == 2) {
+            const double d = dp - 0.5 * tr[p];
+            dd[p] += (2.0 / 3.0) * (d * d);
+            tr[p] += dp;
+          } else {
+            dd[p] += 2.0 * (dp * dp);
+          }
         }
       }
 #pragma unroll
-      for (int p = 0; p < 14; ++p) w += wd[p] * (half_imu * (dd[p] - ctr * (tr[p] * tr[p])));
+      for (int p = 0; p < 14; ++p) w += wd[p] * (half_imu * dd[p] + cvol * (tr[p] * tr[p]));
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -370,7 +392,7 @@ __global__ void __launch_bounds__(kThreads, 2) p2_stress_error_kernel(int32_t n_
         load6(oj + 24 * ec + 6 * q, wide, d);
 #pragma unroll
         for (int c = 0; c < 6; ++c) d[c] -= s[c];
-        w += wd[q] * compliance_form(d, half_imu, ctr);
+        w += wd[q] * compliance_form(d, half_imu, cvol);
       }
     }
     double best = w;
@@ -454,15 +476,15 @@ hipError_t p2_stress_error(ModalOp *op, int32_t m, const double *sigma, int64_t 
   if (!reduce && !eta2) return hipSuccess;
   P2S_TRY(p2_stress_prepare(op));
   if (op->n_elems > 0) {
-    const double half_imu = 0.5 / op->mu, ctr = op->lam / (3.0 * op->lam + 2.0 * op->mu);
+    const double half_imu = 0.5 / op->mu, cvol = 1.0 / (3.0 * (3.0 * op->lam + 2.0 * op->mu));
     double *pw = reduce ? op->st_part_w : nullptr;
     if (sigma_node)
       hipLaunchKernelGGL(p2_stress_error_kernel<true>, elem_grid(op), dim3(kThreads), 0, op->stream, op->n_elems, m, op->xyz,
-                         op->tets, half_imu, ctr, sigma, ld_sigma, sigma_node, ld_node, false, eta2, ld_eta, pw, op->st_part_vm,
+                         op->tets, half_imu, cvol, sigma, ld_sigma, sigma_node, ld_node, false, eta2, ld_eta, pw, op->st_part_vm,
                          op->st_part_idx);
     else
       hipLaunchKernelGGL(p2_stress_error_kernel<false>, elem_grid(op), dim3(kThreads), 0, op->stream, op->n_elems, m, op->xyz,
-                         op->tets, half_imu, ctr, sigma, ld_sigma, sigma_other, ld_other,
+                         op->tets, half_imu, cvol, sigma, ld_sigma, sigma_other, ld_other,
                          wide_rows(sigma, ld_sigma, m) && wide_rows(sigma_other, ld_other, m), eta2, ld_eta, pw, op->st_part_vm,
                          op->st_part_idx);
     P2S_TRY(hipGetLastError());
