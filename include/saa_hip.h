@@ -588,6 +588,56 @@ int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev
                                     int64_t next_step_index, const uint8_t *shared_owned_host);
 
 /*
+ * Finite-strain hyperelastic materials on the operator handle, either element order (csrc/saa_opfs.hip).  Every other kernel
+ * of the handle is small-strain linear elasticity, sigma = lambda tr(H) I + mu (H + H^T), whose internal force does not
+ * vanish under a rigid rotation - and a slender cantilever in bending rotates.  Total-Lagrangian: with H = grad_X u and
+ * F = I + H at the points of the K rule (order 1: the one constant gradient; order 2: the four Gauss points, H formed as the
+ * linear pass forms it) the first Piola-Kirchhoff stress P takes the place of sigma,
+ *     f_a[i] = sum_q w_q detJ_q sum_k P_q[i][k] dN_a/dX_k(q),
+ * with the sign and detJ convention of the linear pass of the same order and u masked to 0 on Dirichlet dofs on input.  Both
+ * materials take the handle's lambda and mu and linearise to the handle's K at u = 0:
+ *   SAA_MATERIAL_SVK          St. Venant-Kirchhoff: E = (H + H^T + H^T H)/2, S = lambda tr(E) I + 2 mu E, P = F S,
+ *                             W = lambda/2 tr(E)^2 + mu E:E
+ *   SAA_MATERIAL_NEO_HOOKEAN  compressible neo-Hooke: J = det F, P = mu (F - F^-T) + lambda ln(J) F^-T,
+ *                             W = mu/2 (F:F - 3) - mu ln J + lambda/2 (ln J)^2
+ * Inversion.  Under neo-Hooke an element with !(J > 0) at any of its points (NaN included) contributes 0 from all its corners
+ * for that evaluation and is counted; SVK does not look at J.  The counters are two device words updated with integer
+ * atomics.  There are no floating-point atomics: every result is bitwise repeatable and independent of how a run is split
+ * into calls.  The order-2 passes read the reduced geometry table of the "stored_geometry" option (40 doubles and one word
+ * per element), which the HANDLE owns: it is made on first need by whoever asks - this call, a stepper with that option or
+ * with a nonlinear material -, there is one per handle, and saa_operator_destroy frees it.  There is no recomputing
+ * variant of the order-2 finite-strain pass.
+ *
+ * saa_operator_internal_force: f_dev = f_int(x_dev), one column of 3*n_nodes doubles, 0 on Dirichlet dofs: the element pass
+ *   and the node sum of saa_operator_apply.  material = SAA_MATERIAL_LINEAR runs the kernels of saa_operator_apply with
+ *   m = 1 (bit-equal to it).  energy_elem_dev (n_elems doubles or NULL) = sum_q w_q |detJ_q| W(F_q) per element, 0 for an
+ *   inverted one; with the linear material it is refused (saa_operator_stress has that energy).  n_inverted (host, or NULL)
+ *   = the number of inverted elements of this call; asking for it synchronises the stream, otherwise the call is enqueued.
+ *   SAA_E_ARG, before the handle or the device is looked at: a material outside {0, 1, 2}; then a null handle, null x_dev or
+ *   f_dev, energy_elem_dev with material 0.
+ * saa_operator_stepper_set_material: the element pass of step, step_begin and step_predicted becomes that of `material`;
+ *   the node passes, the shared-node split, the recorder and the update are what they were, since they only sum whatever
+ *   the element pass wrote.  SAA_MATERIAL_LINEAR (the default) restores the linear pass that "stored_geometry" selects, and
+ *   then exactly the kernels of a stepper that never had a material are launched; that option governs the linear pass only.
+ *   Clears the inversion counters.  SAA_E_ARG as above; SAA_E_STATE between step_begin and step_finish, and while the energy
+ *   balance is on.  saa_operator_stepper_set_energy in turn returns SAA_E_STATE while a nonlinear material is set: its
+ *   identity needs a symmetric constant K, and a balance for W(F) is not provided.
+ *   THE TIME STEP IS NOT FOLLOWED: dt stays what the stepper was created with, by convention gamma * 2/omega_max of the
+ *   LINEAR operator at the reference configuration.  Under large stretch the tangent stiffens and the stability limit
+ *   moves below that; watch the displacements (and, under neo-Hooke, the inversion counters).
+ * saa_operator_stepper_inverted: count = the number of (element, step) inversion events since the counters were cleared,
+ *   first_step = the lowest step index (the recorder's, saa_operator_stepper_set_recorder) at which one occurred, -1 when
+ *   none did.  set_material and set_state clear them.  Synchronises the stream.  Either output may be NULL.
+ */
+#define SAA_MATERIAL_LINEAR 0
+#define SAA_MATERIAL_SVK 1
+#define SAA_MATERIAL_NEO_HOOKEAN 2
+int saa_operator_internal_force(saa_operator *op, int32_t material, const double *x_dev, double *f_dev,
+                                double *energy_elem_dev /* n_elems or NULL */, int64_t *n_inverted /* or NULL */);
+int saa_operator_stepper_set_material(saa_operator_stepper *st, int32_t material);
+int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int64_t *first_step /* -1: none */);
+
+/*
  * Shared-node predictor: the per-rank LSTM encoder-decoder of Tools/DNN_tools.py:16-98 (2-layer bidirectional encoder of
  * width hidden_size, decoder LSTM of width 2*hidden_size + Linear) evaluated for all filter_size phase offsets of one
  * prediction window - what Tools/DNN_prediction.py:38-55 (`encoder_decoder_predictor`) computes with filter_size

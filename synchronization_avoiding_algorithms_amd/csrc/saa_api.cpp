@@ -2219,6 +2219,20 @@ int saa_operator_lumped_mass(saa_operator *op, double *mass_dev) {
   return SAA_OK;
 }
 
+int saa_operator_internal_force(saa_operator *op, int32_t material, const double *x_dev, double *f_dev, double *energy_elem_dev,
+                                int64_t *n_inverted) {
+  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, "saa_operator_internal_force: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_internal_force: null handle");
+  if (!x_dev || !f_dev) return fail(SAA_E_ARG, "saa_operator_internal_force: null x_dev or f_dev");
+  if (energy_elem_dev && material == SAA_MATERIAL_LINEAR)
+    return fail(SAA_E_ARG, "saa_operator_internal_force: energy_elem_dev with the linear material (saa_operator_stress has its energy)");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_internal_force(op->impl, material, x_dev, f_dev, energy_elem_dev, n_inverted);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_internal_force: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
 struct saa_operator_stepper {
   saa::OpStepper *impl = nullptr;
 };
@@ -2250,7 +2264,8 @@ int saa_operator_stepper_set_state(saa_operator_stepper *st, const double *d0_de
   if (!std::isfinite(tn)) return fail(SAA_E_ARG, "saa_operator_stepper_set_state: tn must be finite");
   if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_state: a synchronised step is in flight");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_set_state(st->impl, d0_dev, dn_dev, tn);
+  hipError_t e = saa::opstep_set_state(st->impl, d0_dev, dn_dev, tn);
+  if (e == hipSuccess) e = saa::opstep_clear_inverted(st->impl);
   if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_state: ") + hipGetErrorString(e));
   return SAA_OK;
 }
@@ -2386,6 +2401,8 @@ int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev
   if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: a synchronised step is in flight");
   if (energy_dev && saa::opstep_passes(st->impl) != 3)
     return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: the passes option is 1 or 2 (a measurement aid that does not advance the state)");
+  if (energy_dev && saa::opstep_material(st->impl) != SAA_MATERIAL_LINEAR)
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: a nonlinear material is set (the identity needs a symmetric constant K)");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   const hipError_t e = saa::opstep_set_energy(st->impl, energy_dev, energy_dev ? n_rows : 0, energy_dev ? every : 1,
                                               energy_dev ? next_step_index : 0, shared_owned_host);
@@ -2393,8 +2410,30 @@ int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev
   return SAA_OK;
 }
 
+int saa_operator_stepper_set_material(saa_operator_stepper *st, int32_t material) {
+  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, "saa_operator_stepper_set_material: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_material: null handle");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_material: a synchronised step is in flight");
+  if (saa::opstep_energy_on(st->impl))
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_material: the energy balance is recorded (its identity is that of the linear operator)");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_set_material(st->impl, material);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_material: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int64_t *first_step) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_inverted: null handle");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_inverted(st->impl, count, first_step);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_inverted: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
 int saa_operator_stepper_destroy(saa_operator_stepper *st) {
   if (!st) return SAA_OK;
+  saa::opfs_release(st->impl);
   saa::opstep_destroy(st->impl);
   delete st;
   return SAA_OK;

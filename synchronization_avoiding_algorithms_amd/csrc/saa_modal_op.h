@@ -31,6 +31,11 @@ struct ModalOp {
   double *st_part_w = nullptr;   // [column][workgroup] partial energy sums
   double *st_part_vm = nullptr;  // [column][workgroup] partial von Mises maxima
   int32_t *st_part_idx = nullptr;
+  // order 2: the reduced geometry of opstep_geometry_kernel, made on first need (operator_geometry, saa_opstep.hip) - one
+  // table per handle, read by the stored-geometry pass of every stepper on it and by the finite-strain passes (saa_opfs.hip)
+  double *geom = nullptr;    // [40][n_elems]
+  uint32_t *bits = nullptr;  // n_elems
+  unsigned long long *fs_count = nullptr;  // saa_operator_internal_force: the two counter words of the call (saa_opfs.hip)
 };
 
 // The node pass of saa_modal.hip on any [column][pair][3] contributions of this handle's CSR: y[j][3v + c] = sum of node

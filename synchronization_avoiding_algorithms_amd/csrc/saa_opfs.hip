@@ -1,0 +1,348 @@
+// gfx950 kernels of the finite-strain (total-Lagrangian) element pass on the saa_operator handle, either element order, and
+// the host side of saa_operator_internal_force and of the stepper's material (saa_opstep.h).
+//
+//  * H = grad_X u and F = I + H at the points of the K rule: order 1 the one constant gradient of element_gradients, order 2
+//    H = T G at the four Gauss points exactly as p2_k_column (saa_opstep.hip) forms it.  The first Piola-Kirchhoff stress P
+//    takes the place of the linear pass's symmetric sigma and nothing else changes: f_a[i] = sum_q w_q detJ_q sum_k
+//    P_q[i][k] dN_a/dX_k(q), sign and detJ convention those of the linear pass of the same order, displacements on Dirichlet
+//    dofs masked to 0 on input.
+//      St. Venant-Kirchhoff:    E = (H + H^T + H^T H)/2, S = lam tr(E) I + 2 mu E, P = F S, W = lam/2 tr(E)^2 + mu E:E
+//      compressible neo-Hooke:  J = det F, P = mu (F - F^-T) + lam ln(J) F^-T, W = mu/2 (F:F - 3) - mu ln J + lam/2 (ln J)^2
+//    Both linearise to the handle's K at u = 0.
+//  * The pass writes the [npe e + corner][3] contributions the node passes of saa_modal.hip / saa_opstep.hip sum, so
+//    everything downstream of the element pass is what it was.  ENERGY = true also writes energy_elem[e] = sum_q w_q
+//    |detJ_q| W(F_q); the stepper launches ENERGY = false only.
+//  * Inversion (neo-Hooke only; SVK does not look at J): an element with !(J > 0) at any of its points, NaN included, writes
+//    all its contributions (and its energy) as 0 and is counted in two device words - the number of (element, step) events
+//    and the lowest step index of one - with integer atomics.  No floating-point atomics; bitwise repeatable.
+//  * Order 2 reads the reduced geometry of opstep_geometry_kernel, the component-major [40][n_elems] table and the free-dof
+//    bits, which the HANDLE owns (one table per handle, whoever asks first).  There is no recomputing variant.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "saa_modal_op.h"
+#include "saa_opstep.h"
+#include "saa_opstep_impl.h"
+#include "saa_p2.h"
+#include "saa_p2_elem.h"
+
+namespace saa {
+
+namespace {
+
+constexpr int kSvk = 1, kNeo = 2;
+
+// P (first Piola-Kirchhoff) and, with ENERGY, W of the material MAT at displacement gradient h.  false: MAT is neo-Hooke and
+// !(det F > 0); P and W are then not to be used.
+template <int MAT, bool ENERGY>
+__device__ __forceinline__ bool opfs_stress(const double h[3][3], double lam, double mu, double P[3][3], double &W) {
+  double F[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) F[i][k] = h[i][k] + (i == k ? 1.0 : 0.0);
+  if (MAT == kSvk) {
+    // E = (h + h^T + h^T h)/2, symmetric: the upper triangle is computed, the lower mirrored
+    double E[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = i; k < 3; ++k) {
+        E[i][k] = 0.5 * ((h[i][k] + h[k][i]) + (h[0][i] * h[0][k] + h[1][i] * h[1][k] + h[2][i] * h[2][k]));
+        E[k][i] = E[i][k];
+      }
+    const double tr = E[0][0] + E[1][1] + E[2][2];
+    if (ENERGY) {
+      double ee = 0.0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ee += E[i][k] * E[i][k];
+      W = 0.5 * lam * tr * tr + mu * ee;
+    }
+    const double ltr = lam * tr, mu2 = 2.0 * mu;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) E[i][k] = mu2 * E[i][k] + (i == k ? ltr : 0.0);  // S
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) P[i][k] = F[i][0] * E[0][k] + F[i][1] * E[1][k] + F[i][2] * E[2][k];
+    return true;
+  }
+  // cofactors of F: F^-T = C / J
+  double C[3][3];
+  C[0][0] = F[1][1] * F[2][2] - F[1][2] * F[2][1];
+  C[0][1] = F[1][2] * F[2][0] - F[1][0] * F[2][2];
+  C[0][2] = F[1][0] * F[2][1] - F[1][1] * F[2][0];
+  C[1][0] = F[0][2] * F[2][1] - F[0][1] * F[2][2];
+  C[1][1] = F[0][0] * F[2][2] - F[0][2] * F[2][0];
+  C[1][2] = F[0][1] * F[2][0] - F[0][0] * F[2][1];
+  C[2][0] = F[0][1] * F[1][2] - F[0][2] * F[1][1];
+  C[2][1] = F[0][2] * F[1][0] - F[0][0] * F[1][2];
+  C[2][2] = F[0][0] * F[1][1] - F[0][1] * F[1][0];
+  const double J = F[0][0] * C[0][0] + F[0][1] * C[0][1] + F[0][2] * C[0][2];
+  if (!(J > 0.0)) return false;
+  const double lnJ = log(J);
+  const double c = (lam * lnJ - mu) / J;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) P[i][k] = mu * F[i][k] + c * C[i][k];
+  if (ENERGY) {
+    // F:F - 3 = 2 tr(h) + h:h, without the cancellation
+    double hh = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) hh += h[i][k] * h[i][k];
+    W = 0.5 * mu * (2.0 * (h[0][0] + h[1][1] + h[2][2]) + hh) - mu * lnJ + 0.5 * lam * lnJ * lnJ;
+  }
+  return true;
+}
+
+// one inverted element of step `step`: cnt[0] += 1, cnt[1] = min(cnt[1], step)
+__device__ __forceinline__ void opfs_count(unsigned long long *cnt, int64_t step) {
+  atomicAdd(cnt, 1ull);
+  atomicMin(cnt + 1, static_cast<unsigned long long>(step));
+}
+
+}  // namespace
+
+// Finite-strain element pass, order 1, one column: out[12 e + 3 corner + component].
+template <int MAT, bool ENERGY>
+__global__ void __launch_bounds__(kThreads) opfs_elem_p1_kernel(int32_t n_elems, const double *__restrict__ xyz,
+                                                                const int32_t *__restrict__ tets, const double *__restrict__ free_mask,
+                                                                double lam, double mu, const double *__restrict__ x,
+                                                                double *__restrict__ out, double *__restrict__ energy_elem,
+                                                                unsigned long long *__restrict__ cnt, int64_t step) {
+  const int64_t e = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+  if (e >= n_elems) return;
+  int32_t v[4];
+  double g[4][3];
+  const double det = element_gradients(xyz, tets, e, v, g);
+  const double vol = det / 6.0;  // signed, like the linear pass
+  double u[4][3];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[a][c] = free_mask[3 * (int64_t)v[a] + c] * x[3 * (int64_t)v[a] + c];
+  double h[3][3], P[3][3], W = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) h[i][k] = u[0][i] * g[0][k] + u[1][i] * g[1][k] + u[2][i] * g[2][k] + u[3][i] * g[3][k];
+  const bool ok = opfs_stress<MAT, ENERGY>(h, lam, mu, P, W);
+  double *o = out + 12 * e;
+  if (!ok) {
+#pragma unroll
+    for (int j = 0; j < 12; ++j) o[j] = 0.0;
+    if (ENERGY) energy_elem[e] = 0.0;
+    opfs_count(cnt, step);
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) P[i][k] *= vol;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[3 * a + i] = P[i][0] * g[a][0] + P[i][1] * g[a][1] + P[i][2] * g[a][2];
+  if (ENERGY) energy_elem[e] = fabs(vol) * W;
+}
+
+// Finite-strain element pass, order 2, one column, geometry from the table: out[30 e + 3 corner + component].  The body of
+// p2_k_column (saa_opstep.hip) with P in the place of sigma; the four points are worked through one at a time, each
+// reading its own nine G and its wd, so that F, the strain and the stress of one point only are live next to T.
+template <int MAT, bool ENERGY>
+__global__ void __launch_bounds__(kThreads, 2) opfs_elem_p2_kernel(int32_t n_elems, const int32_t *__restrict__ cells,
+                                                                const double *__restrict__ geom,
+                                                                const uint32_t *__restrict__ bits_tab, double lam, double mu,
+                                                                const double *__restrict__ x, double *__restrict__ out,
+                                                                double *__restrict__ energy_elem,
+                                                                unsigned long long *__restrict__ cnt, int64_t step) {
+  constexpr Rule<4> R = make_rule4();
+  const int64_t e = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+  if (e >= n_elems) return;
+  const uint32_t bits = bits_tab[e];
+  // parametric gradients of the column at the four points: T[q][i][k] = sum_a u_a[i] dN_a/dxi_k(q)
+  double T[4][3][3];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) T[q][i][k] = 0.0;
+#pragma unroll
+  for (int a = 0; a < 10; ++a) {
+    const int64_t va = cells[10 * e + a];
+    double u[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double xv = x[3 * va + i];
+      u[i] = (bits >> (3 * a + i)) & 1u ? xv : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (R.dN[q][a][k] != 0.0) T[q][i][k] += u[i] * R.dN[q][a][k];
+  }
+  // H = T G, P(H), T <- w detJ P G^T
+  bool ok = true;
+  double en = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    double G[3][3], h[3][3], P[3][3], W = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) G[i][k] = geom[(9 * q + 3 * i + k) * (int64_t)n_elems + e];
+    const double wd = geom[(36 + q) * (int64_t)n_elems + e];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) h[i][k] = T[q][i][0] * G[0][k] + T[q][i][1] * G[1][k] + T[q][i][2] * G[2][k];
+    ok = opfs_stress<MAT, ENERGY>(h, lam, mu, P, W) && ok;
+    if (ENERGY) en += fabs(wd) * W;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) P[i][k] *= wd;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) T[q][i][k] = P[i][0] * G[k][0] + P[i][1] * G[k][1] + P[i][2] * G[k][2];
+  }
+  double *o = out + 30 * e;
+  if (MAT == kNeo && !ok) {
+#pragma unroll
+    for (int j = 0; j < 30; ++j) o[j] = 0.0;
+    if (ENERGY) energy_elem[e] = 0.0;
+    opfs_count(cnt, step);
+    return;
+  }
+  // f_a[i] = sum_q sum_k T[q][i][k] dN_a/dxi_k(q)
+#pragma unroll
+  for (int a = 0; a < 10; ++a)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double f = 0.0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (R.dN[q][a][k] != 0.0) f += T[q][i][k] * R.dN[q][a][k];
+      o[3 * a + i] = f;
+    }
+  if (ENERGY) energy_elem[e] = en;
+}
+
+#define OPFS_TRY(expr)               \
+  do {                               \
+    const hipError_t e_ = (expr);    \
+    if (e_ != hipSuccess) return e_; \
+  } while (0)
+
+namespace {
+
+// the two counter words: 0 events, no step yet (all ones)
+hipError_t reset_counters(unsigned long long *cnt, hipStream_t stream) {
+  OPFS_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), stream));
+  return hipMemsetAsync(cnt + 1, 0xff, sizeof(unsigned long long), stream);
+}
+
+hipError_t alloc_counters(unsigned long long **cnt, hipStream_t stream) {
+  if (*cnt) return hipSuccess;
+  OPFS_TRY(hipMalloc(reinterpret_cast<void **>(cnt), 2 * sizeof(unsigned long long)));
+  return reset_counters(*cnt, stream);
+}
+
+template <int MAT, bool ENERGY>
+hipError_t launch(ModalOp *op, const double *x, double *contrib, double *energy_elem, unsigned long long *cnt, int64_t step) {
+  if (op->n_elems == 0) return hipSuccess;
+  if (op->order == 2)
+    hipLaunchKernelGGL((opfs_elem_p2_kernel<MAT, ENERGY>), opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems,
+                       op->tets, op->geom, op->bits, op->lam, op->mu, x, contrib, energy_elem, cnt, step);
+  else
+    hipLaunchKernelGGL((opfs_elem_p1_kernel<MAT, ENERGY>), opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems,
+                       op->xyz, op->tets, op->free_mask, op->lam, op->mu, x, contrib, energy_elem, cnt, step);
+  return hipGetLastError();
+}
+
+hipError_t read_counters(ModalOp *op, const unsigned long long *cnt, int64_t *count, int64_t *first_step) {
+  unsigned long long host[2] = {0, ~0ull};
+  OPFS_TRY(hipMemcpyAsync(host, cnt, sizeof(host), hipMemcpyDeviceToHost, op->stream));
+  OPFS_TRY(hipStreamSynchronize(op->stream));
+  if (count) *count = static_cast<int64_t>(host[0]);
+  if (first_step) *first_step = host[1] == ~0ull ? -1 : static_cast<int64_t>(host[1]);
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t opfs_element_pass(OpStepper *st, const double *x, double *contrib) {
+  ModalOp *op = st->op;
+  if (st->material == kSvk) return launch<kSvk, false>(op, x, contrib, nullptr, st->inverted, st->step_index);
+  return launch<kNeo, false>(op, x, contrib, nullptr, st->inverted, st->step_index);
+}
+
+hipError_t operator_internal_force(ModalOp *op, int material, const double *x, double *f, double *energy_elem, int64_t *n_inverted) {
+  double *contrib = nullptr;
+  OPFS_TRY(operator_scratch(op, 1, &contrib));
+  if (material == 0) {
+    OPFS_TRY(op->order == 2 ? p2_elem_pass_k(op, x, contrib) : modal_elem_pass_k(op, x, contrib));
+    OPFS_TRY(modal_node_sum(op, 1, contrib, 0, f, 0));
+    if (n_inverted) *n_inverted = 0;
+    return hipSuccess;
+  }
+  OPFS_TRY(operator_geometry(op));
+  OPFS_TRY(alloc_counters(&op->fs_count, op->stream));
+  OPFS_TRY(reset_counters(op->fs_count, op->stream));
+  if (material == kSvk)
+    OPFS_TRY(energy_elem ? (launch<kSvk, true>(op, x, contrib, energy_elem, op->fs_count, 0))
+                         : (launch<kSvk, false>(op, x, contrib, nullptr, op->fs_count, 0)));
+  else
+    OPFS_TRY(energy_elem ? (launch<kNeo, true>(op, x, contrib, energy_elem, op->fs_count, 0))
+                         : (launch<kNeo, false>(op, x, contrib, nullptr, op->fs_count, 0)));
+  OPFS_TRY(modal_node_sum(op, 1, contrib, 0, f, 0));
+  if (n_inverted) OPFS_TRY(read_counters(op, op->fs_count, n_inverted, nullptr));
+  return hipSuccess;
+}
+
+int opstep_material(const OpStepper *st) { return st->material; }
+
+hipError_t opstep_set_material(OpStepper *st, int material) {
+  ModalOp *op = st->op;
+  if (material != 0) {
+    OPFS_TRY(operator_geometry(op));
+    OPFS_TRY(alloc_counters(&st->inverted, op->stream));
+  }
+  st->material = material;
+  return opstep_clear_inverted(st);
+}
+
+hipError_t opstep_clear_inverted(OpStepper *st) { return st->inverted ? reset_counters(st->inverted, st->op->stream) : hipSuccess; }
+
+hipError_t opstep_inverted(OpStepper *st, int64_t *count, int64_t *first_step) {
+  if (!st->inverted) {
+    OPFS_TRY(hipStreamSynchronize(st->op->stream));
+    if (count) *count = 0;
+    if (first_step) *first_step = -1;
+    return hipSuccess;
+  }
+  return read_counters(st->op, st->inverted, count, first_step);
+}
+
+void opfs_release(OpStepper *st) {
+  if (!st || !st->inverted) return;
+  (void)hipSetDevice(st->op->device);
+  (void)hipFree(st->inverted);
+  st->inverted = nullptr;
+}
+
+}  // namespace saa

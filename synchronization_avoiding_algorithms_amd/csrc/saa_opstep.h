@@ -78,4 +78,21 @@ hipError_t opstep_set_energy(OpStepper *st, double *energy, int64_t n_rows, int3
 bool opstep_energy_on(const OpStepper *st);
 int opstep_passes(const OpStepper *st);  // the "passes" option
 
+// Finite strain (saa_opfs.hip, which states the materials).  material 0 / 1 / 2 = linear / St. Venant-Kirchhoff / compressible
+// neo-Hooke, validated by the caller.
+// f = the internal force of one column x (0 on Dirichlet dofs): the element pass and modal_node_sum.  material 0: the linear
+// passes of saa_operator_apply, energy_elem must be NULL.  energy_elem (n_elems device doubles or NULL) = sum_q w_q |detJ_q|
+// W(F_q).  n_inverted (host, or NULL): neo-Hooke elements with !(det F > 0) at a point, which contributed 0; reading it
+// synchronises the stream.  An order-2 handle makes its geometry table on first need.
+hipError_t operator_internal_force(ModalOp *op, int material, const double *x, double *f, double *energy_elem, int64_t *n_inverted);
+// The stepper's element pass becomes that of `material` (0: the linear pass the "stored_geometry" option selects); makes
+// the handle's geometry table and the stepper's two inversion counters on first need and clears the counters.
+hipError_t opstep_set_material(OpStepper *st, int material);
+int opstep_material(const OpStepper *st);
+// count = (element, step) inversion events since the counters were cleared, first_step = the lowest step index of one
+// (-1: none).  Synchronises the stream.
+hipError_t opstep_inverted(OpStepper *st, int64_t *count, int64_t *first_step);
+hipError_t opstep_clear_inverted(OpStepper *st);  // enqueued
+void opfs_release(OpStepper *st);                 // frees the counters; before opstep_destroy
+
 }  // namespace saa

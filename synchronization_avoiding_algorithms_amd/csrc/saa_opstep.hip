@@ -358,23 +358,18 @@ hipError_t dev_alloc(T **p, size_t count) {
   return hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T));
 }
 
-// builds the geometry table of an order-2 stepper on first need
+// the handle's geometry table (order 2), built on first need; a stepper reads the handle's
 hipError_t ensure_geometry(OpStepper *st) {
-  ModalOp *op = st->op;
-  if (st->geom || op->order != 2) return hipSuccess;
-  OPSTEP_TRY(dev_alloc(&st->geom, 40 * static_cast<size_t>(op->n_elems)));
-  OPSTEP_TRY(dev_alloc(&st->bits, static_cast<size_t>(op->n_elems)));
-  if (op->n_elems > 0) {
-    hipLaunchKernelGGL(opstep_geometry_kernel, grid_for(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
-                       op->free_mask, st->geom, st->bits);
-    OPSTEP_TRY(hipGetLastError());
-  }
+  OPSTEP_TRY(operator_geometry(st->op));
+  st->geom = st->op->geom;
+  st->bits = st->op->bits;
   return hipSuccess;
 }
 
 // the K element pass of one column x into contrib, by the variant the stepper is set to
 hipError_t element_pass(OpStepper *st, const double *x, double *contrib) {
   ModalOp *op = st->op;
+  if (st->material != 0) return opfs_element_pass(st, x, contrib);
   if (op->order != 2) return modal_elem_pass_k(op, x, contrib);
   if (!st->stored) return p2_elem_pass_k(op, x, contrib);
   if (op->n_elems == 0) return hipSuccess;
@@ -384,6 +379,18 @@ hipError_t element_pass(OpStepper *st, const double *x, double *contrib) {
 }
 
 }  // namespace
+
+hipError_t operator_geometry(ModalOp *op) {
+  if (op->geom || op->order != 2) return hipSuccess;
+  if (!op->bits) OPSTEP_TRY(dev_alloc(&op->bits, static_cast<size_t>(op->n_elems)));
+  OPSTEP_TRY(dev_alloc(&op->geom, 40 * static_cast<size_t>(op->n_elems)));  // (geom set = both exist)
+  if (op->n_elems > 0) {
+    hipLaunchKernelGGL(opstep_geometry_kernel, grid_for(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
+                       op->free_mask, op->geom, op->bits);
+    OPSTEP_TRY(hipGetLastError());
+  }
+  return hipSuccess;
+}
 
 hipError_t operator_lumped_mass(ModalOp *op, double *mass) {
   double *contrib = nullptr;
@@ -406,7 +413,7 @@ void opstep_destroy(OpStepper *st) {
   if (!st) return;
   (void)hipSetDevice(st->op->device);
   openergy_clear(st);
-  void *bufs[] = {st->mass, st->f, st->buf[0], st->buf[1], st->geom, st->bits, st->shared_of, st->node, st->slot, st->foreign};
+  void *bufs[] = {st->mass, st->f, st->buf[0], st->buf[1], st->shared_of, st->node, st->slot, st->foreign};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   delete st;

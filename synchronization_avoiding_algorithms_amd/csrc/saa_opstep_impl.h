@@ -26,8 +26,8 @@ struct OpStepper {
   double *mass = nullptr, *f = nullptr;
   double *buf[2] = {nullptr, nullptr};  // buf[cur] = d0, buf[1 - cur] = dn
   int cur = 0;
-  double *geom = nullptr;               // order 2, stored geometry: [40][n_elems]
-  uint32_t *bits = nullptr;             // n_elems
+  double *geom = nullptr;               // order 2, stored geometry: [40][n_elems]; the handle's table (op->geom), borrowed
+  uint32_t *bits = nullptr;             // n_elems; op->bits, borrowed
   bool stored = false;
   int passes = 3;                       // measurement aid: 1 = element pass only, 2 = node pass only (state not advanced)
   double dt = 0.0, alpha = 0.0, tn = 0.0;
@@ -48,6 +48,9 @@ struct OpStepper {
   double *energy_part = nullptr;   // [node-pass blocks, then finish blocks][5] partial sums of one step
   double *energy_run = nullptr;    // the running W, D
   uint8_t *owned = nullptr;        // n_shared flags: this rank counts the mass and load terms of its k-th shared node
+  // the material (saa_opfs.hip): 0 linear - the passes above -, 1 St. Venant-Kirchhoff, 2 compressible neo-Hooke
+  int material = 0;
+  unsigned long long *inverted = nullptr;  // two device words: (element, step) inversion events, lowest step index (all ones: none)
 };
 
 inline dim3 opstep_grid(int64_t n) { return dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)); }
@@ -60,6 +63,12 @@ hipError_t opstep_element_pass(OpStepper *st, const double *x, double *contrib);
 int64_t opstep_recorder_column(const OpStepper *st);
 hipError_t opstep_ensure_shared_map(OpStepper *st);
 void opstep_advance(OpStepper *st);
+
+// saa_opstep.hip: the handle's order-2 geometry table op->geom / op->bits, built on first need (order 1: nothing).
+hipError_t operator_geometry(ModalOp *op);
+// saa_opfs.hip: the finite-strain element pass of the stepper's material (!= 0) for one column x into contrib; an inverted
+// element is counted at st->step_index.
+hipError_t opfs_element_pass(OpStepper *st, const double *x, double *contrib);
 
 // saa_openergy.hip: the four loops of saa_opstep.h with the energy kernels, entered from them when st->energy is set.
 hipError_t openergy_step(OpStepper *st, int32_t nsteps);

@@ -259,7 +259,7 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
 
 
 def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1, E=None, nu=None, rho=None, fz=None,
-             alpha=None, gamma=None, parts=0, partition="slab", energy_every=0):
+             alpha=None, gamma=None, parts=0, partition="slab", energy_every=0, material="linear"):
     """The explicit run of the whole mesh on one GPU through the operator handle (:func:`dynamics.run_dynamics`), for
     linear (``order=1``) or quadratic tetrahedra (``order=2``: the mesh is elevated like ``steady_state --order 2``),
     clamped on every node of ``x = 0``: lumped mass of the handle (HRZ for order 2), the reference load ``(0, -fz, -fz)``
@@ -268,7 +268,11 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     the mesh cut into ``P`` parts (``partition``: slab, graph or rcb, on the vertex tetrahedra), every synchronised step
     split around the sum of the shared-node forces (:class:`dynamics.OperatorPartition`); same file.  ``energy_every = S >
     0``: the energy balance of every ``S``-th step (``T, U_{n+1/2}, U_n, W, D``, ``include/saa_hip.h``) goes to dataset
-    ``Energy`` of ``Results/Dynamics/Energy_order{p}.hdf5``, and the report gains ``energy`` and ``energy_path``."""
+    ``Energy`` of ``Results/Dynamics/Energy_order{p}.hdf5``, and the report gains ``energy`` and ``energy_path``.
+    ``material``: ``linear``, ``svk`` (St. Venant-Kirchhoff) or ``neo_hookean`` - the finite-strain element pass
+    (``include/saa_hip.h``); with a nonlinear one the report gains ``material``, ``inverted`` and ``first_inverted_step``.  ``dt`` stays that of
+    the LINEAR operator at the reference configuration: under large stretch the tangent stiffens, the stability limit moves,
+    and the stepper does not follow it.  The energy balance is defined for ``linear`` only (ValueError otherwise)."""
     from .dynamics import run_dynamics
     from .mesh import plane_nodes
 
@@ -281,7 +285,7 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     cells = mesh.tets10 if order == 2 else mesh.tets
     epart = make_partition(mesh, int(parts), partition) if parts and int(parts) > 0 else None
     store, report, *table = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device,
-                                         epart=epart, energy_every=int(energy_every or 0), **p)
+                                         epart=epart, energy_every=int(energy_every or 0), material=material, **p)
     path = rio.save_displacement(os.path.join(out_dir, PATHS["dynamics"].format(p=order)), store)
     if table:
         report["energy_path"] = rio.save_displacement(os.path.join(out_dir, PATHS["energy"].format(p=order)), table[0],
@@ -784,6 +788,13 @@ def main(argv=None):
     ap.add_argument("--energy", action="store_true",
                     help="dynamics: record the energy balance (kinetic, strain, work, damping loss) and store the table")
     ap.add_argument("--energy-every", type=int, default=1, help="dynamics --energy: every so many steps")
+    ap.add_argument("--material", choices=["linear", "svk", "neo-hookean"], default="linear",
+                    help="dynamics: the element pass - small-strain linear elasticity, or finite strain with the St. "
+                         "Venant-Kirchhoff or the compressible neo-Hookean material.  dt stays gamma * 2/omega_max of the linear "
+                         "operator at the reference configuration: under large stretch the stability limit moves and the "
+                         "stepper does not follow it")
+    ap.add_argument("--fz", type=float, default=0.5,
+                    help="dynamics: the amplitude of the load (0, -fz, -fz); at the default nothing is nonlinear")
     ap.add_argument("--n-past", type=int, default=20)
     ap.add_argument("--n-future", type=int, default=20)
     ap.add_argument("--filter-size", type=int, default=150)
@@ -803,6 +814,9 @@ def main(argv=None):
                     help="steady_state, modal, dynamics, stress, estimate: 2 = quadratic tetrahedra (the mesh is elevated "
                          "unless the file holds tetra10); stress and estimate then read the run of dynamics --order 2")
     args = ap.parse_args(argv)
+    if args.command == "dynamics" and args.energy and args.material != "linear":
+        ap.error(f"dynamics --material {args.material} --energy: the energy balance is defined for the linear material only "
+                 "(its identity needs a symmetric constant K)")
     if args.command in ("stress", "estimate") and args.order == 2 and args.modeled:
         ap.error(f"{args.command} --order 2 --modeled: there is no modelled p = 2 run (the predictor drives linear elements)")
     rank, world, local = _dist_env()
@@ -820,7 +834,8 @@ def main(argv=None):
         elif args.command == "dynamics":
             path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order,
                                     parts=args.parts, partition=args.partition,
-                                    energy_every=max(args.energy_every, 1) if args.energy else 0)
+                                    energy_every=max(args.energy_every, 1) if args.energy else 0, fz=args.fz,
+                                    material=args.material)
             print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]

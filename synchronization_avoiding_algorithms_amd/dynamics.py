@@ -31,9 +31,10 @@ from .solver import _dev
 class OperatorStepper:
     """``saa_operator_stepper`` on a :class:`modal.ModalOperator` (borrowed: it must stay open while this object lives).
     ``mass`` and ``load`` (the un-ramped ``f``): ``(n_dof,)`` float64, CUDA tensors or arrays, copied.  State
-    ``d0 = dn = 0``, ``tn = 0``."""
+    ``d0 = dn = 0``, ``tn = 0``.  ``material``: ``linear`` (the default: exactly the kernels of a stepper without a material),
+    ``svk`` or ``neo_hookean`` (:meth:`set_material`)."""
 
-    def __init__(self, op, mass, load, dt, alpha, ramp=True):
+    def __init__(self, op, mass, load, dt, alpha, ramp=True, material="linear"):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.op = op
@@ -46,6 +47,23 @@ class OperatorStepper:
         m, f = self._vector(mass), self._vector(load)
         _lib.check(self._lib.saa_operator_stepper_create(op._h, _dev(m), _dev(f), float(dt), float(alpha), 1 if ramp else 0,
                                                          C.byref(self._h)))
+        self.material = "linear"
+        if _lib.material_id(material) != 0:
+            self.set_material(material)
+
+    def set_material(self, name):
+        """The element pass becomes the finite-strain pass of ``svk`` / ``neo_hookean``, or the linear pass again
+        (``saa_operator_stepper_set_material``); clears the inversion counters.  ``dt`` is NOT adapted: it stays what the
+        stepper was made with, and under large stretch the stability limit moves below the linear operator's."""
+        _lib.check(self._lib.saa_operator_stepper_set_material(self._h, _lib.material_id(name)))
+        self.material = str(name).replace("-", "_")
+
+    def inverted(self):
+        """``(count, first_step)``: the (element, step) events at which neo-Hooke found an element inverted and dropped its
+        contributions since :meth:`set_material` / :meth:`set_state`, and the lowest step index of one (-1: none)."""
+        count, first = C.c_int64(0), C.c_int64(-1)
+        _lib.check(self._lib.saa_operator_stepper_inverted(self._h, C.byref(count), C.byref(first)))
+        return int(count.value), int(first.value)
 
     def _vector(self, a):
         import torch
@@ -223,7 +241,7 @@ class OperatorRank:
     which is right for a world of one only."""
 
     def __init__(self, points, layout, global_shared, mass, load, lmd, mu, rho, dt, alpha, reduce=None, ramp=True, device=0,
-                 stored_geometry=None, layouts=None):
+                 stored_geometry=None, layouts=None, material="linear"):
         import torch
 
         from .modal import ModalOperator
@@ -240,7 +258,7 @@ class OperatorRank:
             return t.to(device=self.tensor_device, dtype=torch.float64).reshape(-1)[dof]
 
         self.global_dof = dof
-        self.stepper = OperatorStepper(self.op, local(mass), local(load), dt, alpha, ramp=ramp)
+        self.stepper = OperatorStepper(self.op, local(mass), local(load), dt, alpha, ramp=ramp, material=material)
         if stored_geometry is not None:
             self.stepper.set_option("stored_geometry", stored_geometry)
         self.stepper.set_shared(layout.shared_local, layout.shared_slots, self.n_global_shared)
@@ -303,10 +321,10 @@ class OperatorPartition:
     """All ``P`` ranks of a partition in one process on one GPU: the one-GPU rehearsal of the partitioned loop.  The
     whole-mesh operator is built once for the lumped mass (HRZ for order 2), the load ``(0, -fz, -fz)`` and ``dt = gamma *
     2/omega_max`` (``dt`` given: taken as is; ``lame = (lambda, mu)`` given: instead of ``E``, ``nu``); then one
-    :class:`OperatorRank` per part of ``epart``."""
+    :class:`OperatorRank` per part of ``epart``.  ``material``: every rank's (``dt`` stays the linear operator's)."""
 
     def __init__(self, points, cells, dirichlet_nodes, epart, n_parts=None, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5, gamma=0.9,
-                 ramp=True, device=0, stored_geometry=None, dt=None, lame=None):
+                 ramp=True, device=0, stored_geometry=None, dt=None, lame=None, material="linear"):
         import torch
 
         from . import fem_setup as fs
@@ -327,7 +345,8 @@ class OperatorPartition:
         self.dt = self.time_step["dt"]
         layouts, self.global_shared = fs.build_layouts(cells, epart, self.n_parts, len(points), dirichlet_nodes)
         self.ranks = [OperatorRank(points, lay, self.global_shared, mass, load, lmd, mu, rho, self.dt, alpha, None, ramp, device,
-                                   stored_geometry, layouts) for lay in layouts]
+                                   stored_geometry, layouts, material) for lay in layouts]
+        self.material = str(material).replace("-", "_")
         self._energy = None
         self._sum = torch.zeros(3 * len(self.global_shared), dtype=torch.float64, device=self.tensor_device)
 
@@ -383,6 +402,13 @@ class OperatorPartition:
             total += e
         return total
 
+    def inverted(self):
+        """``(count, first_step)`` of :meth:`OperatorStepper.inverted` over the ranks: the counts summed (an element lives on
+        one rank), the lowest first step (-1: none)."""
+        each = [r.stepper.inverted() for r in self.ranks]
+        firsts = [f for _, f in each if f >= 0]
+        return sum(c for c, _ in each), (min(firsts) if firsts else -1)
+
     def gather(self, which="d0"):
         """The global ``(3 n,)`` CUDA vector of ``d0`` or ``dn``; a shared node comes from its lowest holder."""
         import torch
@@ -430,15 +456,24 @@ def energy_report(rows):
 
 
 def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5,
-                 gamma=0.9, device=0, epart=None, energy_every=0):
+                 gamma=0.9, device=0, epart=None, energy_every=0, material="linear"):
     """What ``drivers dynamics`` computes: the operator of ``cells`` (4 columns: order 1, 10: order 2) clamped on
     ``dirichlet_nodes``, its lumped mass, the reference load ``(0, -fz, -fz)`` ramped over ``t < 1``, ``dt = gamma *
     2/omega_max`` and ``n_steps`` steps recorded every ``save_every``.  Returns ``(trajectory (n_dof, n_cols) array,
     report dict)``.  ``epart`` (element -> part): the same run through :class:`OperatorPartition`, every rank recording
     its own nodes; the report gains ``parts``, ``n_global_shared`` and ``shared_per_rank``.  ``energy_every = S > 0``: the
     energy balance is recorded every ``S`` steps, the report gains ``energy`` (:func:`energy_report`) and the return value
-    a third member, the ``(ceil(n_steps / S), 5)`` table (of a partition: the sum of the ranks' shares)."""
+    a third member, the ``(ceil(n_steps / S), 5)`` table (of a partition: the sum of the ranks' shares).  ``material``:
+    ``linear``, ``svk`` or ``neo_hookean``; with a nonlinear one the report gains ``material``, ``inverted`` and
+    ``first_inverted_step`` (with ``linear`` it is what it always was, key for key).  ``dt``
+    stays that of the linear operator at the reference configuration whatever the material; the energy balance is defined
+    for ``linear`` only (ValueError otherwise)."""
     import torch
+
+    mat = _lib.material_id(material)
+    material = str(material).replace("-", "_")
+    if mat != 0 and energy_every:
+        raise ValueError("the energy balance is defined for the linear material only: its identity needs a symmetric constant K")
 
     from . import fem_setup as fs
     from .modal import ModalOperator, stable_time_step_operator
@@ -447,18 +482,19 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
     cells = np.ascontiguousarray(cells, dtype=np.int32)
     if epart is not None:
         return _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device,
-                                   energy_every)
+                                   energy_every, material)
     n_rows = -(-int(n_steps) // int(energy_every)) if energy_every else 0
     lmd, mu = fs.lame(E, nu)
     with ModalOperator(points, cells, fs.node_to_dof(dirichlet_nodes), lmd, mu, rho, device) as op:
         mass = op.lumped_mass()
         ts = stable_time_step_operator(op, mass, gamma)
         n_cols = int(n_steps / save_every)
-        with OperatorStepper(op, mass, op.load((0.0, -fz, -fz)), ts["dt"], alpha, ramp=True) as st:
+        with OperatorStepper(op, mass, op.load((0.0, -fz, -fz)), ts["dt"], alpha, ramp=True, material=material) as st:
             traj = st.record(n_cols, save_every) if n_cols > 0 else None
             rows = st.record_energy(n_rows, energy_every) if n_rows > 0 else None
             st.step(n_steps)
             d0, _, tn = st.state()
+            inverted, first_inverted = st.inverted()
             store = traj.cpu().numpy() if traj is not None else np.zeros((op.n_dof, 0))
             table = rows.cpu().numpy() if rows is not None else np.zeros((0, 5))
         d = d0.cpu().numpy().reshape(-1, 3)
@@ -469,6 +505,8 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
                   "n_free_dofs": int(op.free.sum().item()), "dt": ts["dt"], "dt_crit": ts["dt_crit"],
                   "dt_reference_rule": rule, "ratio": rule / ts["dt_crit"], "omega_max": ts["omega_max"], "steps": int(n_steps),
                   "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean())}
+        if mat != 0:
+            report.update(material=material, inverted=inverted, first_inverted_step=first_inverted)
     torch.cuda.synchronize(device)
     if energy_every:
         report["energy"] = energy_report(table)
@@ -477,14 +515,15 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
 
 
 def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device,
-                        energy_every=0):
+                        energy_every=0, material="linear"):
     import torch
 
     from . import fem_setup as fs
     from .modal import ModalOperator
 
     n_cols = int(n_steps / save_every)
-    with OperatorPartition(points, cells, dirichlet_nodes, epart, None, E, nu, rho, fz, alpha, gamma, True, device) as part:
+    with OperatorPartition(points, cells, dirichlet_nodes, epart, None, E, nu, rho, fz, alpha, gamma, True, device,
+                           material=material) as part:
         trajs = [r.stepper.record(n_cols, save_every) if n_cols > 0 else None for r in part.ranks]
         n_rows = -(-int(n_steps) // int(energy_every)) if energy_every else 0
         if n_rows > 0:
@@ -493,6 +532,7 @@ def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_eve
         table = part.energy().cpu().numpy() if n_rows > 0 else np.zeros((0, 5))
         d = part.gather("d0").cpu().numpy().reshape(-1, 3)
         tn = part.tn
+        inverted, first_inverted = part.inverted()
         store = np.zeros((part.n_dof, n_cols))
         for r, traj in reversed(list(zip(part.ranks, trajs))):
             if traj is not None:
@@ -509,6 +549,8 @@ def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_eve
               "dt_crit": ts["dt_crit"], "dt_reference_rule": rule, "ratio": rule / ts["dt_crit"], "omega_max": ts["omega_max"],
               "steps": int(n_steps), "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean()),
               "parts": parts, "n_global_shared": n_global_shared, "shared_per_rank": shared}
+    if _lib.material_id(material) != 0:
+        report.update(material=material, inverted=inverted, first_inverted_step=first_inverted)
     torch.cuda.synchronize(device)
     if energy_every:
         report["energy"] = energy_report(table)

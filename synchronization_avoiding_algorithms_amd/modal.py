@@ -189,6 +189,25 @@ class ModalOperator:
         _lib.check(self._lib.saa_operator_lumped_mass(self._h, C.c_void_p(out.data_ptr())))
         return out
 
+    def internal_force(self, x, material="svk", energy=False):
+        """The internal force ``f_int(x)`` of one ``(n_dof,)`` float64 CUDA displacement vector under ``material``
+        (``linear``, ``svk``: St. Venant-Kirchhoff, ``neo_hookean``: compressible neo-Hooke; ``include/saa_hip.h`` has the
+        definitions), 0 on Dirichlet dofs (``saa_operator_internal_force``).  ``linear`` is ``apply(x)[0]`` bit for bit.
+        ``energy=True`` (not with ``linear``): returns ``(f, energy_elem, n_inverted)`` - the stored energy per element and
+        the number of elements that neo-Hooke found inverted (``!(det F > 0)`` at a point), which contributed 0."""
+        import torch
+
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.numel() == self.n_dof):
+            raise ValueError(f"x must be a float64 CUDA tensor of {self.n_dof} values")
+        x = x.reshape(-1).contiguous()
+        f = torch.empty_like(x)
+        en = torch.empty(self.n_elems, dtype=torch.float64, device=self.torch_device) if energy else None
+        n_inv = C.c_int64(0)
+        _lib.check(self._lib.saa_operator_internal_force(self._h, _lib.material_id(material), C.c_void_p(x.data_ptr()),
+                                                         C.c_void_p(f.data_ptr()), C.c_void_p(en.data_ptr()) if energy else None,
+                                                         C.byref(n_inv) if energy else None))
+        return (f, en, int(n_inv.value)) if energy else f
+
     def element_bound(self, return_omega=False) -> dict:
         """``omega_max`` bound ``max_e omega_e``, its element, the count of elements with signed volume <= 0 and
         whether the bound is certified (that count is 0); ``omega_e`` (a CUDA tensor) on request."""
