@@ -67,12 +67,12 @@ hipError_t opstep_step_predicted(OpStepper *st, int32_t nsteps, const double *ta
 // gather: row[3 k + c] = d0[3 node_k + c]; else the reverse.
 hipError_t opstep_halo(OpStepper *st, double *row, bool gather);
 
-// The energy balance (saa_openergy.hip, which states the identity and the shares of a partition).  energy: device, row-major
+// The energy balance (saa_opstep.hip states the identity and the shares of a partition).  energy: device, row-major
 // (n_rows, 5) = T_{n+1/2}, U_{n+1/2}, U_n, W, D, the row of energy step index i at i / every when i % every == 0 and the row
 // exists; NULL switches the balance off.  shared_owned: n_shared host bytes (NULL: all owned).  While it is on, step, step_begin
-// / step_finish and step_predicted launch the energy variants of the node and finish passes (same state, bit for bit) and one
-// more one-block kernel per step; off, exactly the kernels of saa_opstep.hip.  Zeroes the running W, D.  Synchronises the
-// stream.  opstep_set_shared switches it off.  With a shared set, opstep_step counts every node of the rank as owned.
+// / step_finish and step_predicted launch the ENERGY instantiations of the node and finish passes (same state, bit for bit)
+// and one more one-block kernel per step.  Zeroes the running W, D.  Synchronises the stream.  opstep_set_shared switches it
+// off.  With a shared set, opstep_step counts every node of the rank as owned.
 hipError_t opstep_set_energy(OpStepper *st, double *energy, int64_t n_rows, int32_t every, int64_t next_step_index,
                              const uint8_t *shared_owned);
 bool opstep_energy_on(const OpStepper *st);

@@ -10,15 +10,38 @@
 //    m = 1), or, for order 2, opstep_elem_p2_kernel, which reads the element's reduced geometry - J^-1 and w detJ at the four
 //    points of the K rule, 40 fp64, and its 30 free-dof bits - from a table built once, component-major ([40][n_elems]) so
 //    that a wave reads every component coalesced, instead of rebuilding four Jacobians from thirty gathered coordinates.
-//    (b) opstep_node_update_kernel, one lane per node, sums the node's contributions through the node -> (element, corner)
-//    CSR in ascending element order, forms d1 and writes it over dn (a lane touches its own node only, so two buffers and a
-//    pointer swap are the whole state), and writes the recorder column.  f_int never exists in memory.  No floating-point
-//    atomics; every result is bitwise repeatable.  The loop is not captured in a HIP graph.
-//  * The same step on one rank of a partition (saa_operator_stepper_set_shared).  Synchronised: opstep_shared_node_kernel
-//    <false> is the node pass that sends a shared node's sum to the interface buffer instead of updating it, and after the
-//    caller's reduction over the ranks opstep_shared_finish_kernel, one lane per shared or foreign dof, updates the shared
-//    dofs.  Predicted: opstep_shared_node_kernel<true> writes the table row over the shared dofs and into the history in the
-//    node pass itself, so a predicted step stays at two launches.
+//    (b) opstep_node_kernel<MODE, ENERGY>, one lane per node, sums the node's contributions through the node -> (element,
+//    corner) CSR in ascending element order, forms d1 and writes it over dn (a lane touches its own node only, so two buffers
+//    and a pointer swap are the whole state), and writes the recorder column.  f_int never exists in memory.  No
+//    floating-point atomics; every result is bitwise repeatable.  The loop is not captured in a HIP graph.
+//  * The same step on one rank of a partition (saa_operator_stepper_set_shared).  Synchronised: MODE 1 is the node pass that
+//    sends a shared node's sum to the interface buffer instead of updating it, and after the caller's reduction over the
+//    ranks opstep_finish_kernel<ENERGY>, one lane per shared or foreign dof, updates the shared dofs.  Predicted: MODE 2
+//    writes the table row over the shared dofs and into the history in the node pass itself, so a predicted step stays at
+//    two launches.  Every dof of every pass is updated by opstep_update_dof, so a shared node is rounded by the finish kernel
+//    exactly as the node pass would have rounded it.
+//  * The energy balance (saa_operator_stepper_set_energy), ENERGY = true.  The central-difference update
+//    m (d1 - 2 d0 + dn)/dt^2 + alpha m (d1 - dn)/(2 dt) + s = lambda f with s = K d0, multiplied by (d1 - dn)/2 and summed
+//    over the dofs, is with the symmetry of K
+//        (T + U)_{n+1/2} - (T + U)_{n-1/2} = dW_n - dD_n,
+//        T_{n+1/2} = 1/2 sum m ((d1 - d0)/dt)^2,  U_{n+1/2} = 1/2 sum d1 s,  dW_n = lambda sum f (d1 - dn)/2,
+//        dD_n = alpha/(4 dt) sum m (d1 - dn)^2,
+//    exactly, in the discrete sense.  The node pass holds every one of these factors per lane - s in registers, where it
+//    never reaches memory - so the balance costs a block reduction and one small launch per step, not another sweep over the
+//    mesh.  Each lane adds its share to five sums, the block reduces them - __shfl_down over the 64 lanes of a wave, then the
+//    four waves through LDS in wave order - and writes one [block][5] partial; the finish pass likewise, its partials after
+//    the node pass's.  opstep_energy_final_kernel, one block: lane t sums partials t, t + 256, ... in ascending order, the
+//    block reduces as above, and lane 0 adds dW, dD to the running W, D and writes the row (T, U_{n+1/2}, U_n, W, D) on a
+//    recording step.  No floating-point atomics here either: the rows do not depend on how a run is split into calls.  All of
+//    it sits under `if (ENERGY)` in the two kernels, so the state is the same with the balance on and off by construction and
+//    the ENERGY = false instantiations carry none of it.
+//  * Shares of a partition (the rows of all ranks add up to the row of the whole mesh).  A dof counts when it is free and its
+//    node has elements on this rank.  Terms with m or f - T, dW, dD - carry the global mass and load, which every holder of a
+//    shared node has in full: a shared node counts only on the rank whose flag owned[k] is set.  U_n = 1/2 sum d0 s is formed
+//    from the rank's partial s on every holder, and the partial s add up to s.  U_{n+1/2} of a shared node: in a
+//    synchronised step from the summed s of the interface buffer in the finish kernel, on the owner; in a predicted step
+//    from the partial s on every holder (each with the d1 of its own table) - which is why MODE 2 sums a shared node's
+//    contributions when ENERGY is set, and leaves before them when it is not.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -216,117 +239,203 @@ __global__ void __launch_bounds__(kThreads) opstep_mass_check_kernel(int32_t n_n
   if (!(mass[3 * v] > 0.0 && mass[3 * v + 1] > 0.0 && mass[3 * v + 2] > 0.0)) atomicAdd(count, 1);
 }
 
-// Node pass fused with the update, either order: f_int = the node's contributions in ascending element order,
-//   d1 = (dt^2 (scale f - f_int) + 2 m d0 - m dn + dt/2 m alpha dn) / (m + alpha m dt / 2)     (Dynamic_solver.py:13-20),
-// 0 on Dirichlet dofs and at a node without elements; d1 replaces dn, and goes to column `col` of the row-major
-// (3 n_nodes, n_cols) recorder when col >= 0.
-__global__ void __launch_bounds__(kThreads) opstep_node_update_kernel(
-    int32_t n_nodes, const int64_t *__restrict__ offsets, const int32_t *__restrict__ pairs, const double *__restrict__ free_mask,
-    const double *__restrict__ contrib, const double *__restrict__ mass, const double *__restrict__ f, const double *__restrict__ d0,
-    double *__restrict__ dn, double dt, double alpha, double scale, double *__restrict__ traj, int64_t n_cols, int64_t col) {
-  const int64_t v = blockIdx.x * (int64_t)kThreads + threadIdx.x;
-  if (v >= n_nodes) return;
-  const int64_t b = offsets[v], end = offsets[v + 1];
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int64_t i = b; i < end; ++i) {
-    const double *q = contrib + 3 * (int64_t)pairs[i];
-    s[0] += q[0];
-    s[1] += q[1];
-    s[2] += q[2];
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int64_t i = 3 * v + c;
-    const bool live = end > b && free_mask[i] != 0.0;
-    const double m = mass[i], x0 = d0[i], xn = dn[i];
-    const double num = dt * dt * (scale * f[i] - s[c]) + 2.0 * m * x0 - m * xn + 0.5 * dt * m * alpha * xn;
-    const double den = m + alpha * m * 0.5 * dt;
-    const double d1 = live ? num / den : 0.0;  // (a node without elements may carry mass 0: never its 0/0)
-    dn[i] = d1;
-    if (col >= 0) traj[i * n_cols + col] = d1;
-  }
+// ---- the node pass and the finish pass ---------------------------------------------------------------------------------
+
+// The update of one dof, Dynamic_solver.py:13-20, shared by the node pass and the finish pass, so that a shared node is
+// rounded by the finish kernel exactly as the node pass would have rounded it.
+__device__ __forceinline__ double opstep_update_dof(bool live, double s, double fi, double m, double x0, double xn, double dt,
+                                                    double alpha, double scale) {
+  const double num = dt * dt * (scale * fi - s) + 2.0 * m * x0 - m * xn + 0.5 * dt * m * alpha * xn;
+  const double den = m + alpha * m * 0.5 * dt;
+  return live ? num / den : 0.0;
 }
 
-// ---- a partition of the mesh: shared nodes (saa_operator_stepper_set_shared) ---------------------------------------------
-// The update of one dof is opstep_update_dof (saa_opstep_impl.h): the text of opstep_node_update_kernel's loop body, shared
-// by every kernel below so that a shared node is rounded by the finish kernel exactly as the node pass would have rounded it.
+constexpr int kCols = 5;  // of the energy balance: T_{n+1/2}, U_{n+1/2}, U_n, dW (row: W), dD (row: D)
+constexpr int kWaves = kThreads / 64;
+static_assert(kThreads % 64 == 0, "the block reduction works on whole waves");
 
-// The node pass of a partition, one lane per node.  A node that is not shared (shared_of[v] < 0) is updated as by
-// opstep_node_update_kernel.  A shared node, k = shared_of[v] its place in the rank's shared list:
-//   PREDICTED = false (step_begin): its summed contributions go to iface[3 slot[k] + c]; dn and the recorder are left
-//     alone, because d1 overwrites dn in place and the true d1 needs the other ranks' sums (opstep_shared_finish_kernel);
-//   PREDICTED = true: d1 = table_row[3 k + c] unconditionally, a Dirichlet dof included (halo_overwrite_kernel,
+namespace {
+
+// One dof's share of the balance.  `mass_terms`: this rank counts T, dW and dD of the dof.
+__device__ __forceinline__ void energy_add(double (&e)[kCols], bool mass_terms, double s, double fi, double m, double x0, double xn,
+                                           double d1, double dt, double alpha, double scale) {
+  const double v = (d1 - x0) / dt, w = d1 - xn;
+  if (mass_terms) {
+    e[0] += 0.5 * m * (v * v);
+    e[3] += scale * fi * (0.5 * w);
+    e[4] += alpha / (4.0 * dt) * m * (w * w);
+  }
+  e[1] += 0.5 * d1 * s;
+}
+
+// The sums of e[] over the block, valid in lanes 0 .. kCols - 1 of the return value: a wave by __shfl_down (lanes past the
+// data hold 0), the waves through LDS in wave order.  Every lane of the block must call it.
+__device__ __forceinline__ double block_sum(double (&e)[kCols]) {
+  __shared__ double lds[kWaves][kCols];
+#pragma unroll
+  for (int c = 0; c < kCols; ++c)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e[c] += __shfl_down(e[c], off);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < kCols; ++c) lds[wave][c] = e[c];
+  }
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x < kCols) {
+    t = lds[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) t += lds[w][threadIdx.x];
+  }
+  return t;
+}
+
+}  // namespace
+
+// Node pass fused with the update, either order, one lane per node: f_int = the node's contributions in ascending element
+// order,
+//   d1 = (dt^2 (scale f - f_int) + 2 m d0 - m dn + dt/2 m alpha dn) / (m + alpha m dt / 2)     (opstep_update_dof),
+// 0 on Dirichlet dofs and at a node without elements; d1 replaces dn, and goes to column `col` of the row-major
+// (3 n_nodes, n_cols) recorder when col >= 0.  MODE 0 is the whole mesh.  MODE 1 and 2 are one rank of a partition, where a
+// node with k = shared_of[v] >= 0 is the k-th of the rank's shared list:
+//   MODE 1 (step_begin): its summed contributions go to iface[3 slot[k] + c]; dn and the recorder are left alone, because d1
+//     overwrites dn in place and the true d1 needs the other ranks' sums (opstep_finish_kernel);
+//   MODE 2 (predicted): d1 = table_row[3 k + c] unconditionally, a Dirichlet dof included (halo_overwrite_kernel,
 //     Online_predictor.py:298), recorded in hist_row (:301) and in the recorder column.
-template <bool PREDICTED>
-__global__ void __launch_bounds__(kThreads) opstep_shared_node_kernel(
+// ENERGY: the block's five sums go to partial[kCols blockIdx.x + ...]; no lane returns before block_sum.
+template <int MODE, bool ENERGY>
+__global__ void __launch_bounds__(kThreads) opstep_node_kernel(
     int32_t n_nodes, const int64_t *__restrict__ offsets, const int32_t *__restrict__ pairs, const double *__restrict__ free_mask,
     const double *__restrict__ contrib, const double *__restrict__ mass, const double *__restrict__ f, const double *__restrict__ d0,
     double *__restrict__ dn, double dt, double alpha, double scale, double *__restrict__ traj, int64_t n_cols, int64_t col,
     const int32_t *__restrict__ shared_of, const int32_t *__restrict__ slot, double *__restrict__ iface,
-    const double *__restrict__ table_row, double *__restrict__ hist_row) {
+    const double *__restrict__ table_row, double *__restrict__ hist_row, const uint8_t *__restrict__ owned,
+    double *__restrict__ partial) {
   const int64_t v = blockIdx.x * (int64_t)kThreads + threadIdx.x;
-  if (v >= n_nodes) return;
-  const int32_t k = shared_of[v];
-  if (PREDICTED && k >= 0) {
+  double e[kCols] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if (v < n_nodes) {
+    const int32_t k = MODE == 0 ? -1 : shared_of[v];
+    const bool predicted = MODE == 2 && k >= 0;
+    if (predicted && !ENERGY) {  // nothing of the node is needed but its table row
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int64_t i = 3 * v + c;
-      const double d1 = table_row[3 * (int64_t)k + c];
-      dn[i] = d1;
-      if (hist_row) hist_row[3 * (int64_t)k + c] = d1;
-      if (col >= 0) traj[i * n_cols + col] = d1;
+      for (int c = 0; c < 3; ++c) {
+        const int64_t i = 3 * v + c;
+        const double d1 = table_row[3 * (int64_t)k + c];
+        dn[i] = d1;
+        if (hist_row) hist_row[3 * (int64_t)k + c] = d1;
+        if (col >= 0) traj[i * n_cols + col] = d1;
+      }
+      return;
     }
-    return;
-  }
-  const int64_t b = offsets[v], end = offsets[v + 1];
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int64_t i = b; i < end; ++i) {
-    const double *q = contrib + 3 * (int64_t)pairs[i];
-    s[0] += q[0];
-    s[1] += q[1];
-    s[2] += q[2];
-  }
-  if (!PREDICTED && k >= 0) {
-    double *o = iface + 3 * (int64_t)slot[k];
-    o[0] = s[0];
-    o[1] = s[1];
-    o[2] = s[2];
-    return;
-  }
+    const int64_t b = offsets[v], end = offsets[v + 1];
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = b; i < end; ++i) {
+      const double *q = contrib + 3 * (int64_t)pairs[i];
+      s[0] += q[0];
+      s[1] += q[1];
+      s[2] += q[2];
+    }
+    if (MODE == 1 && k >= 0) {
+      double *o = iface + 3 * (int64_t)slot[k];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int64_t i = 3 * v + c;
-    const double d1 = opstep_update_dof(end > b && free_mask[i] != 0.0, s[c], f[i], mass[i], d0[i], dn[i], dt, alpha, scale);
-    dn[i] = d1;
-    if (col >= 0) traj[i * n_cols + col] = d1;
+      for (int c = 0; c < 3; ++c) {
+        const int64_t i = 3 * v + c;
+        o[c] = s[c];
+        if (ENERGY && end > b && free_mask[i] != 0.0) e[2] += 0.5 * d0[i] * s[c];
+      }
+    } else {
+      const bool mine = ENERGY && predicted ? owned[k] != 0 : true;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int64_t i = 3 * v + c;
+        const bool live = end > b && free_mask[i] != 0.0;
+        const double fi = f[i], m = mass[i], x0 = d0[i], xn = dn[i];
+        double d1;
+        if (ENERGY && predicted) {
+          d1 = table_row[3 * (int64_t)k + c];
+          if (hist_row) hist_row[3 * (int64_t)k + c] = d1;
+        } else {
+          d1 = opstep_update_dof(live, s[c], fi, m, x0, xn, dt, alpha, scale);  // (a node without elements: never its 0/0)
+        }
+        dn[i] = d1;
+        if (col >= 0) traj[i * n_cols + col] = d1;
+        if (ENERGY && live) {
+          energy_add(e, mine, s[c], fi, m, x0, xn, d1, dt, alpha, scale);
+          e[2] += 0.5 * x0 * s[c];
+        }
+      }
+    }
+  }
+  if (ENERGY) {
+    const double t = block_sum(e);
+    if (threadIdx.x < kCols) partial[kCols * (int64_t)blockIdx.x + threadIdx.x] = t;
   }
 }
 
 // After the reduction of iface over the ranks, one lane per shared dof and per foreign dof: d1 of shared dof 3 k + c from
 // the summed force iface[3 slot[k] + c] (0 on a Dirichlet dof) over dn, into the recorder column and into hist_row; the
 // slots of shared nodes this rank does not hold are zeroed, so that the next sum sees fresh partial forces only
-// (iface_finish_kernel of saa_kernels.hip).
-__global__ void __launch_bounds__(kThreads) opstep_shared_finish_kernel(
+// (iface_finish_kernel of saa_kernels.hip).  ENERGY: the shared dofs' share of T, U_{n+1/2} (from the summed s), dW and dD,
+// on the owner.
+template <bool ENERGY>
+__global__ void __launch_bounds__(kThreads) opstep_finish_kernel(
     int32_t n_shared, int32_t n_foreign, const int32_t *__restrict__ node, const int32_t *__restrict__ slot,
     const int32_t *__restrict__ foreign, const int64_t *__restrict__ offsets, const double *__restrict__ free_mask,
     const double *__restrict__ mass, const double *__restrict__ f, const double *__restrict__ d0, double *__restrict__ dn, double dt,
     double alpha, double scale, double *__restrict__ traj, int64_t n_cols, int64_t col, double *__restrict__ iface,
-    double *__restrict__ hist_row) {
+    double *__restrict__ hist_row, const uint8_t *__restrict__ owned, double *__restrict__ partial) {
   const int64_t j = blockIdx.x * (int64_t)kThreads + threadIdx.x;
   const int64_t n_local = 3 * (int64_t)n_shared;
+  double e[kCols] = {0.0, 0.0, 0.0, 0.0, 0.0};
   if (j < n_local) {
     const int64_t k = j / 3;
     const int c = (int)(j - 3 * k);
     const int64_t v = node[k], i = 3 * v + c;
     const double s = iface[3 * (int64_t)slot[k] + c];
-    const double d1 =
-        opstep_update_dof(offsets[v + 1] > offsets[v] && free_mask[i] != 0.0, s, f[i], mass[i], d0[i], dn[i], dt, alpha, scale);
+    const bool live = offsets[v + 1] > offsets[v] && free_mask[i] != 0.0;
+    const double fi = f[i], m = mass[i], x0 = d0[i], xn = dn[i];
+    const double d1 = opstep_update_dof(live, s, fi, m, x0, xn, dt, alpha, scale);
     dn[i] = d1;
     if (col >= 0) traj[i * n_cols + col] = d1;
     if (hist_row) hist_row[j] = d1;
+    if (ENERGY && live && owned[k] != 0) energy_add(e, true, s, fi, m, x0, xn, d1, dt, alpha, scale);
   } else if (j < n_local + 3 * (int64_t)n_foreign) {
     const int64_t r = j - n_local;
     iface[3 * (int64_t)foreign[r / 3] + (r % 3)] = 0.0;
+  }
+  if (ENERGY) {
+    const double t = block_sum(e);
+    if (threadIdx.x < kCols) partial[kCols * (int64_t)blockIdx.x + threadIdx.x] = t;
+  }
+}
+
+// One block.  The step's sums from its n_part partials; run[0] += dW, run[1] += dD; row >= 0: energy[kCols row + ...] =
+// T_{n+1/2}, U_{n+1/2}, U_n, W_{n+1}, D_{n+1}.
+__global__ void __launch_bounds__(kThreads) opstep_energy_final_kernel(int32_t n_part, const double *__restrict__ partial,
+                                                                       double *__restrict__ run, double *__restrict__ energy,
+                                                                       int64_t row) {
+  __shared__ double total[kCols];
+  double e[kCols] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int32_t b = threadIdx.x; b < n_part; b += kThreads) {
+#pragma unroll
+    for (int c = 0; c < kCols; ++c) e[c] += partial[kCols * (int64_t)b + c];
+  }
+  const double t = block_sum(e);
+  if (threadIdx.x < kCols) total[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double W = run[0] + total[3], D = run[1] + total[4];
+    run[0] = W;
+    run[1] = D;
+    if (row >= 0) {
+      double *o = energy + kCols * row;
+      o[0] = total[0];
+      o[1] = total[1];
+      o[2] = total[2];
+      o[3] = W;
+      o[4] = D;
+    }
   }
 }
 
@@ -351,19 +460,20 @@ __global__ void __launch_bounds__(kThreads) opstep_halo_kernel(int32_t n_shared,
 
 namespace {
 
-dim3 grid_for(int64_t n) { return dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)); }
-
 template <typename T>
 hipError_t dev_alloc(T **p, size_t count) {
   return hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T));
 }
 
-// the handle's geometry table (order 2), built on first need; a stepper reads the handle's
-hipError_t ensure_geometry(OpStepper *st) {
-  OPSTEP_TRY(operator_geometry(st->op));
-  st->geom = st->op->geom;
-  st->bits = st->op->bits;
-  return hipSuccess;
+// frees the energy buffers and switches the balance off; the caller has made sure that nothing in flight reads them
+void energy_clear(OpStepper *st) {
+  void *bufs[] = {st->energy_part, st->energy_run, st->owned};
+  for (void *b : bufs)
+    if (b) (void)hipFree(b);
+  st->energy = st->energy_part = st->energy_run = nullptr;
+  st->owned = nullptr;
+  st->energy_rows = st->energy_index = 0;
+  st->energy_every = 1;
 }
 
 // the K element pass of one column x into contrib, by the variant the stepper is set to
@@ -373,8 +483,8 @@ hipError_t element_pass(OpStepper *st, const double *x, double *contrib) {
   if (op->order != 2) return modal_elem_pass_k(op, x, contrib);
   if (!st->stored) return p2_elem_pass_k(op, x, contrib);
   if (op->n_elems == 0) return hipSuccess;
-  hipLaunchKernelGGL(opstep_elem_p2_kernel, grid_for(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->tets, st->geom,
-                     st->bits, op->lam, op->mu, x, contrib);
+  hipLaunchKernelGGL(opstep_elem_p2_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->tets, op->geom,
+                     op->bits, op->lam, op->mu, x, contrib);
   return hipGetLastError();
 }
 
@@ -385,7 +495,7 @@ hipError_t operator_geometry(ModalOp *op) {
   if (!op->bits) OPSTEP_TRY(dev_alloc(&op->bits, static_cast<size_t>(op->n_elems)));
   OPSTEP_TRY(dev_alloc(&op->geom, 40 * static_cast<size_t>(op->n_elems)));  // (geom set = both exist)
   if (op->n_elems > 0) {
-    hipLaunchKernelGGL(opstep_geometry_kernel, grid_for(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
+    hipLaunchKernelGGL(opstep_geometry_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
                        op->free_mask, op->geom, op->bits);
     OPSTEP_TRY(hipGetLastError());
   }
@@ -397,14 +507,14 @@ hipError_t operator_lumped_mass(ModalOp *op, double *mass) {
   OPSTEP_TRY(operator_scratch(op, 1, &contrib));  // (npe n_elems scalars fit one column of 3 npe n_elems)
   if (op->n_elems > 0) {
     if (op->order == 2)
-      hipLaunchKernelGGL(opstep_hrz_mass_kernel, grid_for(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
+      hipLaunchKernelGGL(opstep_hrz_mass_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
                          op->rho, contrib);
     else
-      hipLaunchKernelGGL(opstep_p1_mass_kernel, grid_for(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
+      hipLaunchKernelGGL(opstep_p1_mass_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
                          op->rho, contrib);
     OPSTEP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(opstep_mass_node_kernel, grid_for(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs,
+  hipLaunchKernelGGL(opstep_mass_node_kernel, opstep_grid(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs,
                      contrib, mass);
   return hipGetLastError();
 }
@@ -412,7 +522,7 @@ hipError_t operator_lumped_mass(ModalOp *op, double *mass) {
 void opstep_destroy(OpStepper *st) {
   if (!st) return;
   (void)hipSetDevice(st->op->device);
-  openergy_clear(st);
+  energy_clear(st);
   void *bufs[] = {st->mass, st->f, st->buf[0], st->buf[1], st->shared_of, st->node, st->slot, st->foreign};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
@@ -444,7 +554,7 @@ hipError_t opstep_create(ModalOp *op, const double *mass, const double *f_ext, d
   if (e == hipSuccess) e = hipMemsetAsync(st->buf[1], 0, bytes, op->stream);
   if (e == hipSuccess) e = hipMemsetAsync(count, 0, sizeof(int32_t), op->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(opstep_mass_check_kernel, grid_for(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets,
+    hipLaunchKernelGGL(opstep_mass_check_kernel, opstep_grid(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets,
                        st->mass, count);
     e = hipGetLastError();
   }
@@ -455,7 +565,7 @@ hipError_t opstep_create(ModalOp *op, const double *mass, const double *f_ext, d
     err = "saa_operator_stepper_create: the mass is not > 0 at " + std::to_string(bad) + " node(s) that have elements";
     e = hipErrorInvalidValue;
   }
-  if (e == hipSuccess && st->stored) e = ensure_geometry(st);
+  if (e == hipSuccess && st->stored) e = operator_geometry(st->op);
   if (e != hipSuccess) {
     opstep_destroy(st);
     return e;
@@ -502,40 +612,13 @@ bool opstep_set_option(OpStepper *st, const char *name, double value, hipError_t
   }
   if (std::strcmp(name, "stored_geometry") != 0 || (value != 0.0 && value != 1.0)) return false;
   st->stored = value == 1.0 && st->op->order == 2;
-  if (st->stored) *e = ensure_geometry(st);
+  if (st->stored) *e = operator_geometry(st->op);
   return true;
-}
-
-hipError_t opstep_step(OpStepper *st, int32_t nsteps) {
-  ModalOp *op = st->op;
-  if (nsteps <= 0) return hipSuccess;
-  if (st->energy) return openergy_step(st, nsteps);
-  double *contrib = nullptr;
-  OPSTEP_TRY(operator_scratch(op, 1, &contrib));
-  for (int32_t k = 0; k < nsteps; ++k) {
-    const double *d0 = st->buf[st->cur];
-    if (st->passes & 1) OPSTEP_TRY(element_pass(st, d0, contrib));
-    if (st->passes == 1) continue;
-    const double scale = st->ramp ? (st->tn < 1.0 ? st->tn : 1.0) : 1.0;  // min(tn, 1), Dynamic_solver.py:13
-    int64_t col = -1;
-    if (st->traj && st->step_index % st->save_every == 0 && st->step_index / st->save_every < st->n_cols)
-      col = st->step_index / st->save_every;
-    hipLaunchKernelGGL(opstep_node_update_kernel, grid_for(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets,
-                       op->pairs, op->free_mask, contrib, st->mass, st->f, d0, st->buf[1 - st->cur], st->dt, st->alpha, scale, st->traj,
-                       st->n_cols, col);
-    OPSTEP_TRY(hipGetLastError());
-    if (st->passes != 3) continue;
-    st->cur = 1 - st->cur;
-    st->tn += st->dt;
-    ++st->step_index;
-    ++st->energy_index;
-  }
-  return hipSuccess;
 }
 
 namespace {
 
-double ramp_scale(const OpStepper *st) { return st->ramp ? (st->tn < 1.0 ? st->tn : 1.0) : 1.0; }  // min(tn, 1)
+double ramp_scale(const OpStepper *st) { return st->ramp ? (st->tn < 1.0 ? st->tn : 1.0) : 1.0; }  // min(tn, 1), Dynamic_solver.py:13
 
 int64_t recorder_column(const OpStepper *st) {
   if (st->traj && st->step_index % st->save_every == 0 && st->step_index / st->save_every < st->n_cols)
@@ -558,17 +641,87 @@ hipError_t ensure_shared_map(OpStepper *st) {
   return hipMemsetAsync(st->shared_of, 0xff, (n ? n : 1) * sizeof(int32_t), st->op->stream);
 }
 
+int32_t node_blocks(const OpStepper *st) { return static_cast<int32_t>(opstep_grid(st->op->n_nodes).x); }
+int64_t finish_lanes(const OpStepper *st) { return 3 * (static_cast<int64_t>(st->n_shared) + st->n_foreign); }
+
+// the energy row of this step, by the recorder's rule (-1: none)
+int64_t energy_row(const OpStepper *st) {
+  if (st->energy_index % st->energy_every == 0 && st->energy_index / st->energy_every < st->energy_rows)
+    return st->energy_index / st->energy_every;
+  return -1;
+}
+
+// balance on: the step's row from its first n_part partials (node-pass blocks first, then finish blocks)
+hipError_t finalise(OpStepper *st, int32_t n_part) {
+  if (!st->energy) return hipSuccess;
+  hipLaunchKernelGGL(opstep_energy_final_kernel, dim3(1), dim3(kThreads), 0, st->op->stream, n_part, st->energy_part, st->energy_run,
+                     st->energy, energy_row(st));
+  return hipGetLastError();
+}
+
+// the node pass of this step from contrib, with the energy sums when the balance is on
+template <int MODE>
+hipError_t node_pass(OpStepper *st, const double *contrib, const double *table_row, double *hist_row) {
+  ModalOp *op = st->op;
+  if (op->n_nodes == 0) return hipSuccess;
+  const auto kernel = st->energy ? opstep_node_kernel<MODE, true> : opstep_node_kernel<MODE, false>;
+  hipLaunchKernelGGL(kernel, opstep_grid(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs,
+                     op->free_mask, contrib, st->mass, st->f, st->buf[st->cur], st->buf[1 - st->cur], st->dt, st->alpha, ramp_scale(st),
+                     st->traj, st->n_cols, recorder_column(st), st->shared_of, st->slot, st->iface, table_row, hist_row, st->owned,
+                     st->energy_part);
+  return hipGetLastError();
+}
+
 }  // namespace
 
-hipError_t opstep_element_pass(OpStepper *st, const double *x, double *contrib) { return element_pass(st, x, contrib); }
-int64_t opstep_recorder_column(const OpStepper *st) { return recorder_column(st); }
-hipError_t opstep_ensure_shared_map(OpStepper *st) { return ensure_shared_map(st); }
-void opstep_advance(OpStepper *st) { advance(st); }
+hipError_t opstep_step(OpStepper *st, int32_t nsteps) {
+  if (nsteps <= 0) return hipSuccess;
+  double *contrib = nullptr;
+  OPSTEP_TRY(operator_scratch(st->op, 1, &contrib));
+  for (int32_t k = 0; k < nsteps; ++k) {
+    if (st->passes & 1) OPSTEP_TRY(element_pass(st, st->buf[st->cur], contrib));
+    if (st->passes == 1) continue;
+    OPSTEP_TRY(node_pass<0>(st, contrib, nullptr, nullptr));
+    if (st->passes != 3) continue;
+    OPSTEP_TRY(finalise(st, node_blocks(st)));
+    advance(st);
+  }
+  return hipSuccess;
+}
 
 bool opstep_pending(const OpStepper *st) { return st->pending; }
 int32_t opstep_n_shared(const OpStepper *st) { return st->n_shared; }
 bool opstep_lacks_interface_buffer(const OpStepper *st) { return st->n_global_shared > 0 && !st->iface; }
 void opstep_set_interface_buffer(OpStepper *st, double *iface) { st->iface = iface; }
+bool opstep_energy_on(const OpStepper *st) { return st->energy != nullptr; }
+int opstep_passes(const OpStepper *st) { return st->passes; }
+
+hipError_t opstep_set_energy(OpStepper *st, double *energy, int64_t n_rows, int32_t every, int64_t next_step_index,
+                             const uint8_t *shared_owned) {
+  ModalOp *op = st->op;
+  OPSTEP_TRY(hipStreamSynchronize(op->stream));  // the old buffers may still be read by work in flight
+  energy_clear(st);
+  if (!energy) return hipSuccess;
+  const size_t n_part = static_cast<size_t>(node_blocks(st)) + opstep_grid(finish_lanes(st)).x;
+  const size_t n_owned = st->n_shared > 0 ? static_cast<size_t>(st->n_shared) : 1;
+  std::vector<uint8_t> flags(n_owned, 1);
+  if (shared_owned)
+    for (int32_t k = 0; k < st->n_shared; ++k) flags[k] = shared_owned[k] ? 1 : 0;
+  hipError_t e = dev_alloc(&st->energy_part, n_part * kCols);
+  if (e == hipSuccess) e = dev_alloc(&st->energy_run, 2);
+  if (e == hipSuccess) e = dev_alloc(&st->owned, n_owned);
+  if (e == hipSuccess) e = hipMemsetAsync(st->energy_run, 0, 2 * sizeof(double), op->stream);
+  if (e == hipSuccess) e = hipMemcpy(st->owned, flags.data(), n_owned, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    energy_clear(st);
+    return e;
+  }
+  st->energy = energy;
+  st->energy_rows = n_rows;
+  st->energy_every = every;
+  st->energy_index = next_step_index;
+  return hipSuccess;
+}
 
 hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *shared_local, const int32_t *shared_slots,
                              int32_t n_global_shared, std::string &err) {
@@ -594,7 +747,7 @@ hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *sha
     if (!held[s]) foreign.push_back(s);
   // the old lists may still be read by work in flight
   OPSTEP_TRY(hipStreamSynchronize(op->stream));
-  openergy_clear(st);  // its ownership flags and partial sums are sized by the old lists
+  energy_clear(st);  // its ownership flags and partial sums are sized by the old lists
   void *old[] = {st->shared_of, st->node, st->slot, st->foreign};
   for (void *b : old)
     if (b) (void)hipFree(b);
@@ -619,33 +772,28 @@ hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *sha
 }
 
 hipError_t opstep_step_begin(OpStepper *st) {
-  ModalOp *op = st->op;
-  if (st->energy) return openergy_step_begin(st);
   double *contrib = nullptr;
-  OPSTEP_TRY(operator_scratch(op, 1, &contrib));
+  OPSTEP_TRY(operator_scratch(st->op, 1, &contrib));
   OPSTEP_TRY(ensure_shared_map(st));
-  const double *d0 = st->buf[st->cur];
-  OPSTEP_TRY(element_pass(st, d0, contrib));
-  hipLaunchKernelGGL(opstep_shared_node_kernel<false>, grid_for(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets,
-                     op->pairs, op->free_mask, contrib, st->mass, st->f, d0, st->buf[1 - st->cur], st->dt, st->alpha, ramp_scale(st),
-                     st->traj, st->n_cols, recorder_column(st), st->shared_of, st->slot, st->iface, nullptr, nullptr);
-  OPSTEP_TRY(hipGetLastError());
+  OPSTEP_TRY(element_pass(st, st->buf[st->cur], contrib));
+  OPSTEP_TRY(node_pass<1>(st, contrib, nullptr, nullptr));
   st->pending = true;
   return hipSuccess;
 }
 
 hipError_t opstep_step_finish(OpStepper *st, double *hist, int64_t hist_row) {
   ModalOp *op = st->op;
-  if (st->energy) return openergy_step_finish(st, hist, hist_row);
-  const int64_t lanes = 3 * (static_cast<int64_t>(st->n_shared) + st->n_foreign);
+  const int64_t lanes = finish_lanes(st);
   if (lanes > 0) {
     double *row = hist ? hist + hist_row * 3 * static_cast<int64_t>(st->n_shared) : nullptr;
-    hipLaunchKernelGGL(opstep_shared_finish_kernel, grid_for(lanes), dim3(kThreads), 0, op->stream, st->n_shared, st->n_foreign,
-                       st->node, st->slot, st->foreign, op->offsets, op->free_mask, st->mass, st->f, st->buf[st->cur],
-                       st->buf[1 - st->cur], st->dt, st->alpha, ramp_scale(st), st->traj, st->n_cols, recorder_column(st), st->iface,
-                       row);
+    const auto kernel = st->energy ? opstep_finish_kernel<true> : opstep_finish_kernel<false>;
+    hipLaunchKernelGGL(kernel, opstep_grid(lanes), dim3(kThreads), 0, op->stream, st->n_shared, st->n_foreign, st->node, st->slot,
+                       st->foreign, op->offsets, op->free_mask, st->mass, st->f, st->buf[st->cur], st->buf[1 - st->cur], st->dt,
+                       st->alpha, ramp_scale(st), st->traj, st->n_cols, recorder_column(st), st->iface, row, st->owned,
+                       st->energy ? st->energy_part + kCols * static_cast<int64_t>(node_blocks(st)) : nullptr);
     OPSTEP_TRY(hipGetLastError());
   }
+  OPSTEP_TRY(finalise(st, node_blocks(st) + static_cast<int32_t>(opstep_grid(lanes).x)));
   st->pending = false;
   advance(st);
   return hipSuccess;
@@ -653,21 +801,16 @@ hipError_t opstep_step_finish(OpStepper *st, double *hist, int64_t hist_row) {
 
 hipError_t opstep_step_predicted(OpStepper *st, int32_t nsteps, const double *table, int64_t table_row0, double *hist,
                                  int64_t hist_row0) {
-  ModalOp *op = st->op;
   if (nsteps <= 0) return hipSuccess;
-  if (st->energy) return openergy_step_predicted(st, nsteps, table, table_row0, hist, hist_row0);
   double *contrib = nullptr;
-  OPSTEP_TRY(operator_scratch(op, 1, &contrib));
+  OPSTEP_TRY(operator_scratch(st->op, 1, &contrib));
   OPSTEP_TRY(ensure_shared_map(st));
   const int64_t width = 3 * static_cast<int64_t>(st->n_shared);
   for (int32_t k = 0; k < nsteps; ++k) {
-    const double *d0 = st->buf[st->cur];
-    OPSTEP_TRY(element_pass(st, d0, contrib));
-    hipLaunchKernelGGL(opstep_shared_node_kernel<true>, grid_for(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets,
-                       op->pairs, op->free_mask, contrib, st->mass, st->f, d0, st->buf[1 - st->cur], st->dt, st->alpha, ramp_scale(st),
-                       st->traj, st->n_cols, recorder_column(st), st->shared_of, st->slot, nullptr,
-                       width > 0 ? table + (table_row0 + k) * width : nullptr, hist ? hist + (hist_row0 + k) * width : nullptr);
-    OPSTEP_TRY(hipGetLastError());
+    OPSTEP_TRY(element_pass(st, st->buf[st->cur], contrib));
+    OPSTEP_TRY(node_pass<2>(st, contrib, width > 0 ? table + (table_row0 + k) * width : nullptr,
+                            hist ? hist + (hist_row0 + k) * width : nullptr));
+    OPSTEP_TRY(finalise(st, node_blocks(st)));
     advance(st);
   }
   return hipSuccess;
@@ -677,10 +820,10 @@ hipError_t opstep_halo(OpStepper *st, double *row, bool gather) {
   const int64_t lanes = 3 * static_cast<int64_t>(st->n_shared);
   if (lanes == 0) return hipSuccess;
   if (gather)
-    hipLaunchKernelGGL(opstep_halo_kernel<true>, grid_for(lanes), dim3(kThreads), 0, st->op->stream, st->n_shared, st->node,
+    hipLaunchKernelGGL(opstep_halo_kernel<true>, opstep_grid(lanes), dim3(kThreads), 0, st->op->stream, st->n_shared, st->node,
                        st->buf[st->cur], row);
   else
-    hipLaunchKernelGGL(opstep_halo_kernel<false>, grid_for(lanes), dim3(kThreads), 0, st->op->stream, st->n_shared, st->node,
+    hipLaunchKernelGGL(opstep_halo_kernel<false>, opstep_grid(lanes), dim3(kThreads), 0, st->op->stream, st->n_shared, st->node,
                        st->buf[st->cur], row);
   return hipGetLastError();
 }

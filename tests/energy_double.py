@@ -1,4 +1,4 @@
-"""NumPy double of the energy balance of the operator stepper (``saa_operator_stepper_set_energy``, ``csrc/saa_openergy.hip``):
+"""NumPy double of the energy balance of the operator stepper (``saa_operator_stepper_set_energy``, ``csrc/saa_opstep.hip``):
 the five columns ``T_{n+1/2}, U_{n+1/2}, U_n, W, D`` from the states of the doubles of the time loop -
 ``p2_dynamics_double.run`` for the whole mesh, ``p2_partition_double.PartitionDouble`` for a partition - in plain float64
 sums, with ``K d`` from the double's own dense operator and, per rank, the shares under the lowest-holder ownership rule.

@@ -1,6 +1,6 @@
 """The energy balance of the operator stepper without a GPU: the new entry point and its argument checks, the discrete
 identity in the NumPy double (tests/energy_double.py), what a step above the stability limit looks like in it, and the
-register budget of csrc/saa_openergy.hip next to the unchanged rows of csrc/saa_opstep.hip.
+register budget of the energy instantiations of csrc/saa_opstep.hip next to the rows of the kernels they share it with.
 
 Bars.  The identity ``B_n = B_0`` is exact for the exact update.  A step rounds ``d1`` by ``eps |d0|``, which perturbs the
 increment ``d1 - d0`` the energies are made of by the relative ``eps |d0| / |d1 - d0|``; from rest ``d0`` is the sum of at
@@ -26,7 +26,8 @@ E, NU, RHO, FZ = 1e6, 0.3, 1.0, 0.5
 EPS = np.finfo(np.float64).eps
 OMEGA_MAX_36 = 8893.974037          # the dense omega_max of the 36-tet order-2 beam that tests/test_p2_dynamics.py pins
 
-# tools/kernel_resources.py --file=saa_opstep.hip on the parent commit: sgpr vgpr sgpr_spill vgpr_spill scratch occupancy
+# tools/kernel_resources.py --file=saa_opstep.hip: sgpr vgpr sgpr_spill vgpr_spill scratch occupancy.  The rows of the kernels
+# that the energy balance never touched, as they were before it existed:
 PARENT_ROWS = {
     "saa::opstep_geometry_kernel": (30, 108, 0, 0, 0, 4),
     "saa::opstep_elem_p2_kernel": (36, 148, 0, 0, 0, 3),
@@ -34,18 +35,32 @@ PARENT_ROWS = {
     "saa::opstep_p1_mass_kernel": (18, 34, 0, 0, 0, 8),
     "saa::opstep_mass_node_kernel": (14, 12, 0, 0, 0, 8),
     "saa::opstep_mass_check_kernel": (18, 6, 0, 0, 0, 8),
-    "saa::opstep_node_update_kernel": (32, 30, 0, 0, 0, 8),
-    "saa::opstep_shared_finish_kernel": (20, 22, 0, 0, 0, 8),
-    "void saa::opstep_shared_node_kernel<false>": (38, 30, 0, 0, 0, 8),
-    "void saa::opstep_shared_node_kernel<true>": (42, 30, 0, 0, 0, 8),
     "void saa::opstep_halo_kernel<true>": (15, 9, 0, 0, 0, 8),
     "void saa::opstep_halo_kernel<false>": (14, 11, 0, 0, 0, 8),
 }
-# the new node passes, as hipcc gives them: (vgpr, occupancy)
-NODE_PASSES = {"void saa::openergy_node_kernel<0>": (54, 8), "void saa::openergy_node_kernel<1>": (54, 8),
-               "void saa::openergy_node_kernel<2>": (58, 8)}
-PINNED_SUBSTRINGS = ("opstep_shared_node_kernel", "opstep_shared_finish_kernel", "opstep_halo_kernel", "opstep_node_update_kernel",
-                     "opstep_elem_p2_kernel")
+# The node pass <MODE, ENERGY>, the finish pass <ENERGY> and the final kernel of the balance, as hipcc gives them.
+MERGED_ROWS = {
+    "void saa::opstep_node_kernel<0, false>": (32, 30, 0, 0, 0, 8),
+    "void saa::opstep_node_kernel<1, false>": (38, 30, 0, 0, 0, 8),
+    "void saa::opstep_node_kernel<2, false>": (38, 30, 0, 0, 0, 8),
+    "void saa::opstep_finish_kernel<false>": (20, 22, 0, 0, 0, 8),
+    "void saa::opstep_node_kernel<0, true>": (32, 54, 0, 0, 0, 8),
+    "void saa::opstep_node_kernel<1, true>": (44, 54, 0, 0, 0, 8),
+    "void saa::opstep_node_kernel<2, true>": (44, 58, 0, 0, 0, 8),
+    "void saa::opstep_finish_kernel<true>": (30, 32, 0, 0, 0, 8),
+    "saa::opstep_energy_final_kernel": (19, 26, 0, 0, 0, 8),
+}
+# An energy-off instantiation against the kernel it replaced (opstep_node_update_kernel, opstep_shared_node_kernel<false>,
+# <true>, opstep_shared_finish_kernel, before the balance was merged into them): the same row, sgpr at most that kernel's.
+REPLACED_ROWS = {
+    "void saa::opstep_node_kernel<0, false>": (32, 30, 0, 0, 0, 8),
+    "void saa::opstep_node_kernel<1, false>": (38, 30, 0, 0, 0, 8),
+    "void saa::opstep_node_kernel<2, false>": (42, 30, 0, 0, 0, 8),
+    "void saa::opstep_finish_kernel<false>": (20, 22, 0, 0, 0, 8),
+}
+# the energy-on node passes: (vgpr, occupancy)
+NODE_PASSES = {"void saa::opstep_node_kernel<0, true>": (54, 8), "void saa::opstep_node_kernel<1, true>": (54, 8),
+               "void saa::opstep_node_kernel<2, true>": (58, 8)}
 
 
 def test_library_exports_the_energy_entry_point():
@@ -58,7 +73,7 @@ def test_library_exports_the_energy_entry_point():
     decl = " ".join(decl[:decl.index(";")].split())
     assert decl == ("int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev, int64_t n_rows, "
                     "int32_t every, int64_t next_step_index, const uint8_t *shared_owned_host)")
-    assert _lib.SOURCES.index("saa_openergy.hip") < _lib.SOURCES.index("saa_api.cpp") == len(_lib.SOURCES) - 1
+    assert "saa_openergy.hip" not in _lib.SOURCES and _lib.SOURCES.index("saa_opstep.hip") < _lib.SOURCES.index("saa_api.cpp") == len(_lib.SOURCES) - 1
     from synchronization_avoiding_algorithms_amd import dynamics, drivers, results_io
 
     assert hasattr(dynamics.OperatorStepper, "record_energy") and hasattr(dynamics.OperatorRank, "record_energy")
@@ -176,14 +191,16 @@ def _rows(file):
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not installed")
 def test_energy_kernels_use_no_scratch_and_the_stepper_kernels_are_the_parents():
     """The energy node passes carry five accumulators and the operands of the update past their last use in it: 54 / 54 / 58
-    vector registers against the parent's 30, still eight waves per SIMD.  With the balance off the kernels of
-    saa_opstep.hip are launched, and their rows are the parent's."""
-    rows = _rows("saa_openergy.hip")
-    assert len(rows) == 5, rows
+    vector registers against 30 with the balance off, still eight waves per SIMD.  With the balance off the ENERGY = false
+    instantiations of the same kernels are launched: they carry none of it, and their rows are those of the separate kernels
+    they replaced (sgpr: at most)."""
+    rows = _rows("saa_opstep.hip")
+    assert len(rows) == len(PARENT_ROWS) + len(MERGED_ROWS) == 17, rows
     for name, (sgpr, vgpr, sspill, vspill, scratch, occ) in rows.items():
         assert sspill == 0 and vspill == 0 and scratch == 0, (name, rows[name])
-        assert not any(s in name for s in PINNED_SUBSTRINGS), name
     for name, (vgpr, occ) in NODE_PASSES.items():
         assert rows[name][1] == vgpr and rows[name][5] == occ, (name, rows[name])
-    assert rows["saa::openergy_finish_kernel"][5] == 8 and rows["saa::openergy_final_kernel"][5] == 8
-    assert _rows("saa_opstep.hip") == PARENT_ROWS
+    assert rows["void saa::opstep_finish_kernel<true>"][5] == 8 and rows["saa::opstep_energy_final_kernel"][5] == 8
+    for name, was in REPLACED_ROWS.items():
+        assert rows[name][0] <= was[0] and rows[name][1:] == was[1:], (name, rows[name], was)
+    assert rows == {**PARENT_ROWS, **MERGED_ROWS}

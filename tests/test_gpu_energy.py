@@ -264,6 +264,67 @@ def test_predicted_windows_drift_by_the_work_through_the_interface(cases, name):
             assert all(torch.equal(a, b) for a, b in zip(state, synced))   # the true values back: the synchronised state
 
 
+@pytest.mark.parametrize("key", ("p2", "p1"))
+def test_mixed_calls_keep_the_indices_and_partial_offsets_with_the_balance_on_off_and_switched(cases, key):
+    """Rank 0 of the two slabs on its own, 40 steps through every host loop in turn: ``step`` x 7, ``step_begin`` /
+    ``step_finish`` x 11, ``step_predicted`` x 9 as 4 + 5, ``step_begin`` / ``step_finish`` x 13; the reduction by hand (the
+    interface buffer doubled: the other slab's partial forces taken as a copy of this one's).  Three steppers - the balance on
+    with ``every = 3``, off, and on / off after step 17 / on again at index 18 - must agree bit for bit in ``d0``, ``dn``, the
+    recorder and the history, and the rows of the first and the third wherever both recorded.  ``record_energy`` zeroes the
+    running ``W``, ``D``, so after the switch these two columns restart: there their increments from row 6 on are compared,
+    two running sums of 21 additions and two subtractions, each rounded by at most eps ``max |W|`` (or ``D``): 48 eps of it."""
+    import torch
+
+    from synchronization_avoiding_algorithms_amd import fem_setup as fs
+    from synchronization_avoiding_algorithms_amd.dynamics import OperatorRank
+
+    c = cases[key]
+    epart, P = c.epart("slab2")
+    lays, gs = fs.build_layouts(c.cells, epart, P, len(c.pts), c.dnodes)
+    every, n_rows, shared_table = 3, 14, []
+
+    def run(mode):
+        with OperatorRank(c.pts, lays[0], gs, c.p["mass"], c.p["load"], c.lmd, c.mu, c.rho, c.dt, ALPHA, layouts=lays) as rank:
+            st = rank.stepper
+            traj = st.record(20, save_every=2)
+            hist = torch.zeros((40, rank.input_size), dtype=torch.float64, device="cuda")
+            rows = [rank.record_energy(n_rows, every)] if mode != "off" else []
+
+            def synced(first, n):
+                for k in range(first, first + n):
+                    st.step_begin()
+                    rank.iface *= 2.0
+                    st.step_finish(hist, k)
+
+            st.step(7)
+            synced(7, 11)
+            if mode == "switched":
+                assert rank.record_energy(0) is None
+                rows.append(rank.record_energy(n_rows, every, next_step_index=18))
+            if not shared_table:
+                grow = 1.0 + 1e-3 * torch.arange(1, 10, device="cuda", dtype=hist.dtype)
+                shared_table.append((hist[17][None, :] * grow[:, None]).contiguous())
+            st.step_predicted(4, shared_table[0], 0, hist, 18)
+            st.step_predicted(5, shared_table[0], 4, hist, 22)
+            synced(27, 13)
+            d0, dn, tn = st.state()
+            return d0, dn, tn, traj.clone(), hist, [r.cpu() for r in rows]
+
+    on, off, switched = run("on"), run("off"), run("switched")
+    for other in (off, switched):
+        assert all(torch.equal(a, b) for a, b in zip(on[:2] + on[3:5], other[:2] + other[3:5])) and other[2] == on[2]
+    d0, _, _, traj, hist, (rows,) = on
+    assert float(d0.abs().max()) > 0 and bool(traj[:, -1].any()) and bool(hist[7:].any(dim=1).all()) and not bool(hist[:7].any())
+    assert torch.equal(hist[18:27], shared_table[0]) and bool(rows[1:].any(dim=1).all())  # (step 0: the ramp is at 0)
+    early, late = switched[5]
+    assert torch.equal(early[:6], rows[:6]) and not bool(early[6:].any())     # steps 0 .. 15, then switched off
+    assert torch.equal(late[6:, :3], rows[6:, :3]) and not bool(late[:6].any())
+    top = rows[:, 3:].abs().max(dim=0).values
+    err = ((late[6:, 3:] - late[6, 3:]) - (rows[6:, 3:] - rows[6, 3:])).abs().max(dim=0).values / top
+    print(key, "increments of W, D after the switch against the unswitched run / max |W|, |D|:", err.numpy())
+    assert bool((top > 0).all()) and bool((err <= 48 * np.finfo(np.float64).eps).all())
+
+
 # ---- 3. more partials than lanes ----------------------------------------------------------------------------------------------
 
 def test_large_mesh_has_more_partials_than_the_final_kernel_has_lanes():

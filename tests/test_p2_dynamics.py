@@ -152,12 +152,12 @@ def test_stepper_kernels_use_no_scratch_and_spill_no_vector_register():
         rows[" ".join(f[:-6])] = dict(zip(("sgpr", "vgpr", "sspill", "vspill", "scratch", "occ"), (int(v) for v in f[-6:])))
     print(out.stdout)
     for kernel in ("opstep_geometry_kernel", "opstep_elem_p2_kernel", "opstep_hrz_mass_kernel", "opstep_p1_mass_kernel",
-                   "opstep_mass_node_kernel", "opstep_mass_check_kernel", "opstep_node_update_kernel"):
+                   "opstep_mass_node_kernel", "opstep_mass_check_kernel", "opstep_node_kernel<0, false>"):
         assert any(kernel in k for k in rows), (kernel, rows)
     for name, r in rows.items():
         assert r["vspill"] == 0 and r["scratch"] == 0 and r["sspill"] == 0, (name, r)
     for name, r in rows.items():
         if "opstep_elem_p2_kernel" in name:
             assert r["vgpr"] <= 170 and r["occ"] >= 3, (name, r)
-        if "opstep_node_update_kernel" in name:
+        if "opstep_node_kernel<0, false>" in name:
             assert r["occ"] == 8, (name, r)

@@ -142,11 +142,12 @@ def test_partition_kernels_use_no_scratch_and_reach_occupancy_eight():
     print(out.stdout)
     for name, r in rows.items():
         assert r["vspill"] == 0 and r["scratch"] == 0 and r["sspill"] == 0, (name, r)
-    for kernel, count in (("opstep_shared_node_kernel", 2), ("opstep_shared_finish_kernel", 1), ("opstep_halo_kernel", 2)):
+    for kernel, count in (("opstep_node_kernel<1, false>", 1), ("opstep_node_kernel<2, false>", 1), ("opstep_node_kernel<1, true>", 1),
+                          ("opstep_node_kernel<2, true>", 1), ("opstep_finish_kernel", 2), ("opstep_halo_kernel", 2)):
         hit = [r for name, r in rows.items() if kernel in name]
         assert len(hit) == count, (kernel, rows)
         for r in hit:
             assert r["vgpr"] <= 64 and r["occ"] == 8, (kernel, r)
     for name in rows:                                                # the pins of tests/test_p2_dynamics.py stay unambiguous
-        if "opstep_shared" in name or "opstep_halo" in name:
-            assert "opstep_node_update_kernel" not in name and "opstep_elem_p2_kernel" not in name
+        if "opstep_finish" in name or "opstep_halo" in name:
+            assert "opstep_node_kernel" not in name and "opstep_elem_p2_kernel" not in name

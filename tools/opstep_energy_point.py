@@ -2,9 +2,9 @@
 """What the energy balance costs on the operator stepper on one MI355X: us/step with ``record_energy`` on against off, on
 structured_beam(n) (n = 19: 1 028 850 tets) elevated to order 2 and as it is at order 1, for the whole mesh
 (``saa_operator_stepper_step``) and for rank 0 of two slabs timed alone (``step_begin`` + ``step_finish`` and
-``step_predicted`` from a table of zeros; a world of one: nothing is reduced).  Off is the parent's step - the same kernels,
-which the unchanged resource rows of saa_opstep.hip below show - so the ratio on / off is the cost of the feature.  The two
-are timed alternately, twice each, with HIP events around regions of at least ``--seconds`` after a warm-up of every case;
+``step_predicted`` from a table of zeros; a world of one: nothing is reduced).  Off launches the ENERGY = false instantiations
+of the node and finish passes, which carry none of the balance - the resource rows of saa_opstep.hip below show both - so the
+ratio on / off is the cost of the feature.  The two are timed alternately, twice each, with HIP events around regions of at least ``--seconds`` after a warm-up of every case;
 the smaller of the two rounds is compared and both are printed, so the spread can be read next to the difference.
 Writes one text file (default profiles/p2_energy_step_stats.txt).
 
@@ -45,7 +45,7 @@ def main():
     E, nu, rho, fz, alpha = 1e6, 0.3, 1.0, 0.5, 0.5
     lmd, mu = fs.lame(E, nu)
     say(f"Energy balance on the operator stepper, one {torch.cuda.get_device_name(0)}: us/step with record_energy on against off "
-        f"(off = the parent's kernels).")
+        f"(off = the ENERGY = false instantiations).")
     say(f"Times: HIP events around a region of >= {args.seconds:.2f} s per figure, every case warmed up first, off and on alternating, "
         f"two rounds; the ratio compares the smaller of each.")
     best = {}
@@ -100,16 +100,15 @@ def main():
     for key in dict.fromkeys(k for k, _ in best):
         off, on = best[(key, 0)], best[(key, 1)]
         say(f"{key:56s} {off:9.1f} {on:9.1f} {on - off:+9.1f} {on / off:9.3f}")
-    for file in ("saa_openergy.hip", "saa_opstep.hip"):
-        say()
-        say(f"Registers (hipcc -Rpass-analysis=kernel-resource-usage, tools/kernel_resources.py --file={file}):")
-        if os.path.exists("/opt/rocm/bin/hipcc"):
-            res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), f"--file={file}"],
-                                 capture_output=True, text=True)
-            for ln in res.stdout.splitlines():
-                say("  " + ln)
-        else:
-            say("  hipcc not installed here: not measured")
+    say()
+    say("Registers (hipcc -Rpass-analysis=kernel-resource-usage, tools/kernel_resources.py --file=saa_opstep.hip):")
+    if os.path.exists("/opt/rocm/bin/hipcc"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "--file=saa_opstep.hip"],
+                             capture_output=True, text=True)
+        for ln in res.stdout.splitlines():
+            say("  " + ln)
+    else:
+        say("  hipcc not installed here: not measured")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
