@@ -8,7 +8,8 @@
 //    dofs masked to 0 on input.
 //      St. Venant-Kirchhoff:    E = (H + H^T + H^T H)/2, S = lam tr(E) I + 2 mu E, P = F S, W = lam/2 tr(E)^2 + mu E:E
 //      compressible neo-Hooke:  J = det F, P = mu (F - F^-T) + lam ln(J) F^-T, W = mu/2 (F:F - 3) - mu ln J + lam/2 (ln J)^2
-//    Both linearise to the handle's K at u = 0.
+//    Both linearise to the handle's K at u = 0.  Neo-Hooke is evaluated from H without forming F (opfs_stress), so that it
+//    keeps its digits at any strain, however small, and under a rigid rotation.
 //  * The pass writes the [npe e + corner][3] contributions the node passes of saa_modal.hip / saa_opstep.hip sum, so
 //    everything downstream of the element pass is what it was.  ENERGY = true also writes energy_elem[e] = sum_q w_q
 //    |detJ_q| W(F_q); the stepper launches ENERGY = false only.
@@ -32,16 +33,37 @@ namespace {
 
 constexpr int kSvk = 1, kNeo = 2;
 
+// y - log1p(y) of y > -1, log1p_y = log1p(y) as the caller has it.  Below |y| = 1/16 the difference cancels (relative error
+// 2 eps/|y|): there the series y^2 (1/2 - y/3 + ... - y^13/15) by Horner's rule, whose first dropped term is 2^-59 of y^2/2.
+__device__ __forceinline__ double opfs_x_minus_log1p(double y, double log1p_y) {
+  if (!(fabs(y) < 0.0625)) return y - log1p_y;
+  double p = -1.0 / 15.0;
+  p = p * y + 1.0 / 14.0;
+  p = p * y - 1.0 / 13.0;
+  p = p * y + 1.0 / 12.0;
+  p = p * y - 1.0 / 11.0;
+  p = p * y + 1.0 / 10.0;
+  p = p * y - 1.0 / 9.0;
+  p = p * y + 1.0 / 8.0;
+  p = p * y - 1.0 / 7.0;
+  p = p * y + 1.0 / 6.0;
+  p = p * y - 1.0 / 5.0;
+  p = p * y + 1.0 / 4.0;
+  p = p * y - 1.0 / 3.0;
+  p = p * y + 0.5;
+  return y * y * p;
+}
+
 // P (first Piola-Kirchhoff) and, with ENERGY, W of the material MAT at displacement gradient h.  false: MAT is neo-Hooke and
 // !(det F > 0); P and W are then not to be used.
 template <int MAT, bool ENERGY>
 __device__ __forceinline__ bool opfs_stress(const double h[3][3], double lam, double mu, double P[3][3], double &W) {
-  double F[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) F[i][k] = h[i][k] + (i == k ? 1.0 : 0.0);
   if (MAT == kSvk) {
+    double F[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) F[i][k] = h[i][k] + (i == k ? 1.0 : 0.0);
     // E = (h + h^T + h^T h)/2, symmetric: the upper triangle is computed, the lower mirrored
     double E[3][3];
 #pragma unroll
@@ -71,33 +93,51 @@ __device__ __forceinline__ bool opfs_stress(const double h[3][3], double lam, do
       for (int k = 0; k < 3; ++k) P[i][k] = F[i][0] * E[0][k] + F[i][1] * E[1][k] + F[i][2] * E[2][k];
     return true;
   }
-  // cofactors of F: F^-T = C / J
-  double C[3][3];
-  C[0][0] = F[1][1] * F[2][2] - F[1][2] * F[2][1];
-  C[0][1] = F[1][2] * F[2][0] - F[1][0] * F[2][2];
-  C[0][2] = F[1][0] * F[2][1] - F[1][1] * F[2][0];
-  C[1][0] = F[0][2] * F[2][1] - F[0][1] * F[2][2];
-  C[1][1] = F[0][0] * F[2][2] - F[0][2] * F[2][0];
-  C[1][2] = F[0][1] * F[2][0] - F[0][0] * F[2][1];
-  C[2][0] = F[0][1] * F[1][2] - F[0][2] * F[1][1];
-  C[2][1] = F[0][2] * F[1][0] - F[0][0] * F[1][2];
-  C[2][2] = F[0][0] * F[1][1] - F[0][1] * F[1][0];
-  const double J = F[0][0] * C[0][0] + F[0][1] * C[0][1] + F[0][2] * C[0][2];
+  // Neo-Hooke from h, never from F = I + h: at |h| << 1 the textbook P = mu F + ((lam ln J - mu)/J) cof F is an O(h)
+  // difference of O(1) numbers (relative error eps/|h|) and mu tr(h) - mu ln J an O(h^2) difference of O(h) ones
+  // (eps/|h|^2).  With A = cof(h) and cof(I + h) = (1 + tr h) I - h^T + A:
+  //   J - 1 = tr h + tr A + det h,  ln J = log1p(J - 1),  F^-T - I = (A - h^T - (tr A + det h) I) / J
+  //   P = mu (h - (F^-T - I)) + lam ln J (I + (F^-T - I))
+  double A[3][3];
+  A[0][0] = h[1][1] * h[2][2] - h[1][2] * h[2][1];
+  A[0][1] = h[1][2] * h[2][0] - h[1][0] * h[2][2];
+  A[0][2] = h[1][0] * h[2][1] - h[1][1] * h[2][0];
+  A[1][0] = h[0][2] * h[2][1] - h[0][1] * h[2][2];
+  A[1][1] = h[0][0] * h[2][2] - h[0][2] * h[2][0];
+  A[1][2] = h[0][1] * h[2][0] - h[0][0] * h[2][1];
+  A[2][0] = h[0][1] * h[1][2] - h[0][2] * h[1][1];
+  A[2][1] = h[0][2] * h[1][0] - h[0][0] * h[1][2];
+  A[2][2] = h[0][0] * h[1][1] - h[0][1] * h[1][0];
+  const double rest = (A[0][0] + A[1][1] + A[2][2]) + (h[0][0] * A[0][0] + h[0][1] * A[0][1] + h[0][2] * A[0][2]);
+  const double x = (h[0][0] + h[1][1] + h[2][2]) + rest;
+  const double J = 1.0 + x;
   if (!(J > 0.0)) return false;
-  const double lnJ = log(J);
-  const double c = (lam * lnJ - mu) / J;
+  const double lnJ = log1p(x);
+  const double rJ = 1.0 / J, llj = lam * lnJ;
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) P[i][k] = mu * F[i][k] + c * C[i][k];
+    for (int k = 0; k < 3; ++k) {
+      const double G = ((A[i][k] - h[k][i]) - (i == k ? rest : 0.0)) * rJ;
+      P[i][k] = mu * (h[i][k] - G) + llj * ((i == k ? 1.0 : 0.0) + G);
+    }
   if (ENERGY) {
-    // F:F - 3 = 2 tr(h) + h:h, without the cancellation
-    double hh = 0.0;
+    // mu/2 (F:F - 3) - mu ln J = mu/2 (tr e - log1p(y)) with e = 2 E = h + h^T + h^T h and y = J^2 - 1 = tr e + tr cof(e) +
+    // det e, so mu/2 ((y - log1p(y)) - (tr cof(e) + det e)): through e, which a rigid rotation leaves alone (h:h does not)
+    double e[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) hh += h[i][k] * h[i][k];
-    W = 0.5 * mu * (2.0 * (h[0][0] + h[1][1] + h[2][2]) + hh) - mu * lnJ + 0.5 * lam * lnJ * lnJ;
+      for (int k = i; k < 3; ++k) {
+        e[i][k] = (h[i][k] + h[k][i]) + (h[0][i] * h[0][k] + h[1][i] * h[1][k] + h[2][i] * h[2][k]);
+        e[k][i] = e[i][k];
+      }
+    const double c00 = e[1][1] * e[2][2] - e[1][2] * e[1][2], c11 = e[0][0] * e[2][2] - e[0][2] * e[0][2],
+                 c22 = e[0][0] * e[1][1] - e[0][1] * e[0][1];
+    const double c01 = e[1][2] * e[0][2] - e[0][1] * e[2][2], c02 = e[0][1] * e[1][2] - e[1][1] * e[0][2];
+    const double low = (c00 + c11 + c22) + (e[0][0] * c00 + e[0][1] * c01 + e[0][2] * c02);
+    const double y = (e[0][0] + e[1][1] + e[2][2]) + low;
+    W = 0.5 * mu * (opfs_x_minus_log1p(y, 2.0 * lnJ) - low) + 0.5 * lam * lnJ * lnJ;
   }
   return true;
 }

@@ -10,7 +10,22 @@ every contraction an explicit loop over the small index.  With ``H = grad_X u`` 
 
 * ``svk``: ``E = (H + H^T + H^T H)/2``, ``S = lam tr(E) I + 2 mu E``, ``P = F S``, ``W = lam/2 tr(E)^2 + mu E:E``;
 * ``neo_hookean``: ``J = det F``, ``P = mu (F - F^-T) + lam ln(J) F^-T``, ``W = mu/2 (F:F - 3) - mu ln J + lam/2 (ln J)^2``
-  with ``F^-T`` the cofactor matrix over ``J`` and ``F:F - 3 = 2 tr(H) + H:H``;
+  with ``F^-T`` the cofactor matrix over ``J`` and ``F:F - 3 = 2 tr(H) + H:H``.  Evaluated as written (``textbook=True``) ``P``
+  is an ``O(H)`` difference of ``O(1)`` numbers and ``tr(H) - ln J`` an ``O(H^2)`` difference of ``O(H)`` ones: the relative
+  error is ``eps/|H|`` and ``eps/|H|^2``.  The class therefore works from ``H`` and never forms ``F``, in the way
+  ``operator_extended.Extended`` avoids its own cancellations: with ``A = cof(H)``,
+
+      J - 1 = tr H + tr A + det H,     ln J = log1p(J - 1),     F^-T - I = (A - H^T - (tr A + det H) I) / J
+      P = mu (H - (F^-T - I)) + lam ln J (I + (F^-T - I))
+      W = mu/2 ((y - log1p(y)) - (tr cof(e) + det e)) + lam/2 (ln J)^2,   e = 2 E = H + H^T + H^T H,   y = J^2 - 1
+
+  (``cof(I + H) = (1 + tr H) I - H^T + cof(H)``; ``mu/2 (F:F - 3) - mu ln J = mu/2 (tr e - log1p(y))`` and ``y = tr e + tr
+  cof(e) + det e``), and ``y - log1p(y)`` is its series ``y^2/2 - y^3/3 + ...`` below ``|y| = 1/4``.  ``W`` goes through ``e``
+  and not through ``H:H`` because a rigid rotation leaves ``e`` alone: with ``H = O(1)`` and a strain ``s``, ``mu/2 H:H + mu
+  (tr H - ln J)`` is an ``O(s^2)`` difference of ``O(1)`` terms (error ``eps/s^2``), while ``e`` carries ``eps |H|/s``, which is
+  what rounding ``u`` once already costs.  The textbook form stays behind the flag only to prove on the CPU that the bar of
+  tests/finite_strain_extended.py can fail.  The class runs in ``np.longdouble`` (default), ``np.float64`` (the "stable
+  restatement") and ``operator_extended.MP`` (``mpmath.mpf`` objects, which check the longdouble run);
 
 ``f_a[i] = sum_q w_q detJ_q sum_k P_q[i][k] dN_a/dX_k(q)`` summed over the elements and set to 0 on Dirichlet dofs, and
 separately ``energy_elem[e] = sum_q w_q |detJ_q| W(F_q)`` with the total ``Pi(u)``.  Under ``neo_hookean`` an element with
@@ -20,7 +35,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from operator_extended import Extended, conv, zeros
+from operator_extended import MP, Extended, conv, log, log1p, scalar, zeros
 
 MATERIALS = ("svk", "neo_hookean")
 
@@ -28,8 +43,8 @@ MATERIALS = ("svk", "neo_hookean")
 class FiniteStrain:
     """``f_int(u)``, ``energy_elem(u)`` and ``Pi(u)`` on ``points (n, 3)``, ``cells (ne, 4 or 10)`` in the arithmetic ``T``."""
 
-    def __init__(self, points, cells, lmd, mu, dirichlet_dofs=(), T=np.longdouble):
-        self.T = T
+    def __init__(self, points, cells, lmd, mu, dirichlet_dofs=(), T=np.longdouble, textbook=False):
+        self.T, self.textbook = T, bool(textbook)
         self.ext = Extended(points, cells, lmd, mu, 1.0, T)
         self.n_nodes, self.n_elems, self.na, self.nq = self.ext.n_nodes, self.ext.n_elems, self.ext.na, self.ext.nq
         self.cells = self.ext.cells
@@ -92,11 +107,47 @@ class FiniteStrain:
             return P, W, np.zeros(self.n_elems, dtype=bool)
         if material != "neo_hookean":
             raise ValueError(f"unknown material {material!r}")
-        C, J = self._cofactors(F)
-        inverted = ~(np.asarray(J > 0).all(axis=1))
+        if self.textbook:
+            return self._neo_hookean_textbook(H, F, P, W)
+        A, det_h = self._cofactors(H)                                  # cof(H); no entry of F from here on
+        tr_h = H[..., 0, 0] + H[..., 1, 1] + H[..., 2, 2]
+        rest = A[..., 0, 0] + A[..., 1, 1] + A[..., 2, 2] + det_h      # J - 1 - tr H
+        x = tr_h + rest
+        J = 1 + x
+        ok = np.asarray(J > 0, dtype=bool)                             # NaN: not ok
+        inverted = ~ok.all(axis=1)
         with np.errstate(invalid="ignore", divide="ignore"):
-            Jsafe = np.where(J > 0, J, 1)
-            lnJ = np.log(Jsafe)
+            xs, Js = np.where(ok, x, conv(0.0, self.T)), np.where(ok, J, conv(1.0, self.T))
+            lnJ = log1p(xs, self.T)
+            for i in range(3):
+                for k in range(3):
+                    D = A[..., i, k] - H[..., k, i]                    # (cof F - J I)[i, k]
+                    if i == k:
+                        D = D - rest
+                    G = D / Js                                         # (F^-T - I)[i, k]
+                    P[..., i, k] = self.mu * (H[..., i, k] - G) + self.lmd * lnJ * ((1 if i == k else 0) + G)
+            # tr E - ln J from e = 2 E = H + H^T + H^T H, which a rotation leaves alone: det(I + e) = J^2 = 1 + y
+            e = zeros(H.shape, self.T)
+            for i in range(3):
+                for k in range(3):
+                    e[..., i, k] = H[..., i, k] + H[..., k, i]
+                    for l in range(3):
+                        e[..., i, k] = e[..., i, k] + H[..., l, i] * H[..., l, k]
+            c2, det_e = self._cofactors(e)
+            low = c2[..., 0, 0] + c2[..., 1, 1] + c2[..., 2, 2] + det_e  # J^2 - 1 - tr e
+            y = e[..., 0, 0] + e[..., 1, 1] + e[..., 2, 2] + low
+            ys = np.where(ok & np.asarray(y > -1, dtype=bool), y, conv(0.0, self.T))
+            W = self.mu / 2 * (x_minus_log1p(ys, self.T, 2 * lnJ) - low) + self.lmd / 2 * lnJ * lnJ
+        return P, W, inverted
+
+    def _neo_hookean_textbook(self, H, F, P, W):
+        """The formulas as the definitions give them, from ``F``: what csrc/saa_opfs.hip evaluated at first."""
+        C, J = self._cofactors(F)
+        ok = np.asarray(J > 0, dtype=bool)
+        inverted = ~ok.all(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            Jsafe = np.where(ok, J, conv(1.0, self.T))
+            lnJ = log(Jsafe, self.T)
             hh = zeros(H.shape[:2], self.T)
             for i in range(3):
                 for k in range(3):
@@ -110,7 +161,7 @@ class FiniteStrain:
         """``(f (3 n,), energy_elem (ne,), inverted (ne,) bool)``; inverted elements contribute 0 to both."""
         ext = self.ext
         P, W, inverted = self.stress(self.gradient(u), material)
-        keep = conv((~inverted).astype(np.float64), self.T)
+        zero = conv(0.0, self.T)                                       # (selected, not multiplied: a dropped element may hold NaN)
         f = zeros((self.n_elems, self.na, 3), self.T)
         energy = zeros(self.n_elems, self.T)
         for q in range(self.nq):
@@ -118,9 +169,9 @@ class FiniteStrain:
             for i in range(3):
                 for k in range(3):
                     f[..., i] = f[..., i] + (ext.wdk[:, q] * P[:, q, i, k])[:, None] * ext.grad[:, q, :, k]
-        f = f * keep[:, None, None]
+        f = np.where(inverted[:, None, None], zero, f)
         out = ext._scatter(f[None])[0]
-        return np.where(self.free, out, conv(0.0, self.T)), energy * keep, inverted
+        return np.where(self.free, out, zero), np.where(inverted, zero, energy), inverted
 
     def force(self, u, material):
         return self.evaluate(u, material)[0]
@@ -137,6 +188,26 @@ class FiniteStrain:
         """``K u`` of the handle's linear operator (masked on both sides)."""
         u = np.where(self.free, conv(u, self.T), conv(0.0, self.T))
         return np.where(self.free, self.ext.apply_k(u[None])[0], conv(0.0, self.T))
+
+
+def x_minus_log1p(x, T, log1p_x=None):
+    """``x - log1p(x)`` of ``x > -1`` without the cancellation: below ``|x| = 1/4`` the series ``sum_{k >= 2} (-x)^k / k`` by
+    Horner's rule, cut where the first dropped term is below the precision of ``T`` times ``x^2/2``; the difference itself
+    elsewhere (its relative error there is at most ``8 eps``), with ``log1p_x`` for ``log1p(x)`` where the caller has a better
+    one than ``x`` gives (``x = J^2 - 1`` close to -1 knows ``J^2`` only to ``eps / J^2``)."""
+    if T is MP:
+        import mpmath
+
+        bits = mpmath.mp.prec
+    else:
+        bits = 53 if np.dtype(T) == np.float64 else 64
+    n = bits // 2 + 4                                                  # 2 (1/4)^(n - 1) / (n + 1) < 2^-bits
+    p = zeros(x.shape, T) + scalar((-1.0) ** n, T) / n
+    for k in range(n - 1, 1, -1):
+        p = p * x + scalar((-1.0) ** k, T) / k
+    with np.errstate(invalid="ignore", divide="ignore"):
+        direct = x - (log1p(x, T) if log1p_x is None else log1p_x)
+    return np.where(np.asarray(np.abs(x) < 0.25, dtype=bool), x * x * p, direct)
 
 
 def run(force, mass, load, live, dt, alpha, ramp, nsteps, d0=None, dn=None, tn=0.0, record=None):

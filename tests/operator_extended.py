@@ -94,6 +94,22 @@ def sqrt(a, T):
     return np.frompyfunc(mpmath.sqrt, 1, 1)(a)
 
 
+def log(a, T):
+    if T is not MP:
+        return np.log(a)
+    import mpmath
+
+    return np.frompyfunc(mpmath.log, 1, 1)(a)
+
+
+def log1p(a, T):
+    if T is not MP:
+        return np.log1p(a)
+    import mpmath
+
+    return np.frompyfunc(mpmath.log1p, 1, 1)(a)
+
+
 def to_longdouble(a):
     """An array of any of the arithmetics as longdouble (mpf: rounded through a float64 pair, 106 bits)."""
     a = np.asarray(a)
@@ -664,13 +680,20 @@ for _tag in ("zz", "other", "press"):
 # A few elements of a case on their own (the mpmath check), and the element bound
 # ----------------------------------------------------------------------------------------------------------------------
 
+def sub_mesh(points, cells, n_elems=4):
+    """``(nodes, points, cells)`` of the first ``n_elems`` elements as a mesh of their own: the nodes they use (sorted, in
+    the numbering of the whole mesh), those nodes' coordinates and the cells renumbered to them."""
+    cells = np.asarray(cells)[:n_elems]
+    nodes, inv = np.unique(cells, return_inverse=True)
+    return nodes, np.asarray(points)[nodes], inv.reshape(cells.shape)
+
+
 def sub_case(case, n_elems=4, n_columns=2):
     """The first ``n_elems`` elements of a case as a mesh of their own (nodes renumbered), with ``n_columns`` columns."""
-    cells = case["cells"][:n_elems]
-    nodes, inv = np.unique(cells, return_inverse=True)
+    nodes, points, cells = sub_mesh(case["points"], case["cells"], n_elems)
     dof = (3 * nodes[:, None] + np.arange(3)[None, :]).ravel()
     out = dict(case)
-    out["points"], out["cells"] = case["points"][nodes], inv.reshape(cells.shape)
+    out["points"], out["cells"] = points, cells
     for k in ("X", "X_other"):
         out[k] = case[k][:n_columns][:, dof]
     for k in ("sig", "sig_other", "psig"):

@@ -64,8 +64,8 @@ def meshes():
 @pytest.mark.parametrize("k,name", list(enumerate(fd.MESHES)))
 def test_internal_force_against_the_double(meshes, k, name, material):
     """A seeded smooth-plus-random field scaled to ``max|H| = 0.3`` (``min det F`` 0.55 .. 0.71).  Measured on the MI355X, of
-    the largest entry: ``f`` 1.7e-16 .. 1.8e-15 (svk), 4.2e-16 .. 1.8e-15 (neo_hookean), the same with and without the energy;
-    ``energy_elem`` 2.6e-16 .. 1.8e-15 (svk), 8.1e-16 .. 4.9e-15 (neo_hookean)."""
+    the largest entry: ``f`` 1.7e-16 .. 1.8e-15 (svk), 2.3e-16 .. 1.6e-15 (neo_hookean), the same with and without the energy;
+    ``energy_elem`` 2.6e-16 .. 1.8e-15 (svk), 6.2e-16 .. 9.2e-16 (neo_hookean)."""
     import torch
 
     m = meshes[name]
@@ -170,8 +170,8 @@ def dynamic(meshes):
 @pytest.mark.parametrize("order", (1, 2))
 def test_stepper_against_the_double(dynamic, order, material):
     """200 steps, ``ramp=False``, ``alpha = 0.5``, ``dt = 0.9 * 2/omega_max``, from ``d0 = dn = u0``, the circular bend with
-    the tip rotated by 0.3 rad.  Measured on the MI355X, rel-L2 of ``d0``: order 1 9.4e-15 (svk), 2.6e-14 (neo_hookean);
-    order 2 7.4e-15, 2.5e-14.  The linear stepper from the same state ends 1.0e-1 (order 1) and 5.9e-2 (order 2) away."""
+    the tip rotated by 0.3 rad.  Measured on the MI355X, rel-L2 of ``d0``: order 1 9.4e-15 (svk), 4.0e-14 (neo_hookean);
+    order 2 7.4e-15, 7.4e-15.  The linear stepper from the same state ends 1.0e-1 (order 1) and 5.9e-2 (order 2) away."""
     c = dynamic[order]
     d0, dn, inverted = c.run(material)
     force = (lambda x: c.f64.force(x, material))
@@ -291,7 +291,7 @@ def test_partition_order_one():
 def test_inverted_elements_contribute_nothing_and_are_counted(meshes):
     """Vertex 5 of the 36-tet beam (and the mid-edge nodes of its edges by half as much) pushed through the opposite faces
     of its four elements, on a gentle background field so that the other elements carry a force.  Measured on the MI355X:
-    4 inverted, ``f`` 3.4e-15 and ``energy_elem`` 1.9e-13 of the largest entry against the double with them dropped."""
+    4 inverted, ``f`` 8.2e-16 and ``energy_elem`` 1.1e-15 of the largest entry against the double with them dropped."""
     import torch
 
     from synchronization_avoiding_algorithms_amd.dynamics import OperatorStepper
