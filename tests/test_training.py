@@ -199,27 +199,40 @@ def test_batched_validation_equals_the_batch_loop():
 
 @pytest.mark.gpu
 def test_train_stats_kernel_against_the_formulas():
-    """``saa_train_stats``: mse, 1 - mse/var(y), 1 - mse/mean(y^2) added to running sums (DNN_tools.py:144-155)."""
+    """``saa_train_stats``: mse, 1 - mse/var(y), 1 - mse/mean(y^2) added to running sums (DNN_tools.py:144-155).  A single
+    target value (variance 0, R^2 = -inf) has sums of its own: added to the others it would turn their R^2 into -inf too,
+    whatever the kernel's variance is.  R^2 is held to ``1e-12 (1 + msq/var mse/var)`` (tests/training_double.py)."""
     import torch
 
+    import training_double as td
     from synchronization_avoiding_algorithms_amd import _lib
 
     torch.manual_seed(0)
     lib = _lib.load()
-    sums = torch.zeros(3, dtype=torch.float64, device="cuda")
     scratch = torch.zeros(3, dtype=torch.float64, device="cuda")
-    want = torch.zeros(3, dtype=torch.float64)
-    for n in (1, 63, 200 * 3042, 1 << 20):
+
+    def add(sums, n):
         out, y = torch.rand(n, device="cuda") - 1.0, torch.rand(n, device="cuda") - 1.0 if n > 1 else torch.full((1,), -0.3, device="cuda")
         _lib.check(lib.saa_train_stats(0, n, out.data_ptr(), y.data_ptr(), scratch.data_ptr(), sums.data_ptr(),
                                        torch.cuda.current_stream().cuda_stream))
         o, t = out.double().cpu(), y.double().cpu()
         mse = (o - t).square().mean()
         r2 = 1 - mse / (t - t.mean()).square().mean() if n > 1 else torch.tensor(float("-inf"), dtype=torch.float64)
-        want += torch.stack([mse, r2, 1 - mse / t.square().mean()])
+        ref = td.stats(out, y)
+        return torch.stack([mse, r2, 1 - mse / t.square().mean()]), (td.r2_bar(ref) * abs(float(ref["r2"])) if n > 1 else 0.0)
+
+    sums, want, bar = torch.zeros(3, dtype=torch.float64, device="cuda"), torch.zeros(3, dtype=torch.float64), 0.0
+    for n in (63, 200 * 3042, 1 << 20):
+        w, b = add(sums, n)
+        want, bar = want + w, bar + b
     got = sums.cpu()
     assert torch.allclose(got[[0, 2]], want[[0, 2]], rtol=1e-12) and float(scratch.abs().sum()) == 0.0
-    assert got[1] == want[1] or (torch.isinf(got[1]) and torch.isinf(want[1]))  # a single target value: variance 0
+    assert abs(float(got[1] - want[1])) <= bar, (got[1], want[1], bar)
+    single = torch.zeros(3, dtype=torch.float64, device="cuda")
+    want, _ = add(single, 1)
+    got = single.cpu()
+    assert torch.allclose(got[[0, 2]], want[[0, 2]], rtol=1e-12) and float(scratch.abs().sum()) == 0.0
+    assert got[1] == want[1] and torch.isinf(got[1]) and got[1] < 0  # a single target value: variance 0
 
 
 @pytest.mark.gpu
