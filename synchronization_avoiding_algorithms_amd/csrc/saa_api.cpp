@@ -1909,73 +1909,59 @@ struct saa_operator {
   saa::ModalOp *impl = nullptr;
 };
 
-int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
-                        const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
-                        saa_operator **out) {
-  if (!out) return fail(SAA_E_ARG, "saa_operator_create: null output");
+namespace {
+
+// saa_operator_create (npe = 4, order 1) and saa_operator_create_p2 (npe = 10, order 2): they differ in the nodes per cell
+// and in how many elements still index with 32 bits.
+int operator_create(const std::string &name, int npe, bool too_many_elems, const char *capacity, int order, int32_t device,
+                    int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *cells, const int32_t *dirichlet_dofs,
+                    int32_t n_dirichlet, double lambda_, double mu, double rho, saa_operator **out) {
+  if (!out) return fail(SAA_E_ARG, name + ": null output");
   *out = nullptr;
-  if (n_nodes <= 0 || n_elems < 0 || n_dirichlet < 0 || !xyz || (n_elems > 0 && !tets) || (n_dirichlet > 0 && !dirichlet_dofs))
-    return fail(SAA_E_ARG, "saa_operator_create: bad argument");
-  if (4 * static_cast<int64_t>(n_elems) > INT32_MAX || 3 * static_cast<int64_t>(n_nodes) > INT32_MAX)
-    return fail(SAA_E_CAPACITY, "saa_operator_create: more than 2^29 elements or 2^31 dofs");
+  if (n_nodes <= 0 || n_elems < 0 || n_dirichlet < 0 || !xyz || (n_elems > 0 && !cells) || (n_dirichlet > 0 && !dirichlet_dofs))
+    return fail(SAA_E_ARG, name + ": bad argument");
+  if (too_many_elems || 3 * static_cast<int64_t>(n_nodes) > INT32_MAX) return fail(SAA_E_CAPACITY, name + ": " + capacity);
   if (!(std::isfinite(lambda_) && std::isfinite(mu) && std::isfinite(rho) && rho > 0.0))
-    return fail(SAA_E_ARG, "saa_operator_create: material parameters must be finite and rho > 0");
-  for (int64_t i = 0; i < 4 * static_cast<int64_t>(n_elems); ++i)
-    if (tets[i] < 0 || tets[i] >= n_nodes) return fail(SAA_E_ARG, "saa_operator_create: node id out of range");
+    return fail(SAA_E_ARG, name + ": material parameters must be finite and rho > 0");
+  for (int64_t i = 0; i < npe * static_cast<int64_t>(n_elems); ++i)
+    if (cells[i] < 0 || cells[i] >= n_nodes) return fail(SAA_E_ARG, name + ": node id out of range");
   for (int32_t i = 0; i < n_dirichlet; ++i)
-    if (dirichlet_dofs[i] < 0 || dirichlet_dofs[i] >= 3 * n_nodes) return fail(SAA_E_ARG, "saa_operator_create: Dirichlet dof out of range");
+    if (dirichlet_dofs[i] < 0 || dirichlet_dofs[i] >= 3 * n_nodes) return fail(SAA_E_ARG, name + ": Dirichlet dof out of range");
   saa_operator *op = new (std::nothrow) saa_operator;
-  if (!op) return fail(SAA_E_HIP, "saa_operator_create: out of host memory");
+  if (!op) return fail(SAA_E_HIP, name + ": out of host memory");
   std::string err;
   hipError_t e;
   try {
-    e = saa::modal_create(device, n_nodes, n_elems, xyz, tets, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, &op->impl, err);
+    e = saa::modal_create(device, n_nodes, n_elems, xyz, cells, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, &op->impl, err, order);
   } catch (const std::bad_alloc &) {
     delete op;
-    return fail(SAA_E_HIP, "saa_operator_create: out of host memory");
+    return fail(SAA_E_HIP, name + ": out of host memory");
   }
   if (e != hipSuccess) {
     delete op;
     (void)hipGetLastError();
-    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_create: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+    return err.empty() ? fail(SAA_E_HIP, name + ": " + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
   }
   *out = op;
   return SAA_OK;
 }
 
+}  // namespace
+
+int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
+                        const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
+                        saa_operator **out) {
+  return operator_create("saa_operator_create", 4, 4 * static_cast<int64_t>(n_elems) > INT32_MAX,
+                         "more than 2^29 elements or 2^31 dofs", 1, device, n_nodes, n_elems, xyz, tets, dirichlet_dofs,
+                         n_dirichlet, lambda_, mu, rho, out);
+}
+
 int saa_operator_create_p2(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *cells10,
                            const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
                            saa_operator **out) {
-  if (!out) return fail(SAA_E_ARG, "saa_operator_create_p2: null output");
-  *out = nullptr;
-  if (n_nodes <= 0 || n_elems < 0 || n_dirichlet < 0 || !xyz || (n_elems > 0 && !cells10) || (n_dirichlet > 0 && !dirichlet_dofs))
-    return fail(SAA_E_ARG, "saa_operator_create_p2: bad argument");
-  if (n_elems > saa::kP2MaxElems || 3 * static_cast<int64_t>(n_nodes) > INT32_MAX)
-    return fail(SAA_E_CAPACITY, "saa_operator_create_p2: more than 214748364 elements (10 * n_elems must fit 32 bits) or 2^31 dofs");
-  if (!(std::isfinite(lambda_) && std::isfinite(mu) && std::isfinite(rho) && rho > 0.0))
-    return fail(SAA_E_ARG, "saa_operator_create_p2: material parameters must be finite and rho > 0");
-  for (int64_t i = 0; i < 10 * static_cast<int64_t>(n_elems); ++i)
-    if (cells10[i] < 0 || cells10[i] >= n_nodes) return fail(SAA_E_ARG, "saa_operator_create_p2: node id out of range");
-  for (int32_t i = 0; i < n_dirichlet; ++i)
-    if (dirichlet_dofs[i] < 0 || dirichlet_dofs[i] >= 3 * n_nodes)
-      return fail(SAA_E_ARG, "saa_operator_create_p2: Dirichlet dof out of range");
-  saa_operator *op = new (std::nothrow) saa_operator;
-  if (!op) return fail(SAA_E_HIP, "saa_operator_create_p2: out of host memory");
-  std::string err;
-  hipError_t e;
-  try {
-    e = saa::modal_create(device, n_nodes, n_elems, xyz, cells10, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, &op->impl, err, 2);
-  } catch (const std::bad_alloc &) {
-    delete op;
-    return fail(SAA_E_HIP, "saa_operator_create_p2: out of host memory");
-  }
-  if (e != hipSuccess) {
-    delete op;
-    (void)hipGetLastError();
-    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_create_p2: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
-  }
-  *out = op;
-  return SAA_OK;
+  return operator_create("saa_operator_create_p2", 10, n_elems > saa::kP2MaxElems,
+                         "more than 214748364 elements (10 * n_elems must fit 32 bits) or 2^31 dofs", 2, device, n_nodes, n_elems,
+                         xyz, cells10, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, out);
 }
 
 int saa_operator_order(const saa_operator *op) {
@@ -2034,172 +2020,168 @@ int saa_operator_element_bound(saa_operator *op, double *omega_e_dev, double *om
   return SAA_OK;
 }
 
+// ---- stress recovery of both element orders (saa_stress.hip, saa_stress_p2.hip) --------------------------------------
+namespace {
+
+// The checks that the seven entry points share.  Each returns SAA_OK or has set the error.  The linear family checks the
+// handle and its order before the column count; the _p2 family checks the column count first (p2_stress_front).
+int stress_handle(const saa_operator *op, const std::string &name, int order) {
+  if (!op || !op->impl) return fail(SAA_E_ARG, name + ": null handle");
+  if (saa::modal_order(op->impl) == order) return SAA_OK;
+  return fail(SAA_E_ARG, name + (order == 1 ? ": a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)"
+                                            : ": a quadratic-element formula, not available on an order-1 handle "
+                                              "(saa_operator_create)"));
+}
+
+int stress_columns(int32_t m, const std::string &name) {
+  if (m >= 1 && m <= saa::kModalMaxColumns) return SAA_OK;
+  return fail(SAA_E_ARG, name + ": m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+}
+
+int stress_ld(const std::string &name, const char *what, int64_t ld, const char *bound, int64_t need) {
+  if (ld >= need) return SAA_OK;
+  return fail(SAA_E_ARG, name + ": " + what + " = " + std::to_string(ld) + " below " + bound + " = " + std::to_string(need));
+}
+
+// exactly one of the two second fields of an error call
+int stress_one_of(const std::string &name, const double *sigma_node_dev, const double *sigma_other_dev) {
+  if (!sigma_node_dev != !sigma_other_dev) return SAA_OK;
+  return fail(SAA_E_ARG, name + ": " + (sigma_node_dev ? "both" : "neither") +
+                             " of sigma_node_dev and sigma_other_dev given, exactly one is needed");
+}
+
+int stress_compliance(const saa_operator *op, const std::string &name) {
+  if (saa::stress_has_compliance(op->impl)) return SAA_OK;
+  return fail(SAA_E_ARG, name + ": the compliance D^-1 needs mu > 0 and 3 lambda + 2 mu > 0");
+}
+
+int stress_done(hipError_t e, const std::string &name) {
+  return e == hipSuccess ? SAA_OK : fail(SAA_E_HIP, name + ": " + hipGetErrorString(e));
+}
+
+// The front of the three order-2 entry points: a null op, then the column count, then the handle behind op and its order.
+int p2_stress_front(const saa_operator *op, int32_t m, const std::string &name) {
+  if (op)
+    if (const int rc = stress_columns(m, name)) return rc;
+  return stress_handle(op, name, 2);
+}
+
+}  // namespace
+
 int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *sigma_dev, int64_t ld_sigma,
                         double *von_mises_dev, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
                         double *von_mises_max_dev, int32_t *von_mises_argmax_dev) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stress: null handle");
-  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_stress: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
-  if (m < 1 || m > saa::kModalMaxColumns)
-    return fail(SAA_E_ARG, "saa_operator_stress: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
-  if (!x_dev) return fail(SAA_E_ARG, "saa_operator_stress: null displacement x_dev");
+  static const std::string name = "saa_operator_stress";
+  if (const int rc = stress_handle(op, name, 1)) return rc;
+  if (const int rc = stress_columns(m, name)) return rc;
+  if (!x_dev) return fail(SAA_E_ARG, name + ": null displacement x_dev");
   const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
   const int64_t n_elems = saa::modal_n_elems(op->impl);
-  if (ldx < n_dof)
-    return fail(SAA_E_ARG, "saa_operator_stress: ldx = " + std::to_string(ldx) + " below 3 * n_nodes = " + std::to_string(n_dof));
-  if (sigma_dev && ld_sigma < 6 * n_elems)
-    return fail(SAA_E_ARG, "saa_operator_stress: ld_sigma = " + std::to_string(ld_sigma) + " below 6 * n_elems = " +
-                               std::to_string(6 * n_elems));
-  if ((von_mises_dev || energy_dev) && ld_elem < n_elems)
-    return fail(SAA_E_ARG, "saa_operator_stress: ld_elem = " + std::to_string(ld_elem) + " below n_elems = " +
-                               std::to_string(n_elems));
+  if (const int rc = stress_ld(name, "ldx", ldx, "3 * n_nodes", n_dof)) return rc;
+  if (sigma_dev)
+    if (const int rc = stress_ld(name, "ld_sigma", ld_sigma, "6 * n_elems", 6 * n_elems)) return rc;
+  if (von_mises_dev || energy_dev)
+    if (const int rc = stress_ld(name, "ld_elem", ld_elem, "n_elems", n_elems)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, energy_dev, ld_elem,
-                                           energy_total_dev, von_mises_max_dev, von_mises_argmax_dev);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stress: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return stress_done(saa::stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, energy_dev, ld_elem,
+                                         energy_total_dev, von_mises_max_dev, von_mises_argmax_dev),
+                     name);
 }
 
 int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const double *elem_dev, int64_t ld_elem, double *node_dev,
                                int64_t ld_node) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_nodal_average: null handle");
-  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_nodal_average: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
-  if (m < 1 || m > saa::kModalMaxColumns)
-    return fail(SAA_E_ARG, "saa_operator_nodal_average: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+  static const std::string name = "saa_operator_nodal_average";
+  if (const int rc = stress_handle(op, name, 1)) return rc;
+  if (const int rc = stress_columns(m, name)) return rc;
   if (k < 1 || k > saa::kStressMaxComponents)
-    return fail(SAA_E_ARG, "saa_operator_nodal_average: k = " + std::to_string(k) + " components, 1 <= k <= 8");
-  if (!elem_dev || !node_dev) return fail(SAA_E_ARG, "saa_operator_nodal_average: null elem_dev or node_dev");
+    return fail(SAA_E_ARG, name + ": k = " + std::to_string(k) + " components, 1 <= k <= 8");
+  if (!elem_dev || !node_dev) return fail(SAA_E_ARG, name + ": null elem_dev or node_dev");
   const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
-  if (ld_elem < k * n_elems)
-    return fail(SAA_E_ARG, "saa_operator_nodal_average: ld_elem = " + std::to_string(ld_elem) + " below k * n_elems = " +
-                               std::to_string(k * n_elems));
-  if (ld_node < k * n_nodes)
-    return fail(SAA_E_ARG, "saa_operator_nodal_average: ld_node = " + std::to_string(ld_node) + " below k * n_nodes = " +
-                               std::to_string(k * n_nodes));
+  if (const int rc = stress_ld(name, "ld_elem", ld_elem, "k * n_elems", k * n_elems)) return rc;
+  if (const int rc = stress_ld(name, "ld_node", ld_node, "k * n_nodes", k * n_nodes)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::stress_nodal_average(op->impl, m, k, elem_dev, ld_elem, node_dev, ld_node);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_nodal_average: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return stress_done(saa::stress_nodal_average(op->impl, m, k, elem_dev, ld_elem, node_dev, ld_node), name);
 }
 
 int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_elem_dev, int64_t ld_sigma,
                               const double *sigma_node_dev, int64_t ld_node, const double *sigma_other_dev, int64_t ld_other,
                               double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
                               int32_t *eta2_argmax_dev) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stress_error: null handle");
-  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_stress_error: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
-  if (m < 1 || m > saa::kModalMaxColumns)
-    return fail(SAA_E_ARG, "saa_operator_stress_error: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
-  if (!sigma_elem_dev) return fail(SAA_E_ARG, "saa_operator_stress_error: null element stress sigma_elem_dev");
-  if (!sigma_node_dev == !sigma_other_dev)
-    return fail(SAA_E_ARG, std::string("saa_operator_stress_error: ") + (sigma_node_dev ? "both" : "neither") +
-                               " of sigma_node_dev and sigma_other_dev given, exactly one is needed");
+  static const std::string name = "saa_operator_stress_error";
+  if (const int rc = stress_handle(op, name, 1)) return rc;
+  if (const int rc = stress_columns(m, name)) return rc;
+  if (!sigma_elem_dev) return fail(SAA_E_ARG, name + ": null element stress sigma_elem_dev");
+  if (const int rc = stress_one_of(name, sigma_node_dev, sigma_other_dev)) return rc;
   const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
-  if (ld_sigma < 6 * n_elems)
-    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_sigma = " + std::to_string(ld_sigma) + " below 6 * n_elems = " +
-                               std::to_string(6 * n_elems));
-  if (sigma_node_dev && ld_node < 6 * n_nodes)
-    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_node = " + std::to_string(ld_node) + " below 6 * n_nodes = " +
-                               std::to_string(6 * n_nodes));
-  if (sigma_other_dev && ld_other < 6 * n_elems)
-    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_other = " + std::to_string(ld_other) + " below 6 * n_elems = " +
-                               std::to_string(6 * n_elems));
-  if (eta2_dev && ld_eta < n_elems)
-    return fail(SAA_E_ARG, "saa_operator_stress_error: ld_eta = " + std::to_string(ld_eta) + " below n_elems = " +
-                               std::to_string(n_elems));
-  if (!saa::stress_has_compliance(op->impl))
-    return fail(SAA_E_ARG, "saa_operator_stress_error: the compliance D^-1 needs mu > 0 and 3 lambda + 2 mu > 0");
+  if (const int rc = stress_ld(name, "ld_sigma", ld_sigma, "6 * n_elems", 6 * n_elems)) return rc;
+  if (sigma_node_dev)
+    if (const int rc = stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
+  if (sigma_other_dev)
+    if (const int rc = stress_ld(name, "ld_other", ld_other, "6 * n_elems", 6 * n_elems)) return rc;
+  if (eta2_dev)
+    if (const int rc = stress_ld(name, "ld_eta", ld_eta, "n_elems", n_elems)) return rc;
+  if (const int rc = stress_compliance(op, name)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::stress_error(op->impl, m, sigma_elem_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev,
-                                         ld_other, eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stress_error: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return stress_done(saa::stress_error(op->impl, m, sigma_elem_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
+                                       eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev),
+                     name);
 }
-
-// ---- stress recovery of the quadratic element (saa_stress_p2.hip) ---------------------------------------------------
-namespace {
-
-// What the three order-2 entry points check first, before the handle is read: the handle and the column count.
-int p2_stress_front(const saa_operator *op, int32_t m, const char *name) {
-  if (!op) return fail(SAA_E_ARG, std::string(name) + ": null handle");
-  if (m < 1 || m > saa::kModalMaxColumns)
-    return fail(SAA_E_ARG, std::string(name) + ": m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
-  if (!op->impl) return fail(SAA_E_ARG, std::string(name) + ": null handle");
-  if (saa::modal_order(op->impl) != 2)
-    return fail(SAA_E_ARG, std::string(name) + ": a quadratic-element formula, not available on an order-1 handle "
-                                               "(saa_operator_create)");
-  return SAA_OK;
-}
-
-int p2_stress_ld(const char *name, const char *what, int64_t ld, const char *bound, int64_t need) {
-  if (ld >= need) return SAA_OK;
-  return fail(SAA_E_ARG, std::string(name) + ": " + what + " = " + std::to_string(ld) + " below " + bound + " = " +
-                             std::to_string(need));
-}
-
-}  // namespace
 
 int saa_operator_stress_p2(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *sigma_dev, int64_t ld_sigma,
                            double *von_mises_dev, int64_t ld_vm, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
                            double *von_mises_max_dev, int32_t *von_mises_argmax_dev) {
-  static const char *const name = "saa_operator_stress_p2";
+  static const std::string name = "saa_operator_stress_p2";
   if (const int rc = p2_stress_front(op, m, name)) return rc;
-  if (!x_dev) return fail(SAA_E_ARG, std::string(name) + ": null displacement x_dev");
+  if (!x_dev) return fail(SAA_E_ARG, name + ": null displacement x_dev");
   const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
   const int64_t n_elems = saa::modal_n_elems(op->impl);
-  if (const int rc = p2_stress_ld(name, "ldx", ldx, "3 * n_nodes", n_dof)) return rc;
+  if (const int rc = stress_ld(name, "ldx", ldx, "3 * n_nodes", n_dof)) return rc;
   if (sigma_dev)
-    if (const int rc = p2_stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
+    if (const int rc = stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
   if (von_mises_dev)
-    if (const int rc = p2_stress_ld(name, "ld_vm", ld_vm, "4 * n_elems", 4 * n_elems)) return rc;
+    if (const int rc = stress_ld(name, "ld_vm", ld_vm, "4 * n_elems", 4 * n_elems)) return rc;
   if (energy_dev)
-    if (const int rc = p2_stress_ld(name, "ld_elem", ld_elem, "n_elems", n_elems)) return rc;
+    if (const int rc = stress_ld(name, "ld_elem", ld_elem, "n_elems", n_elems)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::p2_stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, ld_vm, energy_dev,
-                                              ld_elem, energy_total_dev, von_mises_max_dev, von_mises_argmax_dev);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return SAA_OK;
+  return stress_done(saa::p2_stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, ld_vm, energy_dev, ld_elem,
+                                            energy_total_dev, von_mises_max_dev, von_mises_argmax_dev),
+                     name);
 }
 
 int saa_operator_nodal_stress_p2(saa_operator *op, int32_t m, const double *sigma_dev, int64_t ld_sigma, double *sigma_node_dev,
                                  int64_t ld_node) {
-  static const char *const name = "saa_operator_nodal_stress_p2";
+  static const std::string name = "saa_operator_nodal_stress_p2";
   if (const int rc = p2_stress_front(op, m, name)) return rc;
-  if (!sigma_dev) return fail(SAA_E_ARG, std::string(name) + ": null Gauss-point stress sigma_dev");
+  if (!sigma_dev) return fail(SAA_E_ARG, name + ": null Gauss-point stress sigma_dev");
   const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
-  if (const int rc = p2_stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
+  if (const int rc = stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
   if (!sigma_node_dev) return SAA_OK;  // (the only output: nothing is launched)
-  if (const int rc = p2_stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
+  if (const int rc = stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::p2_stress_nodal(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return SAA_OK;
+  return stress_done(saa::p2_stress_nodal(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node), name);
 }
 
 int saa_operator_stress_error_p2(saa_operator *op, int32_t m, const double *sigma_dev, int64_t ld_sigma,
                                  const double *sigma_node_dev, int64_t ld_node, const double *sigma_other_dev, int64_t ld_other,
                                  double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
                                  int32_t *eta2_argmax_dev) {
-  static const char *const name = "saa_operator_stress_error_p2";
+  static const std::string name = "saa_operator_stress_error_p2";
   if (const int rc = p2_stress_front(op, m, name)) return rc;
-  if (!sigma_dev) return fail(SAA_E_ARG, std::string(name) + ": null Gauss-point stress sigma_dev");
-  if (!sigma_node_dev == !sigma_other_dev)
-    return fail(SAA_E_ARG, std::string(name) + ": " + (sigma_node_dev ? "both" : "neither") +
-                               " of sigma_node_dev and sigma_other_dev given, exactly one is needed");
+  if (!sigma_dev) return fail(SAA_E_ARG, name + ": null Gauss-point stress sigma_dev");
+  if (const int rc = stress_one_of(name, sigma_node_dev, sigma_other_dev)) return rc;
   const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
-  if (const int rc = p2_stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
+  if (const int rc = stress_ld(name, "ld_sigma", ld_sigma, "24 * n_elems", 24 * n_elems)) return rc;
   if (sigma_node_dev)
-    if (const int rc = p2_stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
+    if (const int rc = stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
   if (sigma_other_dev)
-    if (const int rc = p2_stress_ld(name, "ld_other", ld_other, "24 * n_elems", 24 * n_elems)) return rc;
+    if (const int rc = stress_ld(name, "ld_other", ld_other, "24 * n_elems", 24 * n_elems)) return rc;
   if (eta2_dev)
-    if (const int rc = p2_stress_ld(name, "ld_eta", ld_eta, "n_elems", n_elems)) return rc;
-  if (!saa::stress_has_compliance(op->impl))
-    return fail(SAA_E_ARG, std::string(name) + ": the compliance D^-1 needs mu > 0 and 3 lambda + 2 mu > 0");
+    if (const int rc = stress_ld(name, "ld_eta", ld_eta, "n_elems", n_elems)) return rc;
+  if (const int rc = stress_compliance(op, name)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::p2_stress_error(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
-                                            eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return SAA_OK;
+  return stress_done(saa::p2_stress_error(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
+                                          eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev),
+                     name);
 }
 
 int saa_operator_destroy(saa_operator *op) {

@@ -19,14 +19,14 @@
 #include <new>
 #include <vector>
 
+#include "saa_hip_host.h"
 #include "saa_modal.h"
 #include "saa_modal_op.h"
+#include "saa_stress_dev.h"
 
 namespace saa {
 
 namespace {
-
-constexpr int kThreads = 256;
 
 struct CholD {
   double l[21];  // lower triangle of L, row by row
@@ -78,18 +78,10 @@ __device__ __forceinline__ double jacobi_max_eig6(double a[6][6]) {
   return m;
 }
 
-// better = larger value, on ties the smaller element; NaN never wins
-__device__ __forceinline__ void max_merge(double &v, int32_t &i, double ov, int32_t oi) {
-  if (ov > v || (ov == v && oi < i)) {
-    v = ov;
-    i = oi;
-  }
-}
-
 // wave, then workgroup (kThreads lanes) reduction of (max, argmax, count); the result is valid in thread 0
 __device__ __forceinline__ void block_reduce(double &v, int32_t &i, int32_t &cnt) {
-  __shared__ double sv[kThreads / 64];
-  __shared__ int32_t si[kThreads / 64], sc[kThreads / 64];
+  __shared__ double sv[kWaves];
+  __shared__ int32_t si[kWaves], sc[kWaves];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const double ov = __shfl_xor(v, off, 64);
@@ -105,7 +97,7 @@ __device__ __forceinline__ void block_reduce(double &v, int32_t &i, int32_t &cnt
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int k = 1; k < kThreads / 64; ++k) {
+    for (int k = 1; k < kWaves; ++k) {
       max_merge(v, i, sv[k], si[k]);
       cnt += sc[k];
     }
@@ -274,19 +266,6 @@ __global__ void __launch_bounds__(kThreads) node_sum_kernel(int32_t n_nodes, int
   }
 }
 
-#define MODAL_TRY(expr)              \
-  do {                               \
-    const hipError_t e_ = (expr);    \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
-namespace {
-template <typename T>
-hipError_t dev_alloc(T **p, size_t count) {
-  return hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T));
-}
-}  // namespace
-
 void modal_destroy(ModalOp *op) {
   if (!op) return;
   (void)hipSetDevice(op->device);
@@ -383,20 +362,20 @@ namespace {
 hipError_t ensure_scratch(double **buf, int32_t *cap, int32_t m, int32_t n_elems) {
   if (*cap >= m) return hipSuccess;
   if (*buf) {
-    MODAL_TRY(hipDeviceSynchronize());  // (a launch still reading the old buffer)
-    MODAL_TRY(hipFree(*buf));
+    SAA_HIP_TRY(hipDeviceSynchronize());  // (a launch still reading the old buffer)
+    SAA_HIP_TRY(hipFree(*buf));
     *buf = nullptr;
     *cap = 0;
   }
-  MODAL_TRY(dev_alloc(buf, 12 * static_cast<size_t>(n_elems) * static_cast<size_t>(m)));
+  SAA_HIP_TRY(dev_alloc(buf, 12 * static_cast<size_t>(n_elems) * static_cast<size_t>(m)));
   *cap = m;
   return hipSuccess;
 }
 }  // namespace
 
 hipError_t modal_apply(ModalOp *op, int32_t m, const double *x, int64_t ldx, double *kx, double *mx, int64_t ldy) {
-  if (kx) MODAL_TRY(ensure_scratch(&op->scratch_k, &op->cap_k, m, op->n_elems));
-  if (mx) MODAL_TRY(ensure_scratch(&op->scratch_m, &op->cap_m, m, op->n_elems));
+  if (kx) SAA_HIP_TRY(ensure_scratch(&op->scratch_k, &op->cap_k, m, op->n_elems));
+  if (mx) SAA_HIP_TRY(ensure_scratch(&op->scratch_m, &op->cap_m, m, op->n_elems));
   const int64_t stride = 12 * static_cast<int64_t>(op->n_elems);
   if (op->n_elems > 0) {
     const dim3 grid(static_cast<unsigned>((op->n_elems + kThreads - 1) / kThreads));
@@ -409,7 +388,7 @@ hipError_t modal_apply(ModalOp *op, int32_t m, const double *x, int64_t ldx, dou
     else
       hipLaunchKernelGGL((elem_apply_kernel<false, true>), grid, dim3(kThreads), 0, op->stream, op->n_elems, m, op->xyz, op->tets,
                          op->free_mask, op->lam, op->mu, op->rho, x, ldx, nullptr, op->scratch_m);
-    MODAL_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
   const dim3 ngrid(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads));
   if (kx)
@@ -444,16 +423,16 @@ hipError_t modal_element_bound(ModalOp *op, double *omega_e, double *omega_max, 
   if (n_parts > 0) {
     hipLaunchKernelGGL(elem_bound_kernel, dim3(static_cast<unsigned>(n_parts)), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz,
                        op->tets, L, 4.0 / op->rho, omega_e, op->part_val, op->part_idx, op->part_cnt);
-    MODAL_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(bound_final_kernel, dim3(1), dim3(kThreads), 0, op->stream, n_parts, op->part_val, op->part_idx, op->part_cnt,
                      op->res_val, op->res_int);
-  MODAL_TRY(hipGetLastError());
+  SAA_HIP_TRY(hipGetLastError());
   double val = 0.0;
   int32_t ints[2] = {0, 0};
-  MODAL_TRY(hipMemcpyAsync(&val, op->res_val, sizeof(double), hipMemcpyDeviceToHost, op->stream));
-  MODAL_TRY(hipMemcpyAsync(ints, op->res_int, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, op->stream));
-  MODAL_TRY(hipStreamSynchronize(op->stream));
+  SAA_HIP_TRY(hipMemcpyAsync(&val, op->res_val, sizeof(double), hipMemcpyDeviceToHost, op->stream));
+  SAA_HIP_TRY(hipMemcpyAsync(ints, op->res_int, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, op->stream));
+  SAA_HIP_TRY(hipStreamSynchronize(op->stream));
   if (omega_max) *omega_max = val;
   if (argmax) *argmax = ints[0] == INT32_MAX ? -1 : ints[0];
   if (n_nonpositive) *n_nonpositive = ints[1];

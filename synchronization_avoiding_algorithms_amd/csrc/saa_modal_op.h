@@ -7,6 +7,11 @@
 
 namespace saa {
 
+// workgroup size of every kernel on the handle, and its waves (the block reductions work on whole waves)
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+static_assert(kThreads % 64 == 0, "the block reductions work on whole waves");
+
 struct ModalOp {
   int device = 0;
   int order = 1;  // 1: 4-node elements, 2: 10-node elements (saa_p2.hip)

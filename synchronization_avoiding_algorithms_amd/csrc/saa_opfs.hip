@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "saa_hip_host.h"
 #include "saa_modal_op.h"
 #include "saa_opstep.h"
 #include "saa_opstep_impl.h"
@@ -282,23 +283,17 @@ __global__ void __launch_bounds__(kThreads, 2) opfs_elem_p2_kernel(int32_t n_ele
   if (ENERGY) energy_elem[e] = en;
 }
 
-#define OPFS_TRY(expr)               \
-  do {                               \
-    const hipError_t e_ = (expr);    \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
 namespace {
 
 // the two counter words: 0 events, no step yet (all ones)
 hipError_t reset_counters(unsigned long long *cnt, hipStream_t stream) {
-  OPFS_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), stream));
+  SAA_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), stream));
   return hipMemsetAsync(cnt + 1, 0xff, sizeof(unsigned long long), stream);
 }
 
 hipError_t alloc_counters(unsigned long long **cnt, hipStream_t stream) {
   if (*cnt) return hipSuccess;
-  OPFS_TRY(hipMalloc(reinterpret_cast<void **>(cnt), 2 * sizeof(unsigned long long)));
+  SAA_HIP_TRY(dev_alloc(cnt, 2));
   return reset_counters(*cnt, stream);
 }
 
@@ -316,8 +311,8 @@ hipError_t launch(ModalOp *op, const double *x, double *contrib, double *energy_
 
 hipError_t read_counters(ModalOp *op, const unsigned long long *cnt, int64_t *count, int64_t *first_step) {
   unsigned long long host[2] = {0, ~0ull};
-  OPFS_TRY(hipMemcpyAsync(host, cnt, sizeof(host), hipMemcpyDeviceToHost, op->stream));
-  OPFS_TRY(hipStreamSynchronize(op->stream));
+  SAA_HIP_TRY(hipMemcpyAsync(host, cnt, sizeof(host), hipMemcpyDeviceToHost, op->stream));
+  SAA_HIP_TRY(hipStreamSynchronize(op->stream));
   if (count) *count = static_cast<int64_t>(host[0]);
   if (first_step) *first_step = host[1] == ~0ull ? -1 : static_cast<int64_t>(host[1]);
   return hipSuccess;
@@ -333,24 +328,24 @@ hipError_t opfs_element_pass(OpStepper *st, const double *x, double *contrib) {
 
 hipError_t operator_internal_force(ModalOp *op, int material, const double *x, double *f, double *energy_elem, int64_t *n_inverted) {
   double *contrib = nullptr;
-  OPFS_TRY(operator_scratch(op, 1, &contrib));
+  SAA_HIP_TRY(operator_scratch(op, 1, &contrib));
   if (material == 0) {
-    OPFS_TRY(op->order == 2 ? p2_elem_pass_k(op, x, contrib) : modal_elem_pass_k(op, x, contrib));
-    OPFS_TRY(modal_node_sum(op, 1, contrib, 0, f, 0));
+    SAA_HIP_TRY(op->order == 2 ? p2_elem_pass_k(op, x, contrib) : modal_elem_pass_k(op, x, contrib));
+    SAA_HIP_TRY(modal_node_sum(op, 1, contrib, 0, f, 0));
     if (n_inverted) *n_inverted = 0;
     return hipSuccess;
   }
-  OPFS_TRY(operator_geometry(op));
-  OPFS_TRY(alloc_counters(&op->fs_count, op->stream));
-  OPFS_TRY(reset_counters(op->fs_count, op->stream));
+  SAA_HIP_TRY(operator_geometry(op));
+  SAA_HIP_TRY(alloc_counters(&op->fs_count, op->stream));
+  SAA_HIP_TRY(reset_counters(op->fs_count, op->stream));
   if (material == kSvk)
-    OPFS_TRY(energy_elem ? (launch<kSvk, true>(op, x, contrib, energy_elem, op->fs_count, 0))
+    SAA_HIP_TRY(energy_elem ? (launch<kSvk, true>(op, x, contrib, energy_elem, op->fs_count, 0))
                          : (launch<kSvk, false>(op, x, contrib, nullptr, op->fs_count, 0)));
   else
-    OPFS_TRY(energy_elem ? (launch<kNeo, true>(op, x, contrib, energy_elem, op->fs_count, 0))
+    SAA_HIP_TRY(energy_elem ? (launch<kNeo, true>(op, x, contrib, energy_elem, op->fs_count, 0))
                          : (launch<kNeo, false>(op, x, contrib, nullptr, op->fs_count, 0)));
-  OPFS_TRY(modal_node_sum(op, 1, contrib, 0, f, 0));
-  if (n_inverted) OPFS_TRY(read_counters(op, op->fs_count, n_inverted, nullptr));
+  SAA_HIP_TRY(modal_node_sum(op, 1, contrib, 0, f, 0));
+  if (n_inverted) SAA_HIP_TRY(read_counters(op, op->fs_count, n_inverted, nullptr));
   return hipSuccess;
 }
 
@@ -359,8 +354,8 @@ int opstep_material(const OpStepper *st) { return st->material; }
 hipError_t opstep_set_material(OpStepper *st, int material) {
   ModalOp *op = st->op;
   if (material != 0) {
-    OPFS_TRY(operator_geometry(op));
-    OPFS_TRY(alloc_counters(&st->inverted, op->stream));
+    SAA_HIP_TRY(operator_geometry(op));
+    SAA_HIP_TRY(alloc_counters(&st->inverted, op->stream));
   }
   st->material = material;
   return opstep_clear_inverted(st);
@@ -370,7 +365,7 @@ hipError_t opstep_clear_inverted(OpStepper *st) { return st->inverted ? reset_co
 
 hipError_t opstep_inverted(OpStepper *st, int64_t *count, int64_t *first_step) {
   if (!st->inverted) {
-    OPFS_TRY(hipStreamSynchronize(st->op->stream));
+    SAA_HIP_TRY(hipStreamSynchronize(st->op->stream));
     if (count) *count = 0;
     if (first_step) *first_step = -1;
     return hipSuccess;

@@ -49,6 +49,7 @@
 #include <new>
 #include <vector>
 
+#include "saa_hip_host.h"
 #include "saa_modal_op.h"
 #include "saa_opstep.h"
 #include "saa_opstep_impl.h"
@@ -251,8 +252,6 @@ __device__ __forceinline__ double opstep_update_dof(bool live, double s, double 
 }
 
 constexpr int kCols = 5;  // of the energy balance: T_{n+1/2}, U_{n+1/2}, U_n, dW (row: W), dD (row: D)
-constexpr int kWaves = kThreads / 64;
-static_assert(kThreads % 64 == 0, "the block reduction works on whole waves");
 
 namespace {
 
@@ -452,18 +451,7 @@ __global__ void __launch_bounds__(kThreads) opstep_halo_kernel(int32_t n_shared,
     d[i] = row[j];
 }
 
-#define OPSTEP_TRY(expr)             \
-  do {                               \
-    const hipError_t e_ = (expr);    \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
 namespace {
-
-template <typename T>
-hipError_t dev_alloc(T **p, size_t count) {
-  return hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T));
-}
 
 // frees the energy buffers and switches the balance off; the caller has made sure that nothing in flight reads them
 void energy_clear(OpStepper *st) {
@@ -492,19 +480,19 @@ hipError_t element_pass(OpStepper *st, const double *x, double *contrib) {
 
 hipError_t operator_geometry(ModalOp *op) {
   if (op->geom || op->order != 2) return hipSuccess;
-  if (!op->bits) OPSTEP_TRY(dev_alloc(&op->bits, static_cast<size_t>(op->n_elems)));
-  OPSTEP_TRY(dev_alloc(&op->geom, 40 * static_cast<size_t>(op->n_elems)));  // (geom set = both exist)
+  if (!op->bits) SAA_HIP_TRY(dev_alloc(&op->bits, static_cast<size_t>(op->n_elems)));
+  SAA_HIP_TRY(dev_alloc(&op->geom, 40 * static_cast<size_t>(op->n_elems)));  // (geom set = both exist)
   if (op->n_elems > 0) {
     hipLaunchKernelGGL(opstep_geometry_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
                        op->free_mask, op->geom, op->bits);
-    OPSTEP_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
   return hipSuccess;
 }
 
 hipError_t operator_lumped_mass(ModalOp *op, double *mass) {
   double *contrib = nullptr;
-  OPSTEP_TRY(operator_scratch(op, 1, &contrib));  // (npe n_elems scalars fit one column of 3 npe n_elems)
+  SAA_HIP_TRY(operator_scratch(op, 1, &contrib));  // (npe n_elems scalars fit one column of 3 npe n_elems)
   if (op->n_elems > 0) {
     if (op->order == 2)
       hipLaunchKernelGGL(opstep_hrz_mass_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
@@ -512,7 +500,7 @@ hipError_t operator_lumped_mass(ModalOp *op, double *mass) {
     else
       hipLaunchKernelGGL(opstep_p1_mass_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
                          op->rho, contrib);
-    OPSTEP_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(opstep_mass_node_kernel, opstep_grid(op->n_nodes), dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs,
                      contrib, mass);
@@ -580,9 +568,9 @@ hipError_t opstep_set_state(OpStepper *st, const double *d0, const double *dn, d
   double *dst[2] = {st->buf[st->cur], st->buf[1 - st->cur]};
   for (int k = 0; k < 2; ++k) {
     if (src[k])
-      OPSTEP_TRY(hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, st->op->stream));
+      SAA_HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToDevice, st->op->stream));
     else
-      OPSTEP_TRY(hipMemsetAsync(dst[k], 0, bytes, st->op->stream));
+      SAA_HIP_TRY(hipMemsetAsync(dst[k], 0, bytes, st->op->stream));
   }
   st->tn = tn;
   return hipSuccess;
@@ -590,9 +578,9 @@ hipError_t opstep_set_state(OpStepper *st, const double *d0, const double *dn, d
 
 hipError_t opstep_get_state(OpStepper *st, double *d0, double *dn, double *tn) {
   const size_t bytes = 3 * static_cast<size_t>(st->op->n_nodes) * sizeof(double);
-  if (d0) OPSTEP_TRY(hipMemcpyAsync(d0, st->buf[st->cur], bytes, hipMemcpyDeviceToDevice, st->op->stream));
-  if (dn) OPSTEP_TRY(hipMemcpyAsync(dn, st->buf[1 - st->cur], bytes, hipMemcpyDeviceToDevice, st->op->stream));
-  OPSTEP_TRY(hipStreamSynchronize(st->op->stream));
+  if (d0) SAA_HIP_TRY(hipMemcpyAsync(d0, st->buf[st->cur], bytes, hipMemcpyDeviceToDevice, st->op->stream));
+  if (dn) SAA_HIP_TRY(hipMemcpyAsync(dn, st->buf[1 - st->cur], bytes, hipMemcpyDeviceToDevice, st->op->stream));
+  SAA_HIP_TRY(hipStreamSynchronize(st->op->stream));
   if (tn) *tn = st->tn;
   return hipSuccess;
 }
@@ -637,7 +625,7 @@ void advance(OpStepper *st) {
 hipError_t ensure_shared_map(OpStepper *st) {
   if (st->shared_of) return hipSuccess;
   const size_t n = static_cast<size_t>(st->op->n_nodes);
-  OPSTEP_TRY(dev_alloc(&st->shared_of, n));
+  SAA_HIP_TRY(dev_alloc(&st->shared_of, n));
   return hipMemsetAsync(st->shared_of, 0xff, (n ? n : 1) * sizeof(int32_t), st->op->stream);
 }
 
@@ -677,13 +665,13 @@ hipError_t node_pass(OpStepper *st, const double *contrib, const double *table_r
 hipError_t opstep_step(OpStepper *st, int32_t nsteps) {
   if (nsteps <= 0) return hipSuccess;
   double *contrib = nullptr;
-  OPSTEP_TRY(operator_scratch(st->op, 1, &contrib));
+  SAA_HIP_TRY(operator_scratch(st->op, 1, &contrib));
   for (int32_t k = 0; k < nsteps; ++k) {
-    if (st->passes & 1) OPSTEP_TRY(element_pass(st, st->buf[st->cur], contrib));
+    if (st->passes & 1) SAA_HIP_TRY(element_pass(st, st->buf[st->cur], contrib));
     if (st->passes == 1) continue;
-    OPSTEP_TRY(node_pass<0>(st, contrib, nullptr, nullptr));
+    SAA_HIP_TRY(node_pass<0>(st, contrib, nullptr, nullptr));
     if (st->passes != 3) continue;
-    OPSTEP_TRY(finalise(st, node_blocks(st)));
+    SAA_HIP_TRY(finalise(st, node_blocks(st)));
     advance(st);
   }
   return hipSuccess;
@@ -699,7 +687,7 @@ int opstep_passes(const OpStepper *st) { return st->passes; }
 hipError_t opstep_set_energy(OpStepper *st, double *energy, int64_t n_rows, int32_t every, int64_t next_step_index,
                              const uint8_t *shared_owned) {
   ModalOp *op = st->op;
-  OPSTEP_TRY(hipStreamSynchronize(op->stream));  // the old buffers may still be read by work in flight
+  SAA_HIP_TRY(hipStreamSynchronize(op->stream));  // the old buffers may still be read by work in flight
   energy_clear(st);
   if (!energy) return hipSuccess;
   const size_t n_part = static_cast<size_t>(node_blocks(st)) + opstep_grid(finish_lanes(st)).x;
@@ -746,7 +734,7 @@ hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *sha
   for (int32_t s = 0; s < n_global_shared; ++s)
     if (!held[s]) foreign.push_back(s);
   // the old lists may still be read by work in flight
-  OPSTEP_TRY(hipStreamSynchronize(op->stream));
+  SAA_HIP_TRY(hipStreamSynchronize(op->stream));
   energy_clear(st);  // its ownership flags and partial sums are sized by the old lists
   void *old[] = {st->shared_of, st->node, st->slot, st->foreign};
   for (void *b : old)
@@ -755,16 +743,16 @@ hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *sha
   st->n_shared = st->n_foreign = st->n_global_shared = 0;
   if (n_shared == 0 && n_global_shared == 0) return hipSuccess;
   const int32_t n_foreign = static_cast<int32_t>(foreign.size());
-  OPSTEP_TRY(dev_alloc(&st->shared_of, of.size()));
-  OPSTEP_TRY(dev_alloc(&st->node, static_cast<size_t>(n_shared)));
-  OPSTEP_TRY(dev_alloc(&st->slot, static_cast<size_t>(n_shared)));
-  OPSTEP_TRY(dev_alloc(&st->foreign, foreign.size()));
-  if (n_nodes > 0) OPSTEP_TRY(hipMemcpy(st->shared_of, of.data(), of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  SAA_HIP_TRY(dev_alloc(&st->shared_of, of.size()));
+  SAA_HIP_TRY(dev_alloc(&st->node, static_cast<size_t>(n_shared)));
+  SAA_HIP_TRY(dev_alloc(&st->slot, static_cast<size_t>(n_shared)));
+  SAA_HIP_TRY(dev_alloc(&st->foreign, foreign.size()));
+  if (n_nodes > 0) SAA_HIP_TRY(hipMemcpy(st->shared_of, of.data(), of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   if (n_shared > 0) {
-    OPSTEP_TRY(hipMemcpy(st->node, shared_local, static_cast<size_t>(n_shared) * sizeof(int32_t), hipMemcpyHostToDevice));
-    OPSTEP_TRY(hipMemcpy(st->slot, shared_slots, static_cast<size_t>(n_shared) * sizeof(int32_t), hipMemcpyHostToDevice));
+    SAA_HIP_TRY(hipMemcpy(st->node, shared_local, static_cast<size_t>(n_shared) * sizeof(int32_t), hipMemcpyHostToDevice));
+    SAA_HIP_TRY(hipMemcpy(st->slot, shared_slots, static_cast<size_t>(n_shared) * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  if (n_foreign > 0) OPSTEP_TRY(hipMemcpy(st->foreign, foreign.data(), foreign.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (n_foreign > 0) SAA_HIP_TRY(hipMemcpy(st->foreign, foreign.data(), foreign.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   st->n_shared = n_shared;
   st->n_foreign = n_foreign;
   st->n_global_shared = n_global_shared;
@@ -773,10 +761,10 @@ hipError_t opstep_set_shared(OpStepper *st, int32_t n_shared, const int32_t *sha
 
 hipError_t opstep_step_begin(OpStepper *st) {
   double *contrib = nullptr;
-  OPSTEP_TRY(operator_scratch(st->op, 1, &contrib));
-  OPSTEP_TRY(ensure_shared_map(st));
-  OPSTEP_TRY(element_pass(st, st->buf[st->cur], contrib));
-  OPSTEP_TRY(node_pass<1>(st, contrib, nullptr, nullptr));
+  SAA_HIP_TRY(operator_scratch(st->op, 1, &contrib));
+  SAA_HIP_TRY(ensure_shared_map(st));
+  SAA_HIP_TRY(element_pass(st, st->buf[st->cur], contrib));
+  SAA_HIP_TRY(node_pass<1>(st, contrib, nullptr, nullptr));
   st->pending = true;
   return hipSuccess;
 }
@@ -791,9 +779,9 @@ hipError_t opstep_step_finish(OpStepper *st, double *hist, int64_t hist_row) {
                        st->foreign, op->offsets, op->free_mask, st->mass, st->f, st->buf[st->cur], st->buf[1 - st->cur], st->dt,
                        st->alpha, ramp_scale(st), st->traj, st->n_cols, recorder_column(st), st->iface, row, st->owned,
                        st->energy ? st->energy_part + kCols * static_cast<int64_t>(node_blocks(st)) : nullptr);
-    OPSTEP_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
-  OPSTEP_TRY(finalise(st, node_blocks(st) + static_cast<int32_t>(opstep_grid(lanes).x)));
+  SAA_HIP_TRY(finalise(st, node_blocks(st) + static_cast<int32_t>(opstep_grid(lanes).x)));
   st->pending = false;
   advance(st);
   return hipSuccess;
@@ -803,14 +791,14 @@ hipError_t opstep_step_predicted(OpStepper *st, int32_t nsteps, const double *ta
                                  int64_t hist_row0) {
   if (nsteps <= 0) return hipSuccess;
   double *contrib = nullptr;
-  OPSTEP_TRY(operator_scratch(st->op, 1, &contrib));
-  OPSTEP_TRY(ensure_shared_map(st));
+  SAA_HIP_TRY(operator_scratch(st->op, 1, &contrib));
+  SAA_HIP_TRY(ensure_shared_map(st));
   const int64_t width = 3 * static_cast<int64_t>(st->n_shared);
   for (int32_t k = 0; k < nsteps; ++k) {
-    OPSTEP_TRY(element_pass(st, st->buf[st->cur], contrib));
-    OPSTEP_TRY(node_pass<2>(st, contrib, width > 0 ? table + (table_row0 + k) * width : nullptr,
+    SAA_HIP_TRY(element_pass(st, st->buf[st->cur], contrib));
+    SAA_HIP_TRY(node_pass<2>(st, contrib, width > 0 ? table + (table_row0 + k) * width : nullptr,
                             hist ? hist + (hist_row0 + k) * width : nullptr));
-    OPSTEP_TRY(finalise(st, node_blocks(st)));
+    SAA_HIP_TRY(finalise(st, node_blocks(st)));
     advance(st);
   }
   return hipSuccess;

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "saa_modal.h"
+#include "saa_hip_host.h"
 #include "saa_modal_op.h"
 #include "saa_p2.h"
 #include "saa_p2_elem.h"
@@ -306,25 +307,19 @@ __global__ void __launch_bounds__(kThreads) p1_load_diag_kernel(int32_t n_elems,
   }
 }
 
-#define P2_TRY(expr)                 \
-  do {                               \
-    const hipError_t e_ = (expr);    \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
 namespace {
 
 // scratch of `m` columns of 3 * (nodes per element) * n_elems doubles
 hipError_t ensure_scratch(const ModalOp *op, double **buf, int32_t *cap, int32_t m) {
   if (*cap >= m) return hipSuccess;
   if (*buf) {
-    P2_TRY(hipDeviceSynchronize());  // (a launch still reading the old buffer)
-    P2_TRY(hipFree(*buf));
+    SAA_HIP_TRY(hipDeviceSynchronize());  // (a launch still reading the old buffer)
+    SAA_HIP_TRY(hipFree(*buf));
     *buf = nullptr;
     *cap = 0;
   }
   const size_t count = static_cast<size_t>(op->order == 2 ? 30 : 12) * static_cast<size_t>(op->n_elems) * static_cast<size_t>(m);
-  P2_TRY(hipMalloc(reinterpret_cast<void **>(buf), (count ? count : 1) * sizeof(double)));
+  SAA_HIP_TRY(hipMalloc(reinterpret_cast<void **>(buf), (count ? count : 1) * sizeof(double)));
   *cap = m;
   return hipSuccess;
 }
@@ -336,8 +331,8 @@ dim3 elem_grid(const ModalOp *op) { return dim3(static_cast<unsigned>((op->n_ele
 int modal_order(const ModalOp *op) { return op->order; }
 
 hipError_t p2_apply(ModalOp *op, int32_t m, const double *x, int64_t ldx, double *kx, double *mx, int64_t ldy) {
-  if (kx) P2_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, m));
-  if (mx) P2_TRY(ensure_scratch(op, &op->scratch_m, &op->cap_m, m));
+  if (kx) SAA_HIP_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, m));
+  if (mx) SAA_HIP_TRY(ensure_scratch(op, &op->scratch_m, &op->cap_m, m));
   const int64_t stride = 30 * static_cast<int64_t>(op->n_elems);
   if (op->n_elems > 0) {
     if (kx)
@@ -346,15 +341,15 @@ hipError_t p2_apply(ModalOp *op, int32_t m, const double *x, int64_t ldx, double
     if (mx)
       hipLaunchKernelGGL(p2_apply_m_kernel, elem_grid(op), dim3(kThreads), 0, op->stream, op->n_elems, m, op->xyz, op->tets,
                          op->free_mask, op->rho, x, ldx, op->scratch_m);
-    P2_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
-  if (kx) P2_TRY(modal_node_sum(op, m, op->scratch_k, stride, kx, ldy));
-  if (mx) P2_TRY(modal_node_sum(op, m, op->scratch_m, stride, mx, ldy));
+  if (kx) SAA_HIP_TRY(modal_node_sum(op, m, op->scratch_k, stride, kx, ldy));
+  if (mx) SAA_HIP_TRY(modal_node_sum(op, m, op->scratch_m, stride, mx, ldy));
   return hipSuccess;
 }
 
 hipError_t operator_scratch(ModalOp *op, int32_t m, double **buf) {
-  P2_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, m));
+  SAA_HIP_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, m));
   *buf = op->scratch_k;
   return hipSuccess;
 }
@@ -367,7 +362,7 @@ hipError_t p2_elem_pass_k(ModalOp *op, const double *x, double *contrib) {
 }
 
 hipError_t operator_load(ModalOp *op, double fx, double fy, double fz, double *f) {
-  P2_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, 1));
+  SAA_HIP_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, 1));
   if (op->n_elems > 0) {
     if (op->order == 2)
       hipLaunchKernelGGL(p2_load_kernel, elem_grid(op), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets, fx, fy, fz,
@@ -375,14 +370,14 @@ hipError_t operator_load(ModalOp *op, double fx, double fy, double fz, double *f
     else
       hipLaunchKernelGGL(p1_load_diag_kernel, elem_grid(op), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets, fx, fy,
                          fz, 0.0, 0.0, 0.0, op->scratch_k, static_cast<double *>(nullptr), static_cast<double *>(nullptr));
-    P2_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
   return modal_node_sum(op, 1, op->scratch_k, 0, f, 0);
 }
 
 hipError_t operator_diagonal(ModalOp *op, double *diag_k, double *diag_m) {
-  if (diag_k) P2_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, 1));
-  if (diag_m) P2_TRY(ensure_scratch(op, &op->scratch_m, &op->cap_m, 1));
+  if (diag_k) SAA_HIP_TRY(ensure_scratch(op, &op->scratch_k, &op->cap_k, 1));
+  if (diag_m) SAA_HIP_TRY(ensure_scratch(op, &op->scratch_m, &op->cap_m, 1));
   if (op->n_elems > 0) {
     if (op->order == 2) {
       if (diag_k)
@@ -396,10 +391,10 @@ hipError_t operator_diagonal(ModalOp *op, double *diag_k, double *diag_m) {
                          0.0, 0.0, op->lam, op->mu, op->rho, static_cast<double *>(nullptr), diag_k ? op->scratch_k : nullptr,
                          diag_m ? op->scratch_m : nullptr);
     }
-    P2_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
-  if (diag_k) P2_TRY(modal_node_sum(op, 1, op->scratch_k, 0, diag_k, 0));
-  if (diag_m) P2_TRY(modal_node_sum(op, 1, op->scratch_m, 0, diag_m, 0));
+  if (diag_k) SAA_HIP_TRY(modal_node_sum(op, 1, op->scratch_k, 0, diag_k, 0));
+  if (diag_m) SAA_HIP_TRY(modal_node_sum(op, 1, op->scratch_m, 0, diag_m, 0));
   return hipSuccess;
 }
 

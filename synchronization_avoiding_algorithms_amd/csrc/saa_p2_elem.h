@@ -5,11 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "saa_modal_op.h"
+
 namespace saa {
 
 namespace {
-
-constexpr int kThreads = 256;
 
 // Shape functions and parametric derivatives of the 10-node tetrahedron at NQ points, evaluated by the compiler.
 template <int NQ>

@@ -13,6 +13,7 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "saa_hip_host.h"
 #include "saa_setup.h"
 
 namespace saa {
@@ -107,12 +108,6 @@ struct Scratch {
 };
 }  // namespace
 
-#define SETUP_TRY(expr)            \
-  do {                             \
-    const hipError_t e_ = (expr);  \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
 hipError_t setup_fields(int32_t n_nodes, int32_t n_elems, const double *xyz_host, const int32_t *tets_host, double rho, double fz,
                         double *lumped_host, double *fpre_host, double *min_edge_host) {
   Scratch sc;
@@ -121,18 +116,18 @@ hipError_t setup_fields(int32_t n_nodes, int32_t n_elems, const double *xyz_host
   int32_t *tets, *keys, *vals, *keys_s, *vals_s;
   int64_t *offsets;
   unsigned long long *minbits;
-  SETUP_TRY(sc.alloc(&xyz, 3 * static_cast<size_t>(n_nodes)));
-  SETUP_TRY(sc.alloc(&tets, static_cast<size_t>(n_pairs)));
-  SETUP_TRY(sc.alloc(&qvol, static_cast<size_t>(n_elems)));
-  SETUP_TRY(sc.alloc(&keys, static_cast<size_t>(n_pairs)));
-  SETUP_TRY(sc.alloc(&vals, static_cast<size_t>(n_pairs)));
-  SETUP_TRY(sc.alloc(&keys_s, static_cast<size_t>(n_pairs)));
-  SETUP_TRY(sc.alloc(&vals_s, static_cast<size_t>(n_pairs)));
-  SETUP_TRY(sc.alloc(&offsets, static_cast<size_t>(n_nodes) + 1));
-  SETUP_TRY(sc.alloc(&minbits, 1));
-  SETUP_TRY(hipMemcpy(xyz, xyz_host, 3 * static_cast<size_t>(n_nodes) * sizeof(double), hipMemcpyHostToDevice));
-  if (n_elems > 0) SETUP_TRY(hipMemcpy(tets, tets_host, static_cast<size_t>(n_pairs) * sizeof(int32_t), hipMemcpyHostToDevice));
-  SETUP_TRY(hipMemset(minbits, 0x7f, sizeof(unsigned long long)));  // 0x7f7f... : a huge finite double
+  SAA_HIP_TRY(sc.alloc(&xyz, 3 * static_cast<size_t>(n_nodes)));
+  SAA_HIP_TRY(sc.alloc(&tets, static_cast<size_t>(n_pairs)));
+  SAA_HIP_TRY(sc.alloc(&qvol, static_cast<size_t>(n_elems)));
+  SAA_HIP_TRY(sc.alloc(&keys, static_cast<size_t>(n_pairs)));
+  SAA_HIP_TRY(sc.alloc(&vals, static_cast<size_t>(n_pairs)));
+  SAA_HIP_TRY(sc.alloc(&keys_s, static_cast<size_t>(n_pairs)));
+  SAA_HIP_TRY(sc.alloc(&vals_s, static_cast<size_t>(n_pairs)));
+  SAA_HIP_TRY(sc.alloc(&offsets, static_cast<size_t>(n_nodes) + 1));
+  SAA_HIP_TRY(sc.alloc(&minbits, 1));
+  SAA_HIP_TRY(hipMemcpy(xyz, xyz_host, 3 * static_cast<size_t>(n_nodes) * sizeof(double), hipMemcpyHostToDevice));
+  if (n_elems > 0) SAA_HIP_TRY(hipMemcpy(tets, tets_host, static_cast<size_t>(n_pairs) * sizeof(int32_t), hipMemcpyHostToDevice));
+  SAA_HIP_TRY(hipMemset(minbits, 0x7f, sizeof(unsigned long long)));  // 0x7f7f... : a huge finite double
   const int threads = 256;
   if (n_elems > 0)
     hipLaunchKernelGGL(elem_volume_edge_kernel, dim3((unsigned)((n_elems + threads - 1) / threads)), dim3(threads), 0, nullptr,
@@ -142,25 +137,25 @@ hipError_t setup_fields(int32_t n_nodes, int32_t n_elems, const double *xyz_host
     size_t tmp_bytes = 0;
     int end_bit = 1;
     while (end_bit < 31 && (1ll << end_bit) < n_nodes) ++end_bit;
-    SETUP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<int>(n_pairs), 0, end_bit));
+    SAA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<int>(n_pairs), 0, end_bit));
     char *tmp = nullptr;  // (owned by `sc`: freed on every exit path)
-    SETUP_TRY(sc.alloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-    SETUP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<int>(n_pairs), 0, end_bit));
-    SETUP_TRY(hipDeviceSynchronize());
+    SAA_HIP_TRY(sc.alloc(&tmp, tmp_bytes ? tmp_bytes : 16));
+    SAA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<int>(n_pairs), 0, end_bit));
+    SAA_HIP_TRY(hipDeviceSynchronize());
   }
   hipLaunchKernelGGL(segment_offsets_kernel, dim3((unsigned)((n_pairs + 1 + threads - 1) / threads)), dim3(threads), 0, nullptr,
                      n_pairs, n_nodes, keys_s, offsets);
-  SETUP_TRY(sc.alloc(&lumped, 3 * static_cast<size_t>(n_nodes)));
-  SETUP_TRY(sc.alloc(&fpre, 3 * static_cast<size_t>(n_nodes)));
+  SAA_HIP_TRY(sc.alloc(&lumped, 3 * static_cast<size_t>(n_nodes)));
+  SAA_HIP_TRY(sc.alloc(&fpre, 3 * static_cast<size_t>(n_nodes)));
   hipLaunchKernelGGL(nodal_fields_kernel, dim3((unsigned)((n_nodes + threads - 1) / threads)), dim3(threads), 0, nullptr, n_nodes,
                      offsets, vals_s, qvol, rho, fz, lumped, fpre);
-  SETUP_TRY(hipGetLastError());
-  SETUP_TRY(hipDeviceSynchronize());
-  if (lumped_host) SETUP_TRY(hipMemcpy(lumped_host, lumped, 3 * static_cast<size_t>(n_nodes) * sizeof(double), hipMemcpyDeviceToHost));
-  if (fpre_host) SETUP_TRY(hipMemcpy(fpre_host, fpre, 3 * static_cast<size_t>(n_nodes) * sizeof(double), hipMemcpyDeviceToHost));
+  SAA_HIP_TRY(hipGetLastError());
+  SAA_HIP_TRY(hipDeviceSynchronize());
+  if (lumped_host) SAA_HIP_TRY(hipMemcpy(lumped_host, lumped, 3 * static_cast<size_t>(n_nodes) * sizeof(double), hipMemcpyDeviceToHost));
+  if (fpre_host) SAA_HIP_TRY(hipMemcpy(fpre_host, fpre, 3 * static_cast<size_t>(n_nodes) * sizeof(double), hipMemcpyDeviceToHost));
   if (min_edge_host) {
     unsigned long long bits = 0;
-    SETUP_TRY(hipMemcpy(&bits, minbits, sizeof(bits), hipMemcpyDeviceToHost));
+    SAA_HIP_TRY(hipMemcpy(&bits, minbits, sizeof(bits), hipMemcpyDeviceToHost));
     double len2;
     static_assert(sizeof(len2) == sizeof(bits), "double is 64 bits");
     __builtin_memcpy(&len2, &bits, sizeof(len2));
@@ -186,12 +181,12 @@ hipError_t copy_bandwidth(int device, int64_t n_bytes, int reps, double *bytes_p
   const int64_t n = n_bytes / 16;
   double2 *a, *b;
   (void)device;
-  SETUP_TRY(sc.alloc(&a, static_cast<size_t>(n)));
-  SETUP_TRY(sc.alloc(&b, static_cast<size_t>(n)));
-  SETUP_TRY(hipMemset(a, 0x3c, static_cast<size_t>(n) * 16));  // finite, non-zero doubles
+  SAA_HIP_TRY(sc.alloc(&a, static_cast<size_t>(n)));
+  SAA_HIP_TRY(sc.alloc(&b, static_cast<size_t>(n)));
+  SAA_HIP_TRY(hipMemset(a, 0x3c, static_cast<size_t>(n) * 16));  // finite, non-zero doubles
   hipEvent_t e0, e1;
-  SETUP_TRY(hipEventCreate(&e0));
-  SETUP_TRY(hipEventCreate(&e1));
+  SAA_HIP_TRY(hipEventCreate(&e0));
+  SAA_HIP_TRY(hipEventCreate(&e1));
   const dim3 grid(static_cast<unsigned>((n + 255) / 256));
   for (int r = 0; r < 2; ++r) hipLaunchKernelGGL(copy16_kernel, grid, dim3(256), 0, nullptr, a, b, n);  // warm
   hipError_t e = hipEventRecord(e0, nullptr);

@@ -13,14 +13,18 @@ constexpr int kStressMaxComponents = 8;
 
 int32_t modal_n_elems(const ModalOp *op);
 
-// Shared with saa_stress_p2.hip.  stress_buffers: abs_vol, node_wsum and the partial buffers [column][workgroup] of the
-// handle, one workgroup per 256 elements (freed by modal_destroy); *fresh is set when this call made them, and the caller
-// then fills abs_vol and node_wsum, or gives the buffers back with stress_buffers_free.  stress_reduce_partials: the
-// handle's partials folded in a fixed order, one workgroup per column, into m totals, maxima and lowest argmaxima (each
-// may be null; -1 and 0.0 when no partial holds a value).  Enqueued on the op's stream.
-hipError_t stress_buffers(ModalOp *op, bool *fresh);
-void stress_buffers_free(ModalOp *op);
+// Shared by both element orders (saa_stress.hip, saa_stress_p2.hip).  stress_prepare: on the handle's first stress call,
+// abs_vol, node_wsum and the partial buffers [column][workgroup], one workgroup per 256 elements (freed by modal_destroy),
+// and the two setup kernels of the handle's order that fill abs_vol and node_wsum; nothing stays allocated when it fails.
+// stress_reduce_partials: the handle's partials folded in a fixed order, one workgroup per column, into m totals, maxima
+// and lowest argmaxima (each may be null; -1 and 0.0 when no partial holds a value).  Enqueued on the op's stream.
+hipError_t stress_prepare(ModalOp *op);
 hipError_t stress_reduce_partials(ModalOp *op, int32_t m, double *total, double *best, int32_t *argbest);
+
+// 16-byte loads and stores of the six-double rows of m columns: base and column stride both multiples of 16 bytes
+inline bool wide_rows(const double *p, int64_t ld, int32_t m) {
+  return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (m == 1 || ld % 2 == 0);
+}
 
 // 1 <= m <= kModalMaxColumns displacement columns; any output may be null.  sigma: [column][6 e + c]; von_mises, energy:
 // [column][e]; energy_total, von_mises_max, von_mises_argmax: m entries.  Enqueued on the op's stream; arguments are

@@ -10,41 +10,21 @@
 //    node's elements in ascending element order (the node -> (element, corner) CSR of the handle).  |V_e| and the
 //    per-node weight sums are computed once per handle (stress_vol_kernel, stress_node_weight_kernel).
 // The Dirichlet mask of the handle is not applied: the displacement is read as given.
+//
+// Shared with saa_stress_p2.hip: the reduction helpers, load6 and compliance_form (saa_stress_dev.h), and on the host
+// stress_prepare, stress_reduce_partials and wide_rows (saa_stress.h), which serve the handles of both orders.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cmath>
 
+#include "saa_hip_host.h"
 #include "saa_modal_op.h"
 #include "saa_stress.h"
+#include "saa_stress_dev.h"
+#include "saa_stress_p2.h"
 
 namespace saa {
-
-namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-
-// better = larger value, on ties the smaller element; NaN never wins
-__device__ __forceinline__ void max_merge(double &v, int32_t &i, double ov, int32_t oi) {
-  if (ov > v || (ov == v && oi < i)) {
-    v = ov;
-    i = oi;
-  }
-}
-
-// butterfly over the 64 lanes of a wave: every lane ends with the wave's (sum, max, argmax)
-__device__ __forceinline__ void wave_reduce(double &s, double &v, int32_t &i) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_xor(s, off, 64);
-    const double ov = __shfl_xor(v, off, 64);
-    const int32_t oi = __shfl_xor(i, off, 64);
-    max_merge(v, i, ov, oi);
-  }
-}
-
-}  // namespace
 
 __global__ void __launch_bounds__(kThreads) stress_vol_kernel(int32_t n_elems, const double *__restrict__ xyz,
                                                               const int32_t *__restrict__ tets, double *__restrict__ abs_vol) {
@@ -75,8 +55,7 @@ __global__ void __launch_bounds__(kThreads) stress_elem_kernel(int32_t n_elems, 
                                                                double *__restrict__ von_mises, double *__restrict__ energy,
                                                                int64_t ld_elem, double *__restrict__ part_w,
                                                                double *__restrict__ part_vm, int32_t *__restrict__ part_idx) {
-  __shared__ double lw[kModalMaxColumns][kWaves], lvm[kModalMaxColumns][kWaves];
-  __shared__ int32_t li[kModalMaxColumns][kWaves];
+  __shared__ PartialLds lds;
   const int64_t e = blockIdx.x * (int64_t)kThreads + threadIdx.x;
   const bool valid = e < n_elems;
   int32_t v[4] = {0, 0, 0, 0};
@@ -114,32 +93,9 @@ __global__ void __launch_bounds__(kThreads) stress_elem_kernel(int32_t n_elems, 
       if (von_mises) von_mises[j * ld_elem + e] = vm;
       if (energy) energy[j * ld_elem + e] = w;
     }
-    if (part_w) {  // (uniform branch)
-      int32_t arg = valid ? (int32_t)e : INT32_MAX;
-      wave_reduce(w, vm, arg);
-      if ((threadIdx.x & 63) == 0) {
-        lw[j][threadIdx.x >> 6] = w;
-        lvm[j][threadIdx.x >> 6] = vm;
-        li[j][threadIdx.x >> 6] = arg;
-      }
-    }
+    if (part_w) wave_partial(lds, j, w, vm, valid ? (int32_t)e : INT32_MAX);  // (uniform branch)
   }
-  if (part_w) {
-    __syncthreads();
-    const int32_t j = threadIdx.x;
-    if (j < m) {
-      double w = lw[j][0], vm = lvm[j][0];
-      int32_t arg = li[j][0];
-#pragma unroll
-      for (int k = 1; k < kWaves; ++k) {
-        w += lw[j][k];
-        max_merge(vm, arg, lvm[j][k], li[j][k]);
-      }
-      part_w[(int64_t)j * gridDim.x + blockIdx.x] = w;
-      part_vm[(int64_t)j * gridDim.x + blockIdx.x] = vm;
-      part_idx[(int64_t)j * gridDim.x + blockIdx.x] = arg;
-    }
-  }
+  if (part_w) fold_partials(lds, m, part_w, part_vm, part_idx);
 }
 
 // One workgroup per column: fixed assignment of the partials to lanes, butterfly, then the waves in order.
@@ -176,33 +132,6 @@ __global__ void __launch_bounds__(kThreads) stress_final_kernel(int32_t n_parts,
   }
 }
 
-namespace {
-
-// six consecutive doubles; wide = the address is 16-byte aligned (three 16-byte loads instead of six 8-byte ones)
-__device__ __forceinline__ void load6(const double *__restrict__ p, bool wide, double t[6]) {
-  if (wide) {  // (uniform branch)
-    const double2 *q = reinterpret_cast<const double2 *>(p);
-    const double2 a = q[0], b = q[1], c = q[2];
-    t[0] = a.x, t[1] = a.y, t[2] = b.x, t[3] = b.y, t[4] = c.x, t[5] = c.y;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) t[c] = p[c];
-  }
-}
-
-// t^T C t with C = D^-1 (commons.py:25-31, engineering shear), split as |dev t|^2 / (2 mu) + tr(t)^2 / (3 (3 lambda + 2 mu)):
-// half_imu = 1 / (2 mu), cvol = 1 / (3 (3 lambda + 2 mu)).  A sum of squares: the one-bracket form t.t - lambda / (3 lambda +
-// 2 mu) tr^2 cancels on a pressure-dominated t and loses lambda / mu times the rounding (4e-10 at nu = 0.499999).  The normal
-// part of |dev t|^2 is ((t0 - t1)^2 + (t1 - t2)^2 + (t2 - t0)^2) / 3.
-__device__ __forceinline__ double compliance_form(const double t[6], double half_imu, double cvol) {
-  const double tr = t[0] + t[1] + t[2];
-  const double d01 = t[0] - t[1], d12 = t[1] - t[2], d20 = t[2] - t[0];
-  return half_imu * ((1.0 / 3.0) * (d01 * d01 + d12 * d12 + d20 * d20) + 2.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5])) +
-         cvol * (tr * tr);
-}
-
-}  // namespace
-
 // Error pass, one element per lane, the columns looped inside.  kNodal: against the piecewise-linear field of the nodal
 // values other[column][6 v + c], eta_e^2 = |V_e| / 20 (s^T C s + sum_a delta_a^T C delta_a) with delta_a = other(v_a) -
 // sigma_e and s = sum_a delta_a (the exact integral of a quadratic over the tetrahedron); otherwise against the element
@@ -216,8 +145,7 @@ __global__ void __launch_bounds__(kThreads) stress_error_kernel(int32_t n_elems,
                                                                 bool wide_sigma, bool wide_other, double *__restrict__ eta2,
                                                                 int64_t ld_eta, double *__restrict__ part_w,
                                                                 double *__restrict__ part_vm, int32_t *__restrict__ part_idx) {
-  __shared__ double lw[kModalMaxColumns][kWaves], lvm[kModalMaxColumns][kWaves];
-  __shared__ int32_t li[kModalMaxColumns][kWaves];
+  __shared__ PartialLds lds;
   const int64_t e = blockIdx.x * (int64_t)kThreads + threadIdx.x;
   const bool valid = e < n_elems;
   int32_t v[4] = {0, 0, 0, 0};
@@ -262,32 +190,9 @@ __global__ void __launch_bounds__(kThreads) stress_error_kernel(int32_t n_elems,
       best = w;
       if (eta2) eta2[j * ld_eta + e] = w;
     }
-    if (part_w) {  // (uniform branch)
-      int32_t arg = valid ? (int32_t)e : INT32_MAX;
-      wave_reduce(w, best, arg);
-      if ((threadIdx.x & 63) == 0) {
-        lw[j][threadIdx.x >> 6] = w;
-        lvm[j][threadIdx.x >> 6] = best;
-        li[j][threadIdx.x >> 6] = arg;
-      }
-    }
+    if (part_w) wave_partial(lds, j, w, best, valid ? (int32_t)e : INT32_MAX);  // (uniform branch)
   }
-  if (part_w) {
-    __syncthreads();
-    const int32_t j = threadIdx.x;
-    if (j < m) {
-      double w = lw[j][0], best = lvm[j][0];
-      int32_t arg = li[j][0];
-#pragma unroll
-      for (int k = 1; k < kWaves; ++k) {
-        w += lw[j][k];
-        max_merge(best, arg, lvm[j][k], li[j][k]);
-      }
-      part_w[(int64_t)j * gridDim.x + blockIdx.x] = w;
-      part_vm[(int64_t)j * gridDim.x + blockIdx.x] = best;
-      part_idx[(int64_t)j * gridDim.x + blockIdx.x] = arg;
-    }
-  }
+  if (part_w) fold_partials(lds, m, part_w, part_vm, part_idx);
 }
 
 // Node pass: node[j][K v + c] = sum_{e at v} |V_e| elem[j][K e + c] / node_wsum[v], ascending e.
@@ -319,55 +224,9 @@ __global__ void __launch_bounds__(kThreads) nodal_average_kernel(int32_t n_nodes
   for (int c = 0; c < K; ++c) o[c] = ws > 0.0 ? acc[c] / ws : 0.0;
 }
 
-#define STRESS_TRY(expr)             \
-  do {                               \
-    const hipError_t e_ = (expr);    \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
 namespace {
 
-template <typename T>
-hipError_t dev_alloc(T **p, size_t count) {
-  return hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T));
-}
-
 int32_t n_parts_of(const ModalOp *op) { return (op->n_elems + kThreads - 1) / kThreads; }
-
-// |V_e|, the node weight sums and the partial buffers, once per handle (freed by modal_destroy)
-hipError_t stress_prepare(ModalOp *op) {
-  bool fresh = false;
-  hipError_t e = stress_buffers(op, &fresh);
-  if (e != hipSuccess || !fresh) return e;
-  if (op->n_elems > 0)
-    hipLaunchKernelGGL(stress_vol_kernel, dim3(static_cast<unsigned>(n_parts_of(op))), dim3(kThreads), 0, op->stream,
-                       op->n_elems, op->xyz, op->tets, op->abs_vol);
-  e = hipGetLastError();
-  if (e == hipSuccess)
-    hipLaunchKernelGGL(stress_node_weight_kernel, dim3(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs, op->abs_vol, op->node_wsum);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) stress_buffers_free(op);
-  return e;
-}
-
-}  // namespace
-
-int32_t modal_n_elems(const ModalOp *op) { return op->n_elems; }
-
-hipError_t stress_buffers(ModalOp *op, bool *fresh) {
-  *fresh = false;
-  if (op->st_part_idx) return hipSuccess;
-  const size_t parts = static_cast<size_t>(n_parts_of(op)) * kModalMaxColumns;
-  hipError_t e = dev_alloc(&op->abs_vol, static_cast<size_t>(op->n_elems));
-  if (e == hipSuccess) e = dev_alloc(&op->node_wsum, static_cast<size_t>(op->n_nodes));
-  if (e == hipSuccess) e = dev_alloc(&op->st_part_w, parts);
-  if (e == hipSuccess) e = dev_alloc(&op->st_part_vm, parts);
-  if (e == hipSuccess) e = dev_alloc(&op->st_part_idx, parts);
-  if (e != hipSuccess) stress_buffers_free(op);
-  *fresh = e == hipSuccess;
-  return e;
-}
 
 void stress_buffers_free(ModalOp *op) {
   for (void **b : {reinterpret_cast<void **>(&op->abs_vol), reinterpret_cast<void **>(&op->node_wsum),
@@ -376,6 +235,34 @@ void stress_buffers_free(ModalOp *op) {
     if (*b) (void)hipFree(*b);
     *b = nullptr;
   }
+}
+
+// |V_e| and the node weight sums of a linear-element handle (order 2: p2_stress_setup)
+hipError_t stress_setup(ModalOp *op) {
+  if (op->n_elems > 0)
+    hipLaunchKernelGGL(stress_vol_kernel, dim3(static_cast<unsigned>(n_parts_of(op))), dim3(kThreads), 0, op->stream,
+                       op->n_elems, op->xyz, op->tets, op->abs_vol);
+  SAA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(stress_node_weight_kernel, dim3(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs, op->abs_vol, op->node_wsum);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+int32_t modal_n_elems(const ModalOp *op) { return op->n_elems; }
+
+hipError_t stress_prepare(ModalOp *op) {
+  if (op->st_part_idx) return hipSuccess;
+  const size_t parts = static_cast<size_t>(n_parts_of(op)) * kModalMaxColumns;
+  hipError_t e = dev_alloc(&op->abs_vol, static_cast<size_t>(op->n_elems));
+  if (e == hipSuccess) e = dev_alloc(&op->node_wsum, static_cast<size_t>(op->n_nodes));
+  if (e == hipSuccess) e = dev_alloc(&op->st_part_w, parts);
+  if (e == hipSuccess) e = dev_alloc(&op->st_part_vm, parts);
+  if (e == hipSuccess) e = dev_alloc(&op->st_part_idx, parts);
+  if (e == hipSuccess) e = op->order == 2 ? p2_stress_setup(op) : stress_setup(op);
+  if (e != hipSuccess) stress_buffers_free(op);
+  return e;
 }
 
 hipError_t stress_reduce_partials(ModalOp *op, int32_t m, double *total, double *best, int32_t *argbest) {
@@ -389,19 +276,15 @@ hipError_t stress_element(ModalOp *op, int32_t m, const double *x, int64_t ldx, 
                           int32_t *von_mises_argmax) {
   const bool reduce = energy_total || von_mises_max || von_mises_argmax;
   if (!reduce && !sigma && !von_mises && !energy) return hipSuccess;
-  STRESS_TRY(stress_prepare(op));
+  SAA_HIP_TRY(stress_prepare(op));
   const int32_t n_parts = n_parts_of(op);
   if (n_parts > 0) {
     hipLaunchKernelGGL(stress_elem_kernel, dim3(static_cast<unsigned>(n_parts)), dim3(kThreads), 0, op->stream, op->n_elems, m,
                        op->xyz, op->tets, op->lam, op->mu, x, ldx, sigma, ld_sigma, von_mises, energy, ld_elem,
                        reduce ? op->st_part_w : nullptr, op->st_part_vm, op->st_part_idx);
-    STRESS_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
-  if (reduce) {
-    hipLaunchKernelGGL(stress_final_kernel, dim3(static_cast<unsigned>(m)), dim3(kThreads), 0, op->stream, n_parts,
-                       op->st_part_w, op->st_part_vm, op->st_part_idx, energy_total, von_mises_max, von_mises_argmax);
-    STRESS_TRY(hipGetLastError());
-  }
+  if (reduce) SAA_HIP_TRY(stress_reduce_partials(op, m, energy_total, von_mises_max, von_mises_argmax));
   return hipSuccess;
 }
 
@@ -412,36 +295,32 @@ hipError_t stress_error(ModalOp *op, int32_t m, const double *sigma, int64_t ld_
                         double *eta2_max, int32_t *eta2_argmax) {
   const bool reduce = eta2_total || eta2_max || eta2_argmax;
   if (!reduce && !eta2) return hipSuccess;
-  STRESS_TRY(stress_prepare(op));
+  SAA_HIP_TRY(stress_prepare(op));
   const int32_t n_parts = n_parts_of(op);
   if (n_parts > 0) {
     const double half_imu = 0.5 / op->mu, cvol = 1.0 / (3.0 * (3.0 * op->lam + 2.0 * op->mu));
     const double *other = sigma_node ? sigma_node : sigma_other;
     const int64_t ldo = sigma_node ? ld_node : ld_other;
-    const auto wide = [m](const double *p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (m == 1 || ld % 2 == 0); };
     double *pw = reduce ? op->st_part_w : nullptr;
-#define STRESS_ERROR(NODAL)                                                                                                    \
-  hipLaunchKernelGGL(stress_error_kernel<NODAL>, dim3(static_cast<unsigned>(n_parts)), dim3(kThreads), 0, op->stream,          \
-                     op->n_elems, m, op->tets, op->abs_vol, half_imu, cvol, sigma, ld_sigma, other, ldo, wide(sigma, ld_sigma), \
-                     wide(other, ldo), eta2, ld_eta, pw, op->st_part_vm, op->st_part_idx)
+#define STRESS_ERROR(NODAL)                                                                                           \
+  hipLaunchKernelGGL(stress_error_kernel<NODAL>, dim3(static_cast<unsigned>(n_parts)), dim3(kThreads), 0, op->stream, \
+                     op->n_elems, m, op->tets, op->abs_vol, half_imu, cvol, sigma, ld_sigma, other, ldo,              \
+                     wide_rows(sigma, ld_sigma, m), wide_rows(other, ldo, m), eta2, ld_eta, pw, op->st_part_vm,       \
+                     op->st_part_idx)
     if (sigma_node)
       STRESS_ERROR(true);
     else
       STRESS_ERROR(false);
 #undef STRESS_ERROR
-    STRESS_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
-  if (reduce) {
-    hipLaunchKernelGGL(stress_final_kernel, dim3(static_cast<unsigned>(m)), dim3(kThreads), 0, op->stream, n_parts,
-                       op->st_part_w, op->st_part_vm, op->st_part_idx, eta2_total, eta2_max, eta2_argmax);
-    STRESS_TRY(hipGetLastError());
-  }
+  if (reduce) SAA_HIP_TRY(stress_reduce_partials(op, m, eta2_total, eta2_max, eta2_argmax));
   return hipSuccess;
 }
 
 hipError_t stress_nodal_average(ModalOp *op, int32_t m, int32_t k, const double *elem, int64_t ld_elem, double *node,
                                 int64_t ld_node) {
-  STRESS_TRY(stress_prepare(op));
+  SAA_HIP_TRY(stress_prepare(op));
   const dim3 grid(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads), static_cast<unsigned>(m));
 #define STRESS_NODAL(K)                                                                                                       \
   case K:                                                                                                                     \

@@ -9,6 +9,10 @@
 
 namespace saa {
 
+// The setup kernels of stress_prepare (saa_stress.h) on an order-2 handle: |V_e| = sum_q w_q |detJ_q| into abs_vol, its
+// nodal sums into node_wsum.  Enqueued on the op's stream.
+hipError_t p2_stress_setup(ModalOp *op);
+
 // 1 <= m <= kModalMaxColumns displacement columns; any output may be null.  sigma: [column][24 e + 6 q + c]; von_mises:
 // [column][4 e + q]; energy: [column][e]; energy_total, von_mises_max, von_mises_argmax (a point index 4 e + q): m entries.
 // Enqueued on the op's stream; arguments are validated by the caller.

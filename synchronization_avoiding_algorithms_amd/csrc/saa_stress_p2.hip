@@ -35,7 +35,9 @@
 // error pass starts from the accumulators of component c.  They emit no instruction.  The nodal pass has its two
 // alignments as template arguments, since the branch inside the CSR loop cost 27 registers and three waves.
 //
-// Totals and maxima go through the partial buffers and the final kernel of saa_stress.hip (one workgroup per column,
+// The (sum, max, lowest argmax) partials, load6 / store6 and compliance_form are those of the linear element
+// (saa_stress_dev.h); the buffers of the handle are made by stress_prepare of saa_stress.hip, which launches the two setup
+// kernels here through p2_stress_setup, and totals and maxima go through its final kernel (one workgroup per column,
 // fixed order).  No float atomics: every output is bitwise repeatable, and a column's results do not depend on the other
 // columns of the call.  The Dirichlet mask of the handle is not applied: the displacement is read as given.
 #include <hip/hip_runtime.h>
@@ -43,104 +45,19 @@
 
 #include <cmath>
 
+#include "saa_hip_host.h"
 #include "saa_modal_op.h"
 #include "saa_p2_elem.h"
 #include "saa_stress.h"
+#include "saa_stress_dev.h"
 #include "saa_stress_p2.h"
 
 namespace saa {
 
 namespace {
 
-constexpr int kWaves = kThreads / 64;
 constexpr double kGaussB = 0.1381966011250105;  // make_rule4's b
 constexpr double kSqrt5 = 2.23606797749978969;
-
-// better = larger value, on ties the smaller index; NaN never wins
-__device__ __forceinline__ void max_merge(double &v, int32_t &i, double ov, int32_t oi) {
-  if (ov > v || (ov == v && oi < i)) {
-    v = ov;
-    i = oi;
-  }
-}
-
-// butterfly over the 64 lanes of a wave: every lane ends with the wave's (sum, max, argmax)
-__device__ __forceinline__ void wave_reduce(double &s, double &v, int32_t &i) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_xor(s, off, 64);
-    const double ov = __shfl_xor(v, off, 64);
-    const int32_t oi = __shfl_xor(i, off, 64);
-    max_merge(v, i, ov, oi);
-  }
-}
-
-// The workgroup's partial of column j from its lanes' (w, best, arg): the waves' results into LDS; fold_partials writes them.
-struct PartialLds {
-  double w[kModalMaxColumns][kWaves], best[kModalMaxColumns][kWaves];
-  int32_t arg[kModalMaxColumns][kWaves];
-};
-
-__device__ __forceinline__ void wave_partial(PartialLds &l, int32_t j, double w, double best, int32_t arg) {
-  wave_reduce(w, best, arg);
-  if ((threadIdx.x & 63) == 0) {
-    l.w[j][threadIdx.x >> 6] = w;
-    l.best[j][threadIdx.x >> 6] = best;
-    l.arg[j][threadIdx.x >> 6] = arg;
-  }
-}
-
-__device__ __forceinline__ void fold_partials(PartialLds &l, int32_t m, double *__restrict__ part_w,
-                                              double *__restrict__ part_vm, int32_t *__restrict__ part_idx) {
-  __syncthreads();
-  const int32_t j = threadIdx.x;
-  if (j < m) {
-    double w = l.w[j][0], best = l.best[j][0];
-    int32_t arg = l.arg[j][0];
-#pragma unroll
-    for (int k = 1; k < kWaves; ++k) {
-      w += l.w[j][k];
-      max_merge(best, arg, l.best[j][k], l.arg[j][k]);
-    }
-    part_w[(int64_t)j * gridDim.x + blockIdx.x] = w;
-    part_vm[(int64_t)j * gridDim.x + blockIdx.x] = best;
-    part_idx[(int64_t)j * gridDim.x + blockIdx.x] = arg;
-  }
-}
-
-// six consecutive doubles; wide = the address is 16-byte aligned
-__device__ __forceinline__ void load6(const double *__restrict__ p, bool wide, double t[6]) {
-  if (wide) {  // (uniform branch)
-    const double2 *q = reinterpret_cast<const double2 *>(p);
-    const double2 a = q[0], b = q[1], c = q[2];
-    t[0] = a.x, t[1] = a.y, t[2] = b.x, t[3] = b.y, t[4] = c.x, t[5] = c.y;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) t[c] = p[c];
-  }
-}
-
-__device__ __forceinline__ void store6(double *__restrict__ p, bool wide, const double t[6]) {
-  if (wide) {  // (uniform branch)
-    double2 *q = reinterpret_cast<double2 *>(p);
-    q[0] = make_double2(t[0], t[1]);
-    q[1] = make_double2(t[2], t[3]);
-    q[2] = make_double2(t[4], t[5]);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) p[c] = t[c];
-  }
-}
-
-// t^T C t with C = D^-1 (engineering shear), split as |dev t|^2 / (2 mu) + tr(t)^2 / (3 (3 lambda + 2 mu)) as in saa_stress.hip
-// (a sum of squares; the one-bracket form cancels on a pressure-dominated t): half_imu = 1 / (2 mu), cvol = 1 / (3 (3 lambda +
-// 2 mu))
-__device__ __forceinline__ double compliance_form(const double t[6], double half_imu, double cvol) {
-  const double tr = t[0] + t[1] + t[2];
-  const double d01 = t[0] - t[1], d12 = t[1] - t[2], d20 = t[2] - t[0];
-  return half_imu * ((1.0 / 3.0) * (d01 * d01 + d12 * d12 + d20 * d20) + 2.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5])) +
-         cvol * (tr * tr);
-}
 
 // w_q |detJ_q| at the points of rule R from the element's ten coordinates
 template <int NQ>
@@ -407,57 +324,40 @@ __global__ void __launch_bounds__(kThreads, 2) p2_stress_error_kernel(int32_t n_
   if (part_w) fold_partials(lds, m, part_w, part_vm, part_idx);
 }
 
-#define P2S_TRY(expr)                \
-  do {                               \
-    const hipError_t e_ = (expr);    \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
 namespace {
 
 dim3 elem_grid(const ModalOp *op) { return dim3(static_cast<unsigned>((op->n_elems + kThreads - 1) / kThreads)); }
 
-// 16-byte loads and stores of six-double rows: base and column stride both multiples of 16 bytes
-bool wide_rows(const double *p, int64_t ld, int32_t m) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (m == 1 || ld % 2 == 0); }
+}  // namespace
 
-// |V_e| = sum_q w_q |detJ_q|, the node weight sums and the partial buffers, once per handle (freed by modal_destroy)
-hipError_t p2_stress_prepare(ModalOp *op) {
-  bool fresh = false;
-  P2S_TRY(stress_buffers(op, &fresh));
-  if (!fresh) return hipSuccess;
+hipError_t p2_stress_setup(ModalOp *op) {
   if (op->n_elems > 0)
     hipLaunchKernelGGL(p2_stress_vol_kernel, elem_grid(op), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
                        op->abs_vol);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(p2_stress_node_weight_kernel, dim3(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs, op->abs_vol, op->node_wsum);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) stress_buffers_free(op);
-  return e;
+  SAA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(p2_stress_node_weight_kernel, dim3(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, op->stream, op->n_nodes, op->offsets, op->pairs, op->abs_vol, op->node_wsum);
+  return hipGetLastError();
 }
-
-}  // namespace
 
 hipError_t p2_stress_element(ModalOp *op, int32_t m, const double *x, int64_t ldx, double *sigma, int64_t ld_sigma,
                              double *von_mises, int64_t ld_vm, double *energy, int64_t ld_elem, double *energy_total,
                              double *von_mises_max, int32_t *von_mises_argmax) {
   const bool reduce = energy_total || von_mises_max || von_mises_argmax;
   if (!reduce && !sigma && !von_mises && !energy) return hipSuccess;
-  P2S_TRY(p2_stress_prepare(op));
+  SAA_HIP_TRY(stress_prepare(op));
   if (op->n_elems > 0) {
     hipLaunchKernelGGL(p2_stress_elem_kernel, elem_grid(op), dim3(kThreads), 0, op->stream, op->n_elems, m, op->xyz, op->tets,
                        op->lam, op->mu, x, ldx, sigma, ld_sigma, wide_rows(sigma, ld_sigma, m), von_mises, ld_vm, energy, ld_elem,
                        reduce ? op->st_part_w : nullptr, op->st_part_vm, op->st_part_idx);
-    P2S_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
-  if (reduce) P2S_TRY(stress_reduce_partials(op, m, energy_total, von_mises_max, von_mises_argmax));
+  if (reduce) SAA_HIP_TRY(stress_reduce_partials(op, m, energy_total, von_mises_max, von_mises_argmax));
   return hipSuccess;
 }
 
 hipError_t p2_stress_nodal(ModalOp *op, int32_t m, const double *sigma, int64_t ld_sigma, double *sigma_node, int64_t ld_node) {
-  P2S_TRY(p2_stress_prepare(op));
+  SAA_HIP_TRY(stress_prepare(op));
   if (op->n_nodes <= 0) return hipSuccess;
   const dim3 grid(static_cast<unsigned>((op->n_nodes + kThreads - 1) / kThreads), static_cast<unsigned>(m));
   if (wide_rows(sigma, ld_sigma, m))
@@ -474,7 +374,7 @@ hipError_t p2_stress_error(ModalOp *op, int32_t m, const double *sigma, int64_t 
                            double *eta2_total, double *eta2_max, int32_t *eta2_argmax) {
   const bool reduce = eta2_total || eta2_max || eta2_argmax;
   if (!reduce && !eta2) return hipSuccess;
-  P2S_TRY(p2_stress_prepare(op));
+  SAA_HIP_TRY(stress_prepare(op));
   if (op->n_elems > 0) {
     const double half_imu = 0.5 / op->mu, cvol = 1.0 / (3.0 * (3.0 * op->lam + 2.0 * op->mu));
     double *pw = reduce ? op->st_part_w : nullptr;
@@ -487,9 +387,9 @@ hipError_t p2_stress_error(ModalOp *op, int32_t m, const double *sigma, int64_t 
                          op->tets, half_imu, cvol, sigma, ld_sigma, sigma_other, ld_other,
                          wide_rows(sigma, ld_sigma, m) && wide_rows(sigma_other, ld_other, m), eta2, ld_eta, pw, op->st_part_vm,
                          op->st_part_idx);
-    P2S_TRY(hipGetLastError());
+    SAA_HIP_TRY(hipGetLastError());
   }
-  if (reduce) P2S_TRY(stress_reduce_partials(op, m, eta2_total, eta2_max, eta2_argmax));
+  if (reduce) SAA_HIP_TRY(stress_reduce_partials(op, m, eta2_total, eta2_max, eta2_argmax));
   return hipSuccess;
 }
 

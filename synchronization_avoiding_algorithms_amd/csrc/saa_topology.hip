@@ -12,6 +12,8 @@
 // Minima by integer atomicMin, orders by hipCUB radix sorts of (key, node) pairs with absent nodes keyed to the maximum.
 #include "saa_topology.h"
 
+#include "saa_hip_host.h"
+
 #include <hipcub/hipcub.hpp>
 
 namespace saa {
@@ -154,12 +156,6 @@ struct Scratch {
   }
 };
 
-#define TOPO_TRY(expr)              \
-  do {                              \
-    const hipError_t e_ = (expr);   \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
 
 // The indices 0..n-1 whose key is not `none`, ordered by key: *sorted (device, n entries, the valid ones first), *n_valid.
@@ -167,22 +163,22 @@ template <typename K>
 hipError_t sorted_valid(Scratch &sc, const K *keys, int32_t n, K none, int32_t **sorted, int32_t *n_valid) {
   K *keys_s;
   int32_t *vals, *vals_s, *count;
-  TOPO_TRY(sc.alloc(&keys_s, (size_t)n));
-  TOPO_TRY(sc.alloc(&vals, (size_t)n));
-  TOPO_TRY(sc.alloc(&vals_s, (size_t)n));
-  TOPO_TRY(sc.alloc(&count, 1));
+  SAA_HIP_TRY(sc.alloc(&keys_s, (size_t)n));
+  SAA_HIP_TRY(sc.alloc(&vals, (size_t)n));
+  SAA_HIP_TRY(sc.alloc(&vals_s, (size_t)n));
+  SAA_HIP_TRY(sc.alloc(&count, 1));
   *sorted = vals_s;
   *n_valid = 0;
   if (n == 0) return hipSuccess;
-  TOPO_TRY(hipMemset(count, 0, sizeof(int32_t)));
+  SAA_HIP_TRY(hipMemset(count, 0, sizeof(int32_t)));
   hipLaunchKernelGGL(iota_kernel, grid_for(n), dim3(256), 0, nullptr, n, vals);
   hipLaunchKernelGGL((count_valid_kernel<K>), grid_for(n), dim3(256), 0, nullptr, n, keys, none, count);
   size_t tmp_bytes = 0;
-  TOPO_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_s, vals, vals_s, n));
+  SAA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_s, vals, vals_s, n));
   char *tmp;
-  TOPO_TRY(sc.alloc(&tmp, tmp_bytes));
-  TOPO_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, n));
-  TOPO_TRY(hipMemcpy(n_valid, count, sizeof(int32_t), hipMemcpyDeviceToHost));
+  SAA_HIP_TRY(sc.alloc(&tmp, tmp_bytes));
+  SAA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, n));
+  SAA_HIP_TRY(hipMemcpy(n_valid, count, sizeof(int32_t), hipMemcpyDeviceToHost));
   return hipSuccess;
 }
 
@@ -205,33 +201,33 @@ hipError_t rank_topology(int device, int32_t n_nodes, int32_t n_elems, const int
     err = "saa_topology_build: more than 2^30 elements";
     return hipErrorInvalidValue;
   }
-  TOPO_TRY(hipSetDevice(device));
+  SAA_HIP_TRY(hipSetDevice(device));
   Scratch sc;
   const int32_t words = (n_parts + 63) / 64;
   int32_t *tets, *epart, *lowest_other, *bad, *facets = nullptr;
   unsigned long long *mask, *key3;
   uint32_t *key1, *key2, *elem_key, *gs_key, *keyd;
   double *xyz = nullptr;
-  TOPO_TRY(sc.alloc(&tets, 4 * (size_t)n_elems));
-  TOPO_TRY(sc.alloc(&epart, (size_t)n_elems));
-  TOPO_TRY(sc.alloc(&mask, (size_t)n_nodes * words));
-  TOPO_TRY(sc.alloc(&key1, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&key2, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&key3, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&keyd, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&gs_key, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&lowest_other, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&elem_key, (size_t)n_elems));
-  TOPO_TRY(sc.alloc(&bad, 1));
+  SAA_HIP_TRY(sc.alloc(&tets, 4 * (size_t)n_elems));
+  SAA_HIP_TRY(sc.alloc(&epart, (size_t)n_elems));
+  SAA_HIP_TRY(sc.alloc(&mask, (size_t)n_nodes * words));
+  SAA_HIP_TRY(sc.alloc(&key1, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&key2, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&key3, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&keyd, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&gs_key, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&lowest_other, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&elem_key, (size_t)n_elems));
+  SAA_HIP_TRY(sc.alloc(&bad, 1));
   if (n_elems) {
-    TOPO_TRY(hipMemcpy(tets, tets_host, 4 * (size_t)n_elems * sizeof(int32_t), hipMemcpyHostToDevice));
-    TOPO_TRY(hipMemcpy(epart, epart_host, (size_t)n_elems * sizeof(int32_t), hipMemcpyHostToDevice));
+    SAA_HIP_TRY(hipMemcpy(tets, tets_host, 4 * (size_t)n_elems * sizeof(int32_t), hipMemcpyHostToDevice));
+    SAA_HIP_TRY(hipMemcpy(epart, epart_host, (size_t)n_elems * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  TOPO_TRY(hipMemset(mask, 0, (size_t)n_nodes * words * sizeof(unsigned long long)));
-  TOPO_TRY(hipMemset(key1, 0xff, (size_t)n_nodes * sizeof(uint32_t)));
-  TOPO_TRY(hipMemset(key2, 0xff, (size_t)n_nodes * sizeof(uint32_t)));
-  TOPO_TRY(hipMemset(keyd, 0xff, (size_t)n_nodes * sizeof(uint32_t)));
-  TOPO_TRY(hipMemset(bad, 0, sizeof(int32_t)));
+  SAA_HIP_TRY(hipMemset(mask, 0, (size_t)n_nodes * words * sizeof(unsigned long long)));
+  SAA_HIP_TRY(hipMemset(key1, 0xff, (size_t)n_nodes * sizeof(uint32_t)));
+  SAA_HIP_TRY(hipMemset(key2, 0xff, (size_t)n_nodes * sizeof(uint32_t)));
+  SAA_HIP_TRY(hipMemset(keyd, 0xff, (size_t)n_nodes * sizeof(uint32_t)));
+  SAA_HIP_TRY(hipMemset(bad, 0, sizeof(int32_t)));
   if (n_elems)
     hipLaunchKernelGGL(mark_kernel, grid_for(n_elems), dim3(256), 0, nullptr, n_elems, n_nodes, n_parts, words, rank, tets, epart, mask,
                        key1, elem_key, bad);
@@ -243,14 +239,14 @@ hipError_t rank_topology(int device, int32_t n_nodes, int32_t n_elems, const int
   if (n_nodes)
     hipLaunchKernelGGL(shared_key_kernel, grid_for(n_nodes), dim3(256), 0, nullptr, n_nodes, key1, lowest_other, key2, key3);
   if (n_facets) {
-    TOPO_TRY(sc.alloc(&facets, 3 * (size_t)n_facets));
-    TOPO_TRY(sc.alloc(&xyz, 3 * (size_t)n_nodes));
-    TOPO_TRY(hipMemcpy(facets, facets_host, 3 * (size_t)n_facets * sizeof(int32_t), hipMemcpyHostToDevice));
-    TOPO_TRY(hipMemcpy(xyz, xyz_host, 3 * (size_t)n_nodes * sizeof(double), hipMemcpyHostToDevice));
+    SAA_HIP_TRY(sc.alloc(&facets, 3 * (size_t)n_facets));
+    SAA_HIP_TRY(sc.alloc(&xyz, 3 * (size_t)n_nodes));
+    SAA_HIP_TRY(hipMemcpy(facets, facets_host, 3 * (size_t)n_facets * sizeof(int32_t), hipMemcpyHostToDevice));
+    SAA_HIP_TRY(hipMemcpy(xyz, xyz_host, 3 * (size_t)n_nodes * sizeof(double), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(clamp_key_kernel, grid_for(n_facets), dim3(256), 0, nullptr, n_facets, n_nodes, facets, xyz, clamp_tol, keyd, bad);
   }
   int32_t bad_host = 0;
-  TOPO_TRY(hipMemcpy(&bad_host, bad, sizeof(int32_t), hipMemcpyDeviceToHost));
+  SAA_HIP_TRY(hipMemcpy(&bad_host, bad, sizeof(int32_t), hipMemcpyDeviceToHost));
   if (bad_host) {
     err = bad_host == 1 ? "saa_topology_build: element part outside [0, n_parts)"
                         : (bad_host == 2 ? "saa_topology_build: element node outside [0, n_nodes)"
@@ -259,20 +255,20 @@ hipError_t rank_topology(int device, int32_t n_nodes, int32_t n_elems, const int
   }
   int32_t *elements, *nodes, *gshared, *shared, *dnodes, *dlocal;
   int32_t n_le = 0, n_ln = 0, n_gs = 0, n_sh = 0, n_d = 0, n_dl = 0;
-  TOPO_TRY(sorted_valid<uint32_t>(sc, elem_key, n_elems, kNone, &elements, &n_le));
-  TOPO_TRY(sorted_valid<uint32_t>(sc, key1, n_nodes, kNone, &nodes, &n_ln));
-  TOPO_TRY(sorted_valid<uint32_t>(sc, gs_key, n_nodes, kNone, &gshared, &n_gs));
-  TOPO_TRY(sorted_valid<unsigned long long>(sc, key3, n_nodes, kNone64, &shared, &n_sh));
-  TOPO_TRY(sorted_valid<uint32_t>(sc, keyd, n_nodes, kNone, &dnodes, &n_d));
+  SAA_HIP_TRY(sorted_valid<uint32_t>(sc, elem_key, n_elems, kNone, &elements, &n_le));
+  SAA_HIP_TRY(sorted_valid<uint32_t>(sc, key1, n_nodes, kNone, &nodes, &n_ln));
+  SAA_HIP_TRY(sorted_valid<uint32_t>(sc, gs_key, n_nodes, kNone, &gshared, &n_gs));
+  SAA_HIP_TRY(sorted_valid<unsigned long long>(sc, key3, n_nodes, kNone64, &shared, &n_sh));
+  SAA_HIP_TRY(sorted_valid<uint32_t>(sc, keyd, n_nodes, kNone, &dnodes, &n_d));
   // local numbering and what follows from it
   int32_t *local_of, *slot_of, *cells_local, *shared_local, *shared_slots;
   uint32_t *dl_key;
-  TOPO_TRY(sc.alloc(&local_of, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&slot_of, (size_t)n_nodes));
-  TOPO_TRY(sc.alloc(&cells_local, 4 * (size_t)n_le));
-  TOPO_TRY(sc.alloc(&shared_local, (size_t)n_sh));
-  TOPO_TRY(sc.alloc(&shared_slots, (size_t)n_sh));
-  TOPO_TRY(sc.alloc(&dl_key, (size_t)n_ln));
+  SAA_HIP_TRY(sc.alloc(&local_of, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&slot_of, (size_t)n_nodes));
+  SAA_HIP_TRY(sc.alloc(&cells_local, 4 * (size_t)n_le));
+  SAA_HIP_TRY(sc.alloc(&shared_local, (size_t)n_sh));
+  SAA_HIP_TRY(sc.alloc(&shared_slots, (size_t)n_sh));
+  SAA_HIP_TRY(sc.alloc(&dl_key, (size_t)n_ln));
   if (n_ln) hipLaunchKernelGGL(scatter_positions_kernel, grid_for(n_ln), dim3(256), 0, nullptr, n_ln, nodes, local_of);
   if (n_gs) hipLaunchKernelGGL(scatter_positions_kernel, grid_for(n_gs), dim3(256), 0, nullptr, n_gs, gshared, slot_of);
   if (n_le)
@@ -282,17 +278,17 @@ hipError_t rank_topology(int device, int32_t n_nodes, int32_t n_elems, const int
     hipLaunchKernelGGL(gather_kernel, grid_for(n_sh), dim3(256), 0, nullptr, n_sh, shared, slot_of, shared_slots);
   }
   if (n_ln) hipLaunchKernelGGL(local_clamp_key_kernel, grid_for(n_ln), dim3(256), 0, nullptr, n_ln, nodes, keyd, dl_key);
-  TOPO_TRY(sorted_valid<uint32_t>(sc, dl_key, n_ln, kNone, &dlocal, &n_dl));
-  TOPO_TRY(hipGetLastError());
-  TOPO_TRY(download(out->elements, elements, n_le));
-  TOPO_TRY(download(out->nodes, nodes, n_ln));
-  TOPO_TRY(download(out->cells_local, cells_local, 4 * (size_t)n_le));
-  TOPO_TRY(download(out->shared_nodes, shared, n_sh));
-  TOPO_TRY(download(out->shared_local, shared_local, n_sh));
-  TOPO_TRY(download(out->shared_slots, shared_slots, n_sh));
-  TOPO_TRY(download(out->global_shared, gshared, n_gs));
-  TOPO_TRY(download(out->dirichlet_nodes, dnodes, n_d));
-  TOPO_TRY(download(out->dirichlet_local, dlocal, n_dl));
+  SAA_HIP_TRY(sorted_valid<uint32_t>(sc, dl_key, n_ln, kNone, &dlocal, &n_dl));
+  SAA_HIP_TRY(hipGetLastError());
+  SAA_HIP_TRY(download(out->elements, elements, n_le));
+  SAA_HIP_TRY(download(out->nodes, nodes, n_ln));
+  SAA_HIP_TRY(download(out->cells_local, cells_local, 4 * (size_t)n_le));
+  SAA_HIP_TRY(download(out->shared_nodes, shared, n_sh));
+  SAA_HIP_TRY(download(out->shared_local, shared_local, n_sh));
+  SAA_HIP_TRY(download(out->shared_slots, shared_slots, n_sh));
+  SAA_HIP_TRY(download(out->global_shared, gshared, n_gs));
+  SAA_HIP_TRY(download(out->dirichlet_nodes, dnodes, n_d));
+  SAA_HIP_TRY(download(out->dirichlet_local, dlocal, n_dl));
   return hipSuccess;
 }
 

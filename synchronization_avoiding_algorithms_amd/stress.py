@@ -46,18 +46,19 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class StressRecovery:
-    """Stress recovery of one whole mesh on one GPU.  Wraps ``operator`` (a :class:`modal.ModalOperator`, whose mesh
-    and material are then used) or builds one with no Dirichlet dofs.  float64 CUDA tensors in and out."""
+class _Recovery:
+    """What the two recoveries share: the operator and its ownership, the checks of tensors, the column-chunked loops over
+    the raw calls, :meth:`estimate` and :meth:`history`.  ``_ROW`` is the shape of an element's stress rows, ``()`` for one
+    stress per element and ``(4,)`` for one per Gauss point; the leading dimensions ``6 |row| n_elems`` of ``sigma`` and
+    ``|row| n_elems`` of ``von_mises`` follow from it.  A subclass has ``stress_raw`` (keywords ``energy_total``,
+    ``von_mises_max``, ``von_mises_argmax``), ``error_raw``, ``nodal``, ``element``, ``error`` and ``_stress_columns``."""
 
     MAX_COLUMNS = 16
-    MAX_COMPONENTS = 8
+    _ROW = ()
 
-    def __init__(self, points, cells, lmd, mu, device=0, operator=None):
-        from .modal import ModalOperator
-
-        self._own = operator is None
-        self.op = ModalOperator(points, cells, (), lmd, mu, 1.0, device=device) if operator is None else operator
+    def _adopt(self, operator, own):
+        self._own = own
+        self.op = operator
         self._lib = self.op._lib
         self.n_nodes, self.n_elems, self.n_dof = self.op.n_nodes, self.op.n_elems, self.op.n_dof
         self.torch_device = self.op.torch_device
@@ -72,6 +73,107 @@ class StressRecovery:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _check(self, t, name):
+        import torch
+
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+            raise ValueError(f"{name} must be a float64 CUDA tensor")
+
+    def _chunks(self, m):
+        """``(first column, columns)`` of the launches that cover ``m`` columns."""
+        return [(j, min(self.MAX_COLUMNS, m - j)) for j in range(0, m, self.MAX_COLUMNS)]
+
+    def _element(self, X, sigma, von_mises, energy) -> dict:
+        import torch
+
+        self._check(X, "X")
+        vec = X.dim() == 1
+        X = (X.reshape(1, -1) if vec else X).contiguous()
+        if X.shape[1] != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} dofs per column, got {X.shape[1]}")
+        m, ne, dev = X.shape[0], self.n_elems, self.torch_device
+        per = 4 if self._ROW else 1
+        out = {}
+        if sigma:
+            out["sigma"] = torch.empty((m, ne, *self._ROW, 6), dtype=torch.float64, device=dev)
+        if von_mises:
+            out["von_mises"] = torch.empty((m, ne, *self._ROW), dtype=torch.float64, device=dev)
+        if energy:
+            out["energy"] = torch.empty((m, ne), dtype=torch.float64, device=dev)
+        out["energy_total"] = torch.empty(m, dtype=torch.float64, device=dev)
+        out["von_mises_max"] = torch.empty(m, dtype=torch.float64, device=dev)
+        out["von_mises_argmax"] = torch.empty(m, dtype=torch.int32, device=dev)
+        for j, c in self._chunks(m):
+            g = {k: v[j] for k, v in out.items()}
+            self._stress_columns(c, X[j], g.get("sigma"), 6 * per * ne, g.get("von_mises"), per * ne, g.get("energy"), ne,
+                                 g["energy_total"], g["von_mises_max"], g["von_mises_argmax"])
+        return {k: v[0] for k, v in out.items()} if vec else out
+
+    def _error(self, S, O, nodal, vec) -> dict:
+        """The error of checked, contiguous ``S (m, n_elems, *row, 6)`` against ``O``: ``(m, n_nodes, 6)`` if ``nodal``,
+        otherwise shaped like ``S``."""
+        import torch
+
+        m, ne, dev = S.shape[0], self.n_elems, self.torch_device
+        ld_sigma = 6 * (4 if self._ROW else 1) * ne
+        out = {"eta2": torch.empty((m, ne), dtype=torch.float64, device=dev),
+               "eta2_total": torch.empty(m, dtype=torch.float64, device=dev),
+               "eta2_max": torch.empty(m, dtype=torch.float64, device=dev),
+               "eta2_argmax": torch.empty(m, dtype=torch.int32, device=dev)}
+        for j, c in self._chunks(m):
+            node, oth = (O[j], None) if nodal else (None, O[j])
+            self.error_raw(c, S[j], ld_sigma, node, 6 * self.n_nodes, oth, ld_sigma, out["eta2"][j], ne, out["eta2_total"][j:],
+                           out["eta2_max"][j:], out["eta2_argmax"][j:])
+        return {k: v[0] for k, v in out.items()} if vec else out
+
+    def estimate(self, X) -> dict:
+        """Zienkiewicz-Zhu estimate of the stress error of displacement columns ``(m, n_dof)`` (or one ``(n_dof,)``
+        vector): :meth:`element` stress -> :meth:`nodal` stress -> :meth:`error`.  Returns the dict of :meth:`error` plus
+        ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish)."""
+        import torch
+
+        el = self.element(X, von_mises=False, energy=False)
+        out = self.error(el["sigma"], nodal=self.nodal(el["sigma"]))
+        out["energy_total"] = el["energy_total"]
+        den = 2.0 * el["energy_total"] + out["eta2_total"]
+        out["relative"] = torch.where(den > 0, out["eta2_total"] / den, torch.zeros_like(den)).sqrt()
+        return out
+
+    def history(self, traj) -> dict:
+        """``energy_total``, ``von_mises_max`` and ``von_mises_argmax`` of every column of a row-major
+        ``(n_dof, n_cols)`` trajectory (the recorder's and the HDF5 layout), host array or device tensor.  Only the
+        reductions are computed; no per-element field is written."""
+        import torch
+
+        if traj.shape[0] != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} rows, got {traj.shape[0]}")
+        n = traj.shape[1]
+        dev = self.torch_device
+        out = {"energy_total": torch.empty(n, dtype=torch.float64, device=dev),
+               "von_mises_max": torch.empty(n, dtype=torch.float64, device=dev),
+               "von_mises_argmax": torch.empty(n, dtype=torch.int32, device=dev)}
+        for j, c in self._chunks(n):
+            if isinstance(traj, torch.Tensor):
+                blk = traj[:, j:j + c].to(device=dev, dtype=torch.float64).T.contiguous()
+            else:
+                blk = torch.from_numpy(np.ascontiguousarray(np.asarray(traj[:, j:j + c], dtype=np.float64).T)).to(dev)
+            self.stress_raw(c, blk, self.n_dof, energy_total=out["energy_total"][j:], von_mises_max=out["von_mises_max"][j:],
+                            von_mises_argmax=out["von_mises_argmax"][j:])
+        return out
+
+
+class StressRecovery(_Recovery):
+    """Stress recovery of one whole mesh on one GPU.  Wraps ``operator`` (a :class:`modal.ModalOperator`, whose mesh
+    and material are then used) or builds one with no Dirichlet dofs.  float64 CUDA tensors in and out."""
+
+    MAX_COMPONENTS = 8
+
+    def __init__(self, points, cells, lmd, mu, device=0, operator=None):
+        from .modal import ModalOperator
+
+        own = operator is None
+        self._adopt(ModalOperator(points, cells, (), lmd, mu, 1.0, device=device) if own else operator, own)
 
     # ---- raw calls (any m, k and leading dimension: the library checks them) -----------------------------------------
     def stress_raw(self, m, x, ldx, sigma=None, ld_sigma=0, von_mises=None, energy=None, ld_elem=0, energy_total=None,
@@ -90,41 +192,15 @@ class StressRecovery:
                                                        int(ld_node), _ptr(sigma_other), int(ld_other), _ptr(eta2), int(ld_eta),
                                                        _ptr(eta2_total), _ptr(eta2_max), _ptr(eta2_argmax)))
 
+    def _stress_columns(self, c, x, sigma, ld_sigma, von_mises, ld_vm, energy, ld_elem, *reductions):
+        self.stress_raw(c, x, self.n_dof, sigma, ld_sigma, von_mises, energy, ld_elem, *reductions)  # (ld_vm == ld_elem)
+
     # ---- tensors -------------------------------------------------------------------------------------------------
-    def _check(self, t, name):
-        import torch
-
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
-            raise ValueError(f"{name} must be a float64 CUDA tensor")
-
     def element(self, X, sigma=True, von_mises=True, energy=True) -> dict:
         """Element fields of a ``(n_dof,)`` vector or an ``(m, n_dof)`` block, in launches of at most 16 columns:
         ``sigma (m, n_elems, 6)``, ``von_mises``, ``energy (m, n_elems)`` (those asked for) and ``energy_total``,
         ``von_mises_max``, ``von_mises_argmax (m,)``.  A vector input drops the leading ``m``."""
-        import torch
-
-        self._check(X, "X")
-        vec = X.dim() == 1
-        X = (X.reshape(1, -1) if vec else X).contiguous()
-        if X.shape[1] != self.n_dof:
-            raise ValueError(f"expected {self.n_dof} dofs per column, got {X.shape[1]}")
-        m, ne, dev = X.shape[0], self.n_elems, self.torch_device
-        out = {}
-        if sigma:
-            out["sigma"] = torch.empty((m, ne, 6), dtype=torch.float64, device=dev)
-        if von_mises:
-            out["von_mises"] = torch.empty((m, ne), dtype=torch.float64, device=dev)
-        if energy:
-            out["energy"] = torch.empty((m, ne), dtype=torch.float64, device=dev)
-        out["energy_total"] = torch.empty(m, dtype=torch.float64, device=dev)
-        out["von_mises_max"] = torch.empty(m, dtype=torch.float64, device=dev)
-        out["von_mises_argmax"] = torch.empty(m, dtype=torch.int32, device=dev)
-        for j in range(0, m, self.MAX_COLUMNS):
-            c = min(self.MAX_COLUMNS, m - j)
-            g = {k: v[j] for k, v in out.items()}
-            self.stress_raw(c, X[j], self.n_dof, g.get("sigma"), 6 * ne, g.get("von_mises"), g.get("energy"), ne,
-                            g["energy_total"], g["von_mises_max"], g["von_mises_argmax"])
-        return {k: v[0] for k, v in out.items()} if vec else out
+        return self._element(X, sigma, von_mises, energy)
 
     def nodal(self, E):
         """Volume-weighted nodal average of element fields ``(m, n_elems, k)`` (or ``(n_elems, k)``) ->
@@ -155,8 +231,6 @@ class StressRecovery:
         the Zienkiewicz-Zhu estimate) and ``other (m, n_elems, 6)`` (a second element field).  Returns ``eta2 (m,
         n_elems)`` and ``eta2_total``, ``eta2_max``, ``eta2_argmax (m,)``, in launches of at most 16 columns.  2-D inputs
         drop the leading ``m``."""
-        import torch
-
         if (nodal is None) == (other is None):
             raise ValueError("exactly one of nodal and other is needed")
         second, rows, name = (nodal, self.n_nodes, "nodal") if nodal is not None else (other, self.n_elems, "other")
@@ -169,56 +243,10 @@ class StressRecovery:
             raise ValueError(f"expected (m, {self.n_elems}, 6) element stresses, got {tuple(sigma_elem.shape)}")
         if O.dim() != 3 or tuple(O.shape) != (S.shape[0], rows, 6):
             raise ValueError(f"expected {name} of shape ({S.shape[0]}, {rows}, 6), got {tuple(second.shape)}")
-        m, ne, dev = S.shape[0], self.n_elems, self.torch_device
-        out = {"eta2": torch.empty((m, ne), dtype=torch.float64, device=dev),
-               "eta2_total": torch.empty(m, dtype=torch.float64, device=dev),
-               "eta2_max": torch.empty(m, dtype=torch.float64, device=dev),
-               "eta2_argmax": torch.empty(m, dtype=torch.int32, device=dev)}
-        for j in range(0, m, self.MAX_COLUMNS):
-            c = min(self.MAX_COLUMNS, m - j)
-            node, oth = (O[j], None) if nodal is not None else (None, O[j])
-            self.error_raw(c, S[j], 6 * ne, node, 6 * rows, oth, 6 * rows, out["eta2"][j], ne, out["eta2_total"][j:],
-                           out["eta2_max"][j:], out["eta2_argmax"][j:])
-        return {k: v[0] for k, v in out.items()} if vec else out
-
-    def estimate(self, X) -> dict:
-        """Zienkiewicz-Zhu estimate of the stress error of displacement columns ``(m, n_dof)`` (or one ``(n_dof,)``
-        vector): element stress -> nodal average -> :meth:`error`.  Returns the dict of :meth:`error` plus
-        ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish)."""
-        import torch
-
-        el = self.element(X, von_mises=False, energy=False)
-        out = self.error(el["sigma"], nodal=self.nodal(el["sigma"]))
-        out["energy_total"] = el["energy_total"]
-        den = 2.0 * el["energy_total"] + out["eta2_total"]
-        out["relative"] = torch.where(den > 0, out["eta2_total"] / den, torch.zeros_like(den)).sqrt()
-        return out
-
-    def history(self, traj) -> dict:
-        """``energy_total``, ``von_mises_max`` and ``von_mises_argmax`` of every column of a row-major
-        ``(n_dof, n_cols)`` trajectory (the recorder's and the HDF5 layout), host array or device tensor.  Only the
-        reductions are computed; no per-element field is written."""
-        import torch
-
-        if traj.shape[0] != self.n_dof:
-            raise ValueError(f"expected {self.n_dof} rows, got {traj.shape[0]}")
-        n = traj.shape[1]
-        dev = self.torch_device
-        out = {"energy_total": torch.empty(n, dtype=torch.float64, device=dev),
-               "von_mises_max": torch.empty(n, dtype=torch.float64, device=dev),
-               "von_mises_argmax": torch.empty(n, dtype=torch.int32, device=dev)}
-        for j in range(0, n, self.MAX_COLUMNS):
-            c = min(self.MAX_COLUMNS, n - j)
-            if isinstance(traj, torch.Tensor):
-                blk = traj[:, j:j + c].to(device=dev, dtype=torch.float64).T.contiguous()
-            else:
-                blk = torch.from_numpy(np.ascontiguousarray(np.asarray(traj[:, j:j + c], dtype=np.float64).T)).to(dev)
-            self.stress_raw(c, blk, self.n_dof, energy_total=out["energy_total"][j:], von_mises_max=out["von_mises_max"][j:],
-                            von_mises_argmax=out["von_mises_argmax"][j:])
-        return out
+        return self._error(S, O, nodal is not None, vec)
 
 
-class QuadraticStressRecovery:
+class QuadraticStressRecovery(_Recovery):
     """Stress recovery and error estimate of quadratic (10-node) tetrahedra, one whole mesh on one GPU, on an order-2
     handle (``saa_operator_stress_p2``, ``saa_operator_nodal_stress_p2``, ``saa_operator_stress_error_p2``; the
     definitions are in ``include/saa_hip.h``).  Wraps ``operator`` (an order-2 :class:`modal.ModalOperator`, whose mesh and
@@ -229,34 +257,20 @@ class QuadraticStressRecovery:
     the ``|V_e|``-weighted nodal means of ``sigma_h``, and ``eta_e^2`` the energy norm of ``sigma* - sigma_h`` over the
     element (14-point rule), or of the difference to a second Gauss-point field (4-point rule)."""
 
-    MAX_COLUMNS = 16
+    _ROW = (4,)
 
     def __init__(self, points, cells10, lmd, mu, device=0, operator=None):
         from .modal import ModalOperator
 
-        self._own = operator is None
-        if operator is None:
+        own = operator is None
+        if own:
             cells10 = np.asarray(cells10)
             if cells10.ndim != 2 or cells10.shape[1] != 10:
                 raise ValueError(f"expected (n_elems, 10) cells, got {cells10.shape}")
             operator = ModalOperator(points, cells10, (), lmd, mu, 1.0, device=device)
         elif operator.order != 2:
             raise ValueError("QuadraticStressRecovery needs an order-2 operator; StressRecovery serves order 1")
-        self.op = operator
-        self._lib = self.op._lib
-        self.n_nodes, self.n_elems, self.n_dof = self.op.n_nodes, self.op.n_elems, self.op.n_dof
-        self.torch_device = self.op.torch_device
-
-    def close(self):
-        if self._own and getattr(self, "op", None) is not None:
-            self.op.close()
-        self.op = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._adopt(operator, own)
 
     # ---- raw calls (any m and leading dimension: the library checks them) --------------------------------------------
     def stress_raw(self, m, x, ldx, sigma=None, ld_sigma=0, von_mises=None, ld_vm=0, energy=None, ld_elem=0, energy_total=None,
@@ -275,9 +289,10 @@ class QuadraticStressRecovery:
                                                           int(ld_node), _ptr(sigma_other), int(ld_other), _ptr(eta2),
                                                           int(ld_eta), _ptr(eta2_total), _ptr(eta2_max), _ptr(eta2_argmax)))
 
-    # ---- tensors -------------------------------------------------------------------------------------------------
-    _check = StressRecovery._check
+    def _stress_columns(self, c, x, *fields_and_reductions):
+        self.stress_raw(c, x, self.n_dof, *fields_and_reductions)
 
+    # ---- tensors -------------------------------------------------------------------------------------------------
     def _gauss(self, S, name):
         """``(m, n_elems, 4, 6)`` contiguous from that or ``(n_elems, 4, 6)``; the second value says which."""
         self._check(S, name)
@@ -292,30 +307,7 @@ class QuadraticStressRecovery:
         ``sigma (m, n_elems, 4, 6)``, ``von_mises (m, n_elems, 4)``, ``energy (m, n_elems)`` (those asked for) and
         ``energy_total``, ``von_mises_max``, ``von_mises_argmax (m,)`` (a point index ``4 e + q``).  A vector input drops
         the leading ``m``."""
-        import torch
-
-        self._check(X, "X")
-        vec = X.dim() == 1
-        X = (X.reshape(1, -1) if vec else X).contiguous()
-        if X.shape[1] != self.n_dof:
-            raise ValueError(f"expected {self.n_dof} dofs per column, got {X.shape[1]}")
-        m, ne, dev = X.shape[0], self.n_elems, self.torch_device
-        out = {}
-        if sigma:
-            out["sigma"] = torch.empty((m, ne, 4, 6), dtype=torch.float64, device=dev)
-        if von_mises:
-            out["von_mises"] = torch.empty((m, ne, 4), dtype=torch.float64, device=dev)
-        if energy:
-            out["energy"] = torch.empty((m, ne), dtype=torch.float64, device=dev)
-        out["energy_total"] = torch.empty(m, dtype=torch.float64, device=dev)
-        out["von_mises_max"] = torch.empty(m, dtype=torch.float64, device=dev)
-        out["von_mises_argmax"] = torch.empty(m, dtype=torch.int32, device=dev)
-        for j in range(0, m, self.MAX_COLUMNS):
-            c = min(self.MAX_COLUMNS, m - j)
-            g = {k: v[j] for k, v in out.items()}
-            self.stress_raw(c, X[j], self.n_dof, g.get("sigma"), 24 * ne, g.get("von_mises"), 4 * ne, g.get("energy"), ne,
-                            g["energy_total"], g["von_mises_max"], g["von_mises_argmax"])
-        return {k: v[0] for k, v in out.items()} if vec else out
+        return self._element(X, sigma, von_mises, energy)
 
     def nodal(self, sigma):
         """Recovered nodal stress of Gauss-point stresses ``(m, n_elems, 4, 6)`` (or ``(n_elems, 4, 6)``) ->
@@ -335,12 +327,10 @@ class QuadraticStressRecovery:
         estimate) and ``other (m, n_elems, 4, 6)`` (a second Gauss-point field).  Returns ``eta2 (m, n_elems)`` and
         ``eta2_total``, ``eta2_max``, ``eta2_argmax (m,)``, in launches of at most 16 columns.  Inputs without the leading
         ``m`` drop it."""
-        import torch
-
         if (nodal is None) == (other is None):
             raise ValueError("exactly one of nodal and other is needed")
         S, vec = self._gauss(sigma, "sigma")
-        m, ne, nn, dev = S.shape[0], self.n_elems, self.n_nodes, self.torch_device
+        m, nn = S.shape[0], self.n_nodes
         if nodal is not None:
             self._check(nodal, "nodal")
             O = (nodal.reshape(1, *nodal.shape) if nodal.dim() == 2 else nodal).contiguous()
@@ -350,49 +340,4 @@ class QuadraticStressRecovery:
             O, _ = self._gauss(other, "other")
             if O.shape[0] != m:
                 raise ValueError(f"expected other of {m} columns, got {O.shape[0]}")
-        out = {"eta2": torch.empty((m, ne), dtype=torch.float64, device=dev),
-               "eta2_total": torch.empty(m, dtype=torch.float64, device=dev),
-               "eta2_max": torch.empty(m, dtype=torch.float64, device=dev),
-               "eta2_argmax": torch.empty(m, dtype=torch.int32, device=dev)}
-        for j in range(0, m, self.MAX_COLUMNS):
-            c = min(self.MAX_COLUMNS, m - j)
-            node, oth = (O[j], None) if nodal is not None else (None, O[j])
-            self.error_raw(c, S[j], 24 * ne, node, 6 * nn, oth, 24 * ne, out["eta2"][j], ne, out["eta2_total"][j:],
-                           out["eta2_max"][j:], out["eta2_argmax"][j:])
-        return {k: v[0] for k, v in out.items()} if vec else out
-
-    def estimate(self, X) -> dict:
-        """Zienkiewicz-Zhu estimate of the stress error of displacement columns ``(m, n_dof)`` (or one ``(n_dof,)``
-        vector): Gauss-point stress -> recovered nodal stress -> :meth:`error`.  Returns the dict of :meth:`error` plus
-        ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish)."""
-        import torch
-
-        el = self.element(X, von_mises=False, energy=False)
-        out = self.error(el["sigma"], nodal=self.nodal(el["sigma"]))
-        out["energy_total"] = el["energy_total"]
-        den = 2.0 * el["energy_total"] + out["eta2_total"]
-        out["relative"] = torch.where(den > 0, out["eta2_total"] / den, torch.zeros_like(den)).sqrt()
-        return out
-
-    def history(self, traj) -> dict:
-        """``energy_total``, ``von_mises_max`` and ``von_mises_argmax`` of every column of a row-major
-        ``(n_dof, n_cols)`` trajectory (the recorder's and the HDF5 layout), host array or device tensor.  Only the
-        reductions are computed; no per-element field is written."""
-        import torch
-
-        if traj.shape[0] != self.n_dof:
-            raise ValueError(f"expected {self.n_dof} rows, got {traj.shape[0]}")
-        n = traj.shape[1]
-        dev = self.torch_device
-        out = {"energy_total": torch.empty(n, dtype=torch.float64, device=dev),
-               "von_mises_max": torch.empty(n, dtype=torch.float64, device=dev),
-               "von_mises_argmax": torch.empty(n, dtype=torch.int32, device=dev)}
-        for j in range(0, n, self.MAX_COLUMNS):
-            c = min(self.MAX_COLUMNS, n - j)
-            if isinstance(traj, torch.Tensor):
-                blk = traj[:, j:j + c].to(device=dev, dtype=torch.float64).T.contiguous()
-            else:
-                blk = torch.from_numpy(np.ascontiguousarray(np.asarray(traj[:, j:j + c], dtype=np.float64).T)).to(dev)
-            self.stress_raw(c, blk, self.n_dof, energy_total=out["energy_total"][j:], von_mises_max=out["von_mises_max"][j:],
-                            von_mises_argmax=out["von_mises_argmax"][j:])
-        return out
+        return self._error(S, O, nodal is not None, vec)
