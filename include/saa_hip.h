@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration; so did the partition entry points of the operator stepper, saa_operator_stepper_set_shared, _set_interface_buffer, _step_begin, _step_finish, _step_predicted, _halo_gather and _halo_scatter, and then saa_operator_stepper_set_energy). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration; so did the partition entry points of the operator stepper, saa_operator_stepper_set_shared, _set_interface_buffer, _step_begin, _step_finish, _step_predicted, _halo_gather and _halo_scatter, then saa_operator_stepper_set_energy, the finite-strain entry points and saa_operator_tangent_apply). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -624,7 +624,25 @@ int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev
  *   identity needs a symmetric constant K, and a balance for W(F) is not provided.
  *   THE TIME STEP IS NOT FOLLOWED: dt stays what the stepper was created with, by convention gamma * 2/omega_max of the
  *   LINEAR operator at the reference configuration.  Under large stretch the tangent stiffens and the stability limit
- *   moves below that; watch the displacements (and, under neo-Hooke, the inversion counters).
+ *   moves below that; watch the displacements (and, under neo-Hooke, the inversion counters).  The limit at a state can
+ *   be MEASURED: 2/omega_max of M_L^-1 K_T(d) by Lanczos on saa_operator_tangent_apply (modal.stable_time_step_operator,
+ *   OperatorStepper.stable_time_step, drivers dynamics --dt-check-every); the step itself is never changed.
+ * saa_operator_tangent_apply: kv_dev = K_T(u_dev) v_dev, the tangent of saa_operator_internal_force at u applied to one
+ *   column v, K_T(u) v = d/ds f_int(u + s v) at s = 0 (csrc/saa_optan.hip): one column of 3*n_nodes doubles, 0 on Dirichlet
+ *   dofs.  u and v are both masked to 0 on Dirichlet dofs on input, exactly as saa_operator_internal_force masks x.  At each
+ *   point of the K rule, with H = grad_X u and dH = grad_X v formed as the force pass forms H and its weights and sign:
+ *     SAA_MATERIAL_SVK          dE = (dH + dH^T + H^T dH + dH^T H)/2, dS = lambda tr(dE) I + 2 mu dE, dP = dH S + F dS
+ *     SAA_MATERIAL_NEO_HOOKEAN  dP = mu dH + (mu - lambda ln J) F^-T dH^T F^-T + lambda (F^-T : dH) F^-T, with F^-T - I and
+ *                               ln J from H as the force pass has them (cofactors of H, log1p(J - 1)), never from an
+ *                               inverse of I + H
+ *   and kv_a[i] = sum_q w_q detJ_q sum_k dP_q[i][k] dN_a/dX_k(q).  At u = 0 both are the handle's K; K_T is symmetric.
+ *   SAA_MATERIAL_LINEAR runs the kernels of saa_operator_apply with m = 1 on v (bit-equal to it); u_dev may then be NULL.
+ *   Inversion: under neo-Hooke an element with !(J > 0) at any point, NaN included, contributes 0 from all its corners and is
+ *   counted, by the rule and in the counter words of the force pass; SVK does not look at J.  n_inverted (host, or NULL) =
+ *   that count; asking for it synchronises the stream, otherwise the call is enqueued.  The call uses the element
+ *   contributions scratch and the node sum of the force; H(u) is recomputed on every call and nothing is stored per point.
+ *   No floating-point atomics: bitwise repeatable.  SAA_E_ARG, before the handle or the device is looked at: a material
+ *   outside {0, 1, 2}; then a null handle, null v_dev or kv_dev, null u_dev with a nonlinear material.
  * saa_operator_stepper_inverted: count = the number of (element, step) inversion events since the counters were cleared,
  *   first_step = the lowest step index (the recorder's, saa_operator_stepper_set_recorder) at which one occurred, -1 when
  *   none did.  set_material and set_state clear them.  Synchronises the stream.  Either output may be NULL.
@@ -634,6 +652,8 @@ int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev
 #define SAA_MATERIAL_NEO_HOOKEAN 2
 int saa_operator_internal_force(saa_operator *op, int32_t material, const double *x_dev, double *f_dev,
                                 double *energy_elem_dev /* n_elems or NULL */, int64_t *n_inverted /* or NULL */);
+int saa_operator_tangent_apply(saa_operator *op, int32_t material, const double *u_dev, const double *v_dev,
+                               double *kv_dev, int64_t *n_inverted /* host, or NULL */);
 int saa_operator_stepper_set_material(saa_operator_stepper *st, int32_t material);
 int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int64_t *first_step /* -1: none */);
 

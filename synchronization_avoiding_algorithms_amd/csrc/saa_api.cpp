@@ -2215,6 +2215,20 @@ int saa_operator_internal_force(saa_operator *op, int32_t material, const double
   return SAA_OK;
 }
 
+int saa_operator_tangent_apply(saa_operator *op, int32_t material, const double *u_dev, const double *v_dev, double *kv_dev,
+                               int64_t *n_inverted) {
+  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, "saa_operator_tangent_apply: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_tangent_apply: null handle");
+  if (!v_dev || !kv_dev) return fail(SAA_E_ARG, "saa_operator_tangent_apply: null v_dev or kv_dev");
+  if (!u_dev && material != SAA_MATERIAL_LINEAR)
+    return fail(SAA_E_ARG, "saa_operator_tangent_apply: null u_dev with a nonlinear material");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_tangent_apply(op->impl, material, u_dev, v_dev, kv_dev, n_inverted);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_tangent_apply: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
 struct saa_operator_stepper {
   saa::OpStepper *impl = nullptr;
 };

@@ -1,5 +1,6 @@
 // gfx950 kernels of the finite-strain (total-Lagrangian) element pass on the saa_operator handle, either element order, and
-// the host side of saa_operator_internal_force and of the stepper's material (saa_opstep.h).
+// the host side of saa_operator_internal_force, of saa_operator_tangent_apply (whose element passes are saa_optan.hip) and of
+// the stepper's material (saa_opstep.h).
 //
 //  * H = grad_X u and F = I + H at the points of the K rule: order 1 the one constant gradient of element_gradients, order 2
 //    H = T G at the four Gauss points exactly as p2_k_column (saa_opstep.hip) forms it.  The first Piola-Kirchhoff stress P
@@ -23,6 +24,7 @@
 
 #include "saa_hip_host.h"
 #include "saa_modal_op.h"
+#include "saa_opfs_dev.h"
 #include "saa_opstep.h"
 #include "saa_opstep_impl.h"
 #include "saa_p2.h"
@@ -31,8 +33,6 @@
 namespace saa {
 
 namespace {
-
-constexpr int kSvk = 1, kNeo = 2;
 
 // y - log1p(y) of y > -1, log1p_y = log1p(y) as the caller has it.  Below |y| = 1/16 the difference cancels (relative error
 // 2 eps/|y|): there the series y^2 (1/2 - y/3 + ... - y^13/15) by Horner's rule, whose first dropped term is 2^-59 of y^2/2.
@@ -141,12 +141,6 @@ __device__ __forceinline__ bool opfs_stress(const double h[3][3], double lam, do
     W = 0.5 * mu * (opfs_x_minus_log1p(y, 2.0 * lnJ) - low) + 0.5 * lam * lnJ * lnJ;
   }
   return true;
-}
-
-// one inverted element of step `step`: cnt[0] += 1, cnt[1] = min(cnt[1], step)
-__device__ __forceinline__ void opfs_count(unsigned long long *cnt, int64_t step) {
-  atomicAdd(cnt, 1ull);
-  atomicMin(cnt + 1, static_cast<unsigned long long>(step));
 }
 
 }  // namespace
@@ -345,6 +339,19 @@ hipError_t operator_internal_force(ModalOp *op, int material, const double *x, d
     SAA_HIP_TRY(energy_elem ? (launch<kNeo, true>(op, x, contrib, energy_elem, op->fs_count, 0))
                          : (launch<kNeo, false>(op, x, contrib, nullptr, op->fs_count, 0)));
   SAA_HIP_TRY(modal_node_sum(op, 1, contrib, 0, f, 0));
+  if (n_inverted) SAA_HIP_TRY(read_counters(op, op->fs_count, n_inverted, nullptr));
+  return hipSuccess;
+}
+
+hipError_t operator_tangent_apply(ModalOp *op, int material, const double *u, const double *v, double *kv, int64_t *n_inverted) {
+  if (material == 0) return operator_internal_force(op, 0, v, kv, nullptr, n_inverted);
+  double *contrib = nullptr;
+  SAA_HIP_TRY(operator_scratch(op, 1, &contrib));
+  SAA_HIP_TRY(operator_geometry(op));
+  SAA_HIP_TRY(alloc_counters(&op->fs_count, op->stream));
+  SAA_HIP_TRY(reset_counters(op->fs_count, op->stream));
+  SAA_HIP_TRY(optan_element_pass(op, material, u, v, contrib, op->fs_count));
+  SAA_HIP_TRY(modal_node_sum(op, 1, contrib, 0, kv, 0));
   if (n_inverted) SAA_HIP_TRY(read_counters(op, op->fs_count, n_inverted, nullptr));
   return hipSuccess;
 }

@@ -85,6 +85,10 @@ int opstep_passes(const OpStepper *st);  // the "passes" option
 // W(F_q).  n_inverted (host, or NULL): neo-Hooke elements with !(det F > 0) at a point, which contributed 0; reading it
 // synchronises the stream.  An order-2 handle makes its geometry table on first need.
 hipError_t operator_internal_force(ModalOp *op, int material, const double *x, double *f, double *energy_elem, int64_t *n_inverted);
+// kv = K_T(u) v, the tangent of that force at u applied to one column v (both masked on input, kv 0 on Dirichlet dofs): the
+// element pass of saa_optan.hip and modal_node_sum.  material 0: operator_internal_force of v (u is not looked at).
+// n_inverted as above.
+hipError_t operator_tangent_apply(ModalOp *op, int material, const double *u, const double *v, double *kv, int64_t *n_inverted);
 // The stepper's element pass becomes that of `material` (0: the linear pass the "stored_geometry" option selects); makes
 // the handle's geometry table and the stepper's two inversion counters on first need and clears the counters.
 hipError_t opstep_set_material(OpStepper *st, int material);

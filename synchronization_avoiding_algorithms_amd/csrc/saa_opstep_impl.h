@@ -47,5 +47,9 @@ hipError_t operator_geometry(ModalOp *op);
 // saa_opfs.hip: the finite-strain element pass of the stepper's material (!= 0) for one column x into contrib; an inverted
 // element is counted at st->step_index.
 hipError_t opfs_element_pass(OpStepper *st, const double *x, double *contrib);
+// saa_optan.hip: the tangent element pass of `material` (!= 0) at u for one column v into contrib; an inverted element writes
+// zeros and is counted in cnt (the two words of saa_opfs.hip) at step 0.  The handle's geometry table must exist.
+hipError_t optan_element_pass(ModalOp *op, int material, const double *u, const double *v, double *contrib,
+                              unsigned long long *cnt);
 
 }  // namespace saa

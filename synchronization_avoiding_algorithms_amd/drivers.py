@@ -190,6 +190,63 @@ def steady_state(mesh, out_dir=".", device=0, tol=1e-12, verbose=False, E=None, 
     return path, d
 
 
+class NotConverged(RuntimeError):
+    """The Newton iteration of :func:`steady_state_nonlinear` stopped short of its tolerance; ``report`` is what it printed."""
+
+    def __init__(self, message, report):
+        super().__init__(message)
+        self.report = report
+
+
+def steady_state_nonlinear(mesh, out_dir=".", device=0, material="svk", order=1, fz=None, load_steps=1, tol=1e-8, E=None,
+                           nu=None, rho=None):
+    """The static equilibrium ``f_int(d) = F`` of a finite-strain material (``svk``, ``neo_hookean``) on the whole mesh of
+    either order, clamped on every node of ``x = 0`` under the un-ramped load ``(0, -fz, -fz)`` (the clamp and load of
+    ``steady_state --order 2``): Newton-PCG on the operator handle (:func:`steady.newton_solve_operator`), written to
+    ``Results/Static/steady_distributed.vtk`` like the linear solution.  Returns ``(path, d (3n, 1), report)``; the report
+    holds the order, the sizes, the material, the solver's ``info`` without its history, ``max_abs_d`` and the mean
+    ``tip_deflection``, and under ``linear`` the same two figures of ``K d = F``.  Raises :class:`NotConverged` (after writing
+    nothing) when the iteration does not reach ``tol``.  The default ``tol`` is 1e-8 of ``|F|`` in the TRUE residual (the
+    linear driver's 1e-12 is the residual of the CG recurrence): on the 25 : 1 beam ``f_int`` itself is only good to about
+    ``eps (L/h)^4`` = 1e-9 of ``|F|`` in float64, because an element's nodal displacements are mostly its rigid motion."""
+    from . import fem_setup as fs
+    from .mesh import plane_nodes
+    from .modal import ModalOperator
+    from .steady import newton_solve_operator, steady_solve_operator, write_vtk_point_data
+
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    E = DEFAULTS["E"] if E is None else E
+    nu = DEFAULTS["nu"] if nu is None else nu
+    rho = DEFAULTS["rho"] if rho is None else rho
+    fz = DEFAULTS["fz"] if fz is None else fz
+    lmd, mu = fs.lame(E, nu)
+    if order == 2:
+        mesh = _quadratic(mesh)
+    cells = np.asarray(mesh.tets10 if order == 2 else mesh.tets)
+    points = np.asarray(mesh.points, dtype=np.float64)
+    n_vert = int(cells[:, :4].max()) + 1 if len(cells) else 0
+    tip = np.nonzero(np.abs(points[:n_vert, 0] - points[:, 0].max()) < 1e-9)[0]
+
+    def figures(d):
+        d = np.asarray(d).reshape(-1, 3)
+        return {"max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean())}
+
+    with ModalOperator(points, cells, fs.node_to_dof(plane_nodes(points)), lmd, mu, rho, device) as op:
+        load = op.load((0.0, -fz, -fz))
+        d_lin, _, _ = steady_solve_operator(op, load, tol=1e-12)
+        d, info = newton_solve_operator(op, load, material, tol=tol, load_steps=load_steps)
+        report = {"order": op.order, "n_nodes": op.n_nodes, "n_elems": op.n_elems, "n_free_dofs": int(op.free.sum().item()),
+                  "material": str(material).replace("-", "_"), "fz": float(fz),
+                  **{k: v for k, v in info.items() if k != "residual_history"}, **figures(d), "linear": figures(d_lin)}
+    if not info["converged"]:
+        raise NotConverged(f"steady_state --material {material}: Newton stopped after {info['newton_iterations']} iterations at "
+                           f"a relative residual of {info['residual']:.3e} (tolerance {tol:g}, {info['n_inverted']} inverted "
+                           "elements); try more --load-steps", report)
+    d = d.reshape(-1, 1)
+    return write_vtk_point_data(os.path.join(out_dir, STEADY_PATH), points, cells, d), d, report
+
+
 def shared_extraction(out_dir=".", rank=0):
     """``Shared_extraction.py:22-40``: rows ``shared_dof`` of the rank's trajectory."""
     local = rio.load_int_list(os.path.join(out_dir, PATHS["local_nodes"].format(r=rank)))
@@ -259,7 +316,7 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
 
 
 def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1, E=None, nu=None, rho=None, fz=None,
-             alpha=None, gamma=None, parts=0, partition="slab", energy_every=0, material="linear"):
+             alpha=None, gamma=None, parts=0, partition="slab", energy_every=0, material="linear", dt_check_every=0):
     """The explicit run of the whole mesh on one GPU through the operator handle (:func:`dynamics.run_dynamics`), for
     linear (``order=1``) or quadratic tetrahedra (``order=2``: the mesh is elevated like ``steady_state --order 2``),
     clamped on every node of ``x = 0``: lumped mass of the handle (HRZ for order 2), the reference load ``(0, -fz, -fz)``
@@ -272,7 +329,10 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     ``material``: ``linear``, ``svk`` (St. Venant-Kirchhoff) or ``neo_hookean`` - the finite-strain element pass
     (``include/saa_hip.h``); with a nonlinear one the report gains ``material``, ``inverted`` and ``first_inverted_step``.  ``dt`` stays that of
     the LINEAR operator at the reference configuration: under large stretch the tangent stiffens, the stability limit moves,
-    and the stepper does not follow it.  The energy balance is defined for ``linear`` only (ValueError otherwise)."""
+    and the stepper does not follow it.  The energy balance is defined for ``linear`` only (ValueError otherwise).
+    ``dt_check_every = S > 0`` (a nonlinear material, no ``parts``): the limit ``2/omega_max`` of the tangent at the current
+    state is measured every ``S`` steps and the report gains ``dt_check`` (:func:`dynamics.run_dynamics`); ``dt`` itself is
+    not changed."""
     from .dynamics import run_dynamics
     from .mesh import plane_nodes
 
@@ -285,7 +345,8 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     cells = mesh.tets10 if order == 2 else mesh.tets
     epart = make_partition(mesh, int(parts), partition) if parts and int(parts) > 0 else None
     store, report, *table = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device,
-                                         epart=epart, energy_every=int(energy_every or 0), material=material, **p)
+                                         epart=epart, energy_every=int(energy_every or 0), material=material,
+                                         dt_check_every=int(dt_check_every or 0), **p)
     path = rio.save_displacement(os.path.join(out_dir, PATHS["dynamics"].format(p=order)), store)
     if table:
         report["energy_path"] = rio.save_displacement(os.path.join(out_dir, PATHS["energy"].format(p=order)), table[0],
@@ -794,7 +855,13 @@ def main(argv=None):
                          "operator at the reference configuration: under large stretch the stability limit moves and the "
                          "stepper does not follow it")
     ap.add_argument("--fz", type=float, default=0.5,
-                    help="dynamics: the amplitude of the load (0, -fz, -fz); at the default nothing is nonlinear")
+                    help="dynamics, steady_state --material: the amplitude of the load (0, -fz, -fz); at the default nothing "
+                         "is nonlinear")
+    ap.add_argument("--load-steps", type=int, default=1,
+                    help="steady_state --material svk / neo-hookean: apply the load in this many equal fractions")
+    ap.add_argument("--dt-check-every", type=int, default=0,
+                    help="dynamics --material svk / neo-hookean: every so many steps measure 2/omega_max of the tangent at the "
+                         "current state and report it against dt (dt_check); dt is not changed")
     ap.add_argument("--n-past", type=int, default=20)
     ap.add_argument("--n-future", type=int, default=20)
     ap.add_argument("--filter-size", type=int, default=150)
@@ -817,6 +884,17 @@ def main(argv=None):
     if args.command == "dynamics" and args.energy and args.material != "linear":
         ap.error(f"dynamics --material {args.material} --energy: the energy balance is defined for the linear material only "
                  "(its identity needs a symmetric constant K)")
+    if args.command == "dynamics" and args.dt_check_every:
+        if args.dt_check_every < 0:
+            ap.error("dynamics --dt-check-every must be >= 0")
+        if args.material == "linear":
+            ap.error("dynamics --dt-check-every: the check is for --material svk or neo-hookean (the linear operator's limit "
+                     "does not move)")
+        if args.parts and args.parts > 0:
+            ap.error("dynamics --dt-check-every --parts: a rank's operator is only its share of the tangent; run the check "
+                     "on the whole mesh")
+    if args.command == "steady_state" and args.load_steps < 1:
+        ap.error("steady_state --load-steps must be >= 1")
     if args.command in ("stress", "estimate") and args.order == 2 and args.modeled:
         ap.error(f"{args.command} --order 2 --modeled: there is no modelled p = 2 run (the predictor drives linear elements)")
     rank, world, local = _dist_env()
@@ -835,7 +913,7 @@ def main(argv=None):
             path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order,
                                     parts=args.parts, partition=args.partition,
                                     energy_every=max(args.energy_every, 1) if args.energy else 0, fz=args.fz,
-                                    material=args.material)
+                                    material=args.material, dt_check_every=args.dt_check_every)
             print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
@@ -856,6 +934,17 @@ def main(argv=None):
                                args.partition, device=local, verbose=True)
     elif args.command == "steady_state":
         if rank != 0:
+            return
+        if args.material != "linear":
+            import json
+
+            try:
+                path, _, report = steady_state_nonlinear(_load_mesh(args), args.out, device=local, material=args.material,
+                                                         order=args.order, fz=args.fz, load_steps=args.load_steps)
+            except NotConverged as exc:
+                print(json.dumps(exc.report))
+                raise SystemExit(f"error: {exc}") from None
+            print(json.dumps({**report, "path": path}))
             return
         path, _ = steady_state(_load_mesh(args), args.out, device=local, verbose=True, order=args.order)
     elif args.command == "shared_extraction":

@@ -47,9 +47,24 @@ class OperatorStepper:
         m, f = self._vector(mass), self._vector(load)
         _lib.check(self._lib.saa_operator_stepper_create(op._h, _dev(m), _dev(f), float(dt), float(alpha), 1 if ramp else 0,
                                                          C.byref(self._h)))
+        self._mass = m                    # (for stable_time_step; the library has its own copy)
         self.material = "linear"
         if _lib.material_id(material) != 0:
             self.set_material(material)
+
+    def stable_time_step(self, gamma=0.9, lanczos_tol=1e-10):
+        """:func:`modal.stable_time_step_operator` with the stepper's mass and material at its current ``d0``: ``omega_max`` of
+        ``M_L^-1 K_T(d0)``, ``dt_crit = 2/omega_max`` and what goes with them, plus ``dt`` (the stepper's own, which this call
+        does not change) and ``dt_over_dt_crit``: above 1 the linearised update at this state is unstable.  Synchronises."""
+        from .modal import stable_time_step_operator
+
+        if _lib.material_id(self.material) == 0:
+            out = stable_time_step_operator(self.op, self._mass, gamma, lanczos_tol)
+        else:
+            out = stable_time_step_operator(self.op, self._mass, gamma, lanczos_tol, self.material, self.state()[0])
+        out["dt"] = self.dt
+        out["dt_over_dt_crit"] = self.dt / out["dt_crit"]
+        return out
 
     def set_material(self, name):
         """The element pass becomes the finite-strain pass of ``svk`` / ``neo_hookean``, or the linear pass again
@@ -456,7 +471,7 @@ def energy_report(rows):
 
 
 def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5,
-                 gamma=0.9, device=0, epart=None, energy_every=0, material="linear"):
+                 gamma=0.9, device=0, epart=None, energy_every=0, material="linear", dt_check_every=0):
     """What ``drivers dynamics`` computes: the operator of ``cells`` (4 columns: order 1, 10: order 2) clamped on
     ``dirichlet_nodes``, its lumped mass, the reference load ``(0, -fz, -fz)`` ramped over ``t < 1``, ``dt = gamma *
     2/omega_max`` and ``n_steps`` steps recorded every ``save_every``.  Returns ``(trajectory (n_dof, n_cols) array,
@@ -467,13 +482,25 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
     ``linear``, ``svk`` or ``neo_hookean``; with a nonlinear one the report gains ``material``, ``inverted`` and
     ``first_inverted_step`` (with ``linear`` it is what it always was, key for key).  ``dt``
     stays that of the linear operator at the reference configuration whatever the material; the energy balance is defined
-    for ``linear`` only (ValueError otherwise)."""
+    for ``linear`` only (ValueError otherwise).  ``dt_check_every = S > 0`` (a nonlinear material on the whole mesh only,
+    ValueError otherwise): the run is split into calls of ``S`` steps - the stepper is bit-equal under any split - and after
+    each, the last included, :meth:`OperatorStepper.stable_time_step` measures the limit at the current state; the report
+    gains ``dt_check``: ``every``, ``n_checks``, ``dt_crit_min`` and the step count ``dt_crit_min_step`` at which it was seen,
+    ``dt_over_dt_crit_max`` and ``first_exceeded_step`` (the step count of the first check with ``dt > dt_crit``, -1: never).
+    ``dt`` is not changed during the run."""
     import torch
 
     mat = _lib.material_id(material)
     material = str(material).replace("-", "_")
     if mat != 0 and energy_every:
         raise ValueError("the energy balance is defined for the linear material only: its identity needs a symmetric constant K")
+    dt_check_every = int(dt_check_every or 0)
+    if dt_check_every < 0:
+        raise ValueError("dt_check_every must be >= 0")
+    if dt_check_every and mat == 0:
+        raise ValueError("the time-step check is for a nonlinear material: the linear operator's limit does not move")
+    if dt_check_every and epart is not None:
+        raise ValueError("the time-step check is not defined for a partition: a rank's operator is only its share of the tangent")
 
     from . import fem_setup as fs
     from .modal import ModalOperator, stable_time_step_operator
@@ -492,7 +519,15 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
         with OperatorStepper(op, mass, op.load((0.0, -fz, -fz)), ts["dt"], alpha, ramp=True, material=material) as st:
             traj = st.record(n_cols, save_every) if n_cols > 0 else None
             rows = st.record_energy(n_rows, energy_every) if n_rows > 0 else None
-            st.step(n_steps)
+            if dt_check_every:
+                checks, done = [], 0
+                while done < int(n_steps):
+                    n = min(dt_check_every, int(n_steps) - done)
+                    st.step(n)
+                    done += n
+                    checks.append((done, st.stable_time_step(gamma)))
+            else:
+                st.step(n_steps)
             d0, _, tn = st.state()
             inverted, first_inverted = st.inverted()
             store = traj.cpu().numpy() if traj is not None else np.zeros((op.n_dof, 0))
@@ -507,11 +542,25 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
                   "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean())}
         if mat != 0:
             report.update(material=material, inverted=inverted, first_inverted_step=first_inverted)
+        if dt_check_every:
+            report["dt_check"] = dt_check_report(checks, dt_check_every)
     torch.cuda.synchronize(device)
     if energy_every:
         report["energy"] = energy_report(table)
         return store, report, table
     return store, report
+
+
+def dt_check_report(checks, every):
+    """What ``drivers dynamics --dt-check-every`` prints of ``[(steps done, OperatorStepper.stable_time_step())]``."""
+    out = {"every": int(every), "n_checks": len(checks), "dt_crit_min": None, "dt_crit_min_step": -1,
+           "dt_over_dt_crit_max": None, "first_exceeded_step": -1}
+    if checks:
+        step, low = min(checks, key=lambda c: c[1]["dt_crit"])
+        out.update(dt_crit_min=low["dt_crit"], dt_crit_min_step=step,
+                   dt_over_dt_crit_max=max(c[1]["dt_over_dt_crit"] for c in checks),
+                   first_exceeded_step=next((s for s, c in checks if c["dt_over_dt_crit"] > 1.0), -1))
+    return out
 
 
 def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device,

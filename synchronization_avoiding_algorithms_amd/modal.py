@@ -208,6 +208,30 @@ class ModalOperator:
                                                          C.byref(n_inv) if energy else None))
         return (f, en, int(n_inv.value)) if energy else f
 
+    def tangent_apply(self, u, v, material="svk", count=False):
+        """``K_T(u) v``, the tangent of :meth:`internal_force` at the displacement ``u`` applied to ``v`` (both ``(n_dof,)``
+        float64 CUDA tensors, masked on Dirichlet dofs on input), 0 on Dirichlet dofs (``saa_operator_tangent_apply``).
+        ``linear`` is ``apply(v)[0]`` bit for bit and ``u`` may then be None.  ``count=True``: returns ``(kv, n_inverted)`` -
+        the number of elements that neo-Hooke found inverted at ``u``, which contributed 0 - and synchronises."""
+        import torch
+
+        def ok(x):
+            return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.numel() == self.n_dof
+
+        mat = _lib.material_id(material)
+        if not ok(v):
+            raise ValueError(f"v must be a float64 CUDA tensor of {self.n_dof} values")
+        if not (ok(u) or (u is None and mat == 0)):
+            raise ValueError(f"u must be a float64 CUDA tensor of {self.n_dof} values")
+        v = v.reshape(-1).contiguous()
+        u = u.reshape(-1).contiguous() if u is not None else None
+        kv = torch.empty_like(v)
+        n_inv = C.c_int64(0)
+        _lib.check(self._lib.saa_operator_tangent_apply(self._h, mat, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                        C.c_void_p(v.data_ptr()), C.c_void_p(kv.data_ptr()),
+                                                        C.byref(n_inv) if count else None))
+        return (kv, int(n_inv.value)) if count else kv
+
     def element_bound(self, return_omega=False) -> dict:
         """``omega_max`` bound ``max_e omega_e``, its element, the count of elements with signed volume <= 0 and
         whether the bound is certified (that count is 0); ``omega_e`` (a CUDA tensor) on request."""
@@ -425,19 +449,36 @@ def stable_time_step(points, cells, dirichlet_nodes, E, nu, rho, gamma=0.9, devi
             "seconds": {"setup": t1 - t0, "element_bound": t2 - t1, "lanczos": t3 - t2}}
 
 
-def stable_time_step_operator(op: ModalOperator, mass, gamma=0.9, lanczos_tol=1e-10) -> dict:
+def stable_time_step_operator(op: ModalOperator, mass, gamma=0.9, lanczos_tol=1e-10, material="linear", state=None) -> dict:
     """``{"omega_max", "dt_crit", "dt"}`` of the central-difference update on an operator handle of either order with the
     lumped mass ``mass`` (``(n_dof,)``, e.g. :meth:`ModalOperator.lumped_mass`): ``omega_max`` of ``M_L^-1 K`` on the free
     dofs by :func:`lanczos_max` on the handle's ``K`` apply, ``dt_crit = 2/omega_max`` and ``dt = gamma * dt_crit``.  The
-    step of :class:`dynamics.OperatorStepper`; nothing else picks its ``dt`` from it."""
+    step of :class:`dynamics.OperatorStepper`; nothing else picks its ``dt`` from it.
+
+    With a nonlinear ``material`` and a ``state`` (an ``(n_dof,)`` float64 CUDA displacement) the operator is the tangent
+    ``K_T(state)`` of that material (:meth:`ModalOperator.tangent_apply`): the limit of the linearised update at that state.
+    The dict then also holds ``material``, ``n_inverted`` (elements neo-Hooke dropped from the tangent) and
+    ``lanczos_residual``."""
     import torch
 
     m = mass if torch.is_tensor(mass) else torch.as_tensor(np.asarray(mass, dtype=np.float64))
     m = m.to(device=op.torch_device, dtype=torch.float64).reshape(-1)
     s = torch.where(m > 0, op.free / torch.sqrt(torch.where(m > 0, m, 1.0)), 0.0)  # (a node without elements has no mass)
-    omega_max, _, _ = lanczos_max(lambda X: op.apply(X)[0], s, tol=lanczos_tol)
-    dt_crit = 2.0 / omega_max
-    return {"omega_max": omega_max, "dt_crit": dt_crit, "dt": gamma * dt_crit}
+    mat = _lib.material_id(material)
+    if mat == 0:
+        if state is not None:
+            raise ValueError("a state is given with the linear material, whose operator does not depend on it")
+        omega_max, _, _ = lanczos_max(lambda X: op.apply(X)[0], s, tol=lanczos_tol)
+        dt_crit = 2.0 / omega_max
+        return {"omega_max": omega_max, "dt_crit": dt_crit, "dt": gamma * dt_crit}
+    if state is None:
+        raise ValueError("a nonlinear material needs the state at which its tangent is taken")
+    state = state.reshape(-1).contiguous()
+    n_inverted = op.tangent_apply(state, s, material, count=True)[1]
+    omega_max, res, _ = lanczos_max(lambda X: op.tangent_apply(state, X.reshape(-1), material).reshape(1, -1), s, tol=lanczos_tol)
+    dt_crit = 2.0 / omega_max if omega_max > 0 else math.inf
+    return {"omega_max": omega_max, "dt_crit": dt_crit, "dt": gamma * dt_crit, "material": str(material).replace("-", "_"),
+            "n_inverted": n_inverted, "lanczos_residual": res}
 
 
 def device_lowest_modes(op: ModalOperator, points, cells, lmd, mu, k, **kw):

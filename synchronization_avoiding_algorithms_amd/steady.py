@@ -124,6 +124,143 @@ def steady_solve_operator(op, b, tol=1e-12, max_iter=None, check_every=25):
     return (d[0] if vec else d), it, rel
 
 
+def _tangent_pcg(apply_kt, r0, minv, rtol, max_iter, check_every):
+    """The Jacobi-PCG loop of :func:`steady_solve_operator` on one right-hand side ``r0`` with the operator ``apply_kt`` (a
+    tangent, which need not be positive definite), from 0 until ``|r| <= rtol |r0|``.  It stops at the first direction with
+    ``p . K_T p <= 0`` and returns the iterate so far, or the preconditioned residual ``minv r0`` when it has made no step.
+    The curvature test stays on the device; the host looks every ``check_every`` iterations.  ``(x, iterations)``."""
+    import torch
+
+    x = torch.zeros_like(r0)
+    r = r0.clone()
+    z = minv * r
+    z0 = z
+    p = z.clone()
+    rz = torch.dot(r, z)
+    target = rtol * float(torch.linalg.vector_norm(r0))
+    alive = torch.ones((), dtype=torch.float64, device=r0.device)
+    steps = torch.zeros((), dtype=torch.float64, device=r0.device)
+    it = 0
+    while it < max_iter:
+        ap = apply_kt(p)
+        pap = torch.dot(p, ap)
+        alive = alive * (pap > 0)
+        alpha = alive * rz / torch.where(pap > 0, pap, 1.0)
+        x = x + alpha * p
+        r = r - alpha * ap
+        steps = steps + alive
+        z = minv * r
+        rz_new = torch.dot(r, z)
+        p = z + torch.where(rz > 0, rz_new / torch.where(rz > 0, rz, 1.0), 0.0) * p
+        rz = rz_new
+        it += 1
+        if it % check_every == 0 or it == 1:     # the only host synchronisations (the first: a start without curvature)
+            if float(alive) == 0.0 or float(torch.linalg.vector_norm(r)) <= target:
+                break
+    return (x if float(steps) > 0 else z0), it
+
+
+def newton_solve_operator(op, b, material, u0=None, tol=1e-10, max_newton=50, load_steps=1, check_every=25):
+    """The static equilibrium ``f_int(u) = b`` of a finite-strain material (``svk``, ``neo_hookean``) on an operator handle
+    (:class:`modal.ModalOperator`) of either order: ``|f_int(u) - b| <= tol |b|`` on the free dofs, ``u = 0`` on the others.
+
+    Per load fraction ``k / load_steps`` an inexact Newton iteration (at most ``max_newton`` each): the system ``K_T(u) du =
+    b_k - f_int(u)`` by the Jacobi-PCG loop of :func:`steady_solve_operator` on ``op.tangent_apply``, preconditioned with
+    ``op.diagonal()`` of the linear ``K``, to a forcing tolerance that shrinks with the residual (Eisenstat-Walker's second
+    choice, ``0.9 (|r_k| / |r_k-1|)^2`` in ``[tol-limited floor, 0.1]``); CG stops at the first ``p . K_T p <= 0`` and hands
+    back the iterate so far, or the preconditioned residual if it has none.  Then a backtracking Armijo line search on ``Pi(u)
+    - b_k . u`` with ``Pi`` the sum of ``energy_elem`` of ``op.internal_force(..., energy=True)``; a trial in which neo-Hooke
+    finds an inverted element is rejected like an increase.  Two energies closer than their round-off (``8 eps (|Pi| + |b .
+    u|)``) count as equal, since near the solution the decrease is of the order of the residual squared.  Intermediate load
+    fractions are solved to ``max(tol, 1e-6)`` only: they are starting points.  The iteration also ends, unconverged, when
+    three steps in a row were accepted inside that round-off without lowering the residual: ``f_int`` is then at its own
+    round-off, which on a slender beam is far above ``eps`` - the nodal displacements are mostly rigid motion of the element
+    (``eps (L/h)^4`` of ``|b|``, about 1e-9 on a 25 : 1 cantilever).
+
+    Returns ``(u (n_dof,) NumPy, info)``; ``info``: ``converged``, ``newton_iterations``, ``cg_iterations``, ``residual`` (``|f_int(u)
+    - b| / |b|`` recomputed with ``internal_force`` at the end), ``residual_history`` (one per Newton iteration, relative to the
+    full ``|b|``), ``load_steps``, ``n_inverted`` (at the returned ``u``).  It does not raise when it does not converge."""
+    import torch
+
+    from . import _lib
+
+    if _lib.material_id(material) == 0:
+        raise ValueError("newton_solve_operator is for svk and neo_hookean; the linear solve is steady_solve_operator")
+    if int(load_steps) < 1:
+        raise ValueError("load_steps must be >= 1")
+    B = b if torch.is_tensor(b) else torch.as_tensor(np.asarray(b, dtype=np.float64))
+    B = B.to(device=op.torch_device, dtype=torch.float64).reshape(-1) * op.free
+    if B.numel() != op.n_dof:
+        raise ValueError(f"b must hold {op.n_dof} values")
+    if u0 is None:
+        u = torch.zeros_like(B)
+    else:
+        u = u0 if torch.is_tensor(u0) else torch.as_tensor(np.asarray(u0, dtype=np.float64))
+        u = u.to(device=op.torch_device, dtype=torch.float64).reshape(-1) * op.free
+    diag_k, _ = op.diagonal(k=True, m=False)
+    minv = torch.where(diag_k > 0, op.free / torch.where(diag_k > 0, diag_k, 1.0), op.free)
+    bnorm = float(torch.linalg.vector_norm(B))
+    info = {"converged": True, "newton_iterations": 0, "cg_iterations": 0, "residual": 0.0, "residual_history": [],
+            "load_steps": int(load_steps), "n_inverted": 0}
+    if bnorm == 0.0 and u0 is None:
+        return np.zeros(op.n_dof), info
+    scale = bnorm if bnorm > 0 else 1.0
+    eps = float(np.finfo(np.float64).eps)
+    max_cg = 20 * op.n_dof
+
+    def state(x, bk):
+        f, en, n_inv = op.internal_force(x, material, energy=True)
+        pi, work = float(en.sum()), float(torch.dot(bk, x))
+        return (bk - f) * op.free, pi - work, 8.0 * eps * (abs(pi) + abs(work)), n_inv
+
+    for k in range(1, int(load_steps) + 1):
+        bk = B * (k / int(load_steps))
+        goal = (tol if k == int(load_steps) else max(tol, 1e-6)) * scale
+        r, phi, noise, n_inv = state(u, bk)
+        rnorm, previous, done, stalled = float(torch.linalg.vector_norm(r)), None, False, 0
+        for _ in range(int(max_newton)):
+            if rnorm <= goal:
+                done = True
+                break
+            eta = 0.1 if previous is None else min(0.1, 0.9 * (rnorm / previous) ** 2)
+            eta = max(eta, 0.1 * goal / rnorm)
+            du, its = _tangent_pcg(lambda p: op.tangent_apply(u, p, material), r, minv, eta, max_cg, check_every)
+            info["cg_iterations"] += its
+            slope = -float(torch.dot(r, du))
+            if not slope < 0.0:                  # not a descent direction: steepest descent in the preconditioner's metric
+                du = minv * r
+                slope = -float(torch.dot(r, du))
+            t, accepted = 1.0, None
+            for _ in range(40):
+                trial = u + t * du
+                rt, phit, noiset, inv_t = state(trial, bk)
+                if inv_t == 0 and phit <= phi + 1e-4 * t * slope + max(noise, noiset):
+                    accepted = (trial, rt, phit, noiset, inv_t)
+                    in_noise = phit > phi + 1e-4 * t * slope
+                    break
+                t *= 0.5
+            info["newton_iterations"] += 1
+            if accepted is None:
+                break
+            previous = rnorm
+            u, r, phi, noise, n_inv = accepted
+            rnorm = float(torch.linalg.vector_norm(r))
+            info["residual_history"].append(rnorm / scale)
+            stalled = stalled + 1 if in_noise and rnorm >= previous else 0
+            if stalled >= 3:                     # the residual sits at the round-off of f_int: no step can lower it
+                break
+        else:
+            done = rnorm <= goal
+        if not done:
+            info["converged"] = False
+            break
+    f, _, n_inv = op.internal_force(u, material, energy=True)
+    info["residual"] = float(torch.linalg.vector_norm((B - f) * op.free)) / scale
+    info["n_inverted"] = int(n_inv)
+    info["converged"] = bool(info["converged"] and info["residual"] <= tol and n_inv == 0)
+    return u.cpu().numpy(), info
+
+
 def write_vtk_point_data(path, points, cells, displacement):
     """Legacy-VTK file with the mesh and the point data ``displacement-x/-y/-z`` - the arrays the reference hands to
     ``meshio.write_points_cells`` at ``Data_prepare.py:165-168`` (ASCII here).  4-column cells are written as VTK type 10,
