@@ -658,6 +658,56 @@ int saa_operator_stepper_set_material(saa_operator_stepper *st, int32_t material
 int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int64_t *first_step /* -1: none */);
 
 /*
+ * Finite-strain stress recovery (csrc/saa_stress_fs.hip): what saa_operator_stress / saa_operator_stress_p2 are to the linear
+ * material, for the two materials above on a handle of either order.  At each point of the K rule (nq = 1 on an order-1
+ * handle, the four Gauss points on an order-2 handle) H = grad_X x, formed as the force pass of that order forms it; x is read
+ * as given: the Dirichlet mask is NOT applied, as in the linear stress entries.  With F = I + H, A = cof(H):
+ *     J - 1 = tr H + tr A + det H,   det_f = 1 + (J - 1),   ln J = log1p(J - 1),
+ *     G = F^-T - I = (A - H^T - (tr A + det H) I) / J   (never from an inverse of I + H)
+ *   SAA_MATERIAL_SVK          E = (H + H^T + H^T H)/2,  S = lambda tr(E) I + 2 mu E,  sigma = F S F^T / J,
+ *                             W = lambda/2 tr(E)^2 + mu E:E
+ *   SAA_MATERIAL_NEO_HOOKEAN  S = -mu (G + G^T + G^T G) + lambda ln J (I + G + G^T + G^T G),
+ *                             sigma = (mu (H + H^T + H H^T) + lambda ln J I) / J,
+ *                             W = mu/2 (F:F - 3) - mu ln J + lambda/2 (ln J)^2, evaluated as saa_operator_internal_force does
+ * measure = SAA_STRESS_PK2 writes S (second Piola-Kirchhoff, reference configuration), SAA_STRESS_CAUCHY sigma; F S = P of
+ * saa_operator_internal_force and P F^T / J = sigma.  Both vanish under a rigid motion to the rounding of x.  von_mises is
+ * sqrt(((s_xx - s_yy)^2 + (s_yy - s_zz)^2 + (s_zz - s_xx)^2)/2 + 3 (s_yz^2 + s_xz^2 + s_xy^2)) of the chosen measure, and
+ * energy[e] = sum_q w_q |detJ_q| W(F_q), the stored energy of the element (that of saa_operator_internal_force).
+ *
+ * Layouts are those of the linear entries, so that saa_operator_nodal_average / saa_operator_stress_error (order 1) and
+ * saa_operator_nodal_stress_p2 / saa_operator_stress_error_p2 (order 2) take the fields unchanged: Voigt rows xx, yy, zz, yz,
+ * xz, xy (no factor on the shear rows: these are stresses); m = 1..16 column-major columns;
+ *   order 1: stress[column][6 e + c],          von_mises, det_f[column][e],        energy[column][e]
+ *   order 2: stress[column][24 e + 6 q + c],   von_mises, det_f[column][4 e + q],  energy[column][e]
+ * energy_total, von_mises_max and von_mises_argmax (a point index nq e + q, the lowest on ties; -1 and 0.0 when no point
+ * holds a value) have m entries.  Any output may be NULL; with every output NULL nothing is launched.
+ *
+ * Inversion.  An element with !(J > 0) at any of its points (NaN included) is inverted for a column under neo-Hooke with
+ * either measure and under either material with the Cauchy measure; SVK with PK2 does not look at J.  An inverted element
+ * writes 0 to stress, von_mises and energy of that column, is left out of the column's total and maximum, and is counted in
+ * n_inverted[column] (host, m entries, or NULL).  Asking for the count synchronises the stream; otherwise the call is
+ * enqueued on the handle's stream.  det_f always holds the computed value, so that the inverted points can be found.  One
+ * column's inversion or NaN does not touch another column.  The per-column counters are device words updated with integer
+ * atomics; there are no floating-point atomics, every output is bitwise repeatable and a column's results do not depend on
+ * the other columns of the call.  An order-2 handle reads its reduced geometry table (made on first need, see above).
+ *
+ * SAA_E_ARG with the entry named in saa_last_error, before the handle or the device is looked at: a material outside {1, 2}
+ * (the linear material has saa_operator_stress and saa_operator_stress_p2); a measure outside {0, 1}; then a null handle or a
+ * null x_dev; m outside 1..16; a leading dimension below its minimum (3 * n_nodes, 6 * nq * n_elems, nq * n_elems, nq *
+ * n_elems, n_elems) for a non-null output.
+ */
+#define SAA_STRESS_PK2 0
+#define SAA_STRESS_CAUCHY 1
+int saa_operator_stress_finite(saa_operator *op, int32_t material, int32_t measure, int32_t m,
+                               const double *x_dev, int64_t ldx,
+                               double *stress_dev, int64_t ld_stress,      /* 6*nq*n_elems per column */
+                               double *von_mises_dev, int64_t ld_vm,       /* nq*n_elems per column  */
+                               double *det_f_dev, int64_t ld_det,          /* nq*n_elems per column  */
+                               double *energy_dev, int64_t ld_elem,        /* n_elems per column     */
+                               double *energy_total_dev, double *von_mises_max_dev, int32_t *von_mises_argmax_dev,
+                               int64_t *n_inverted /* host, m entries, or NULL */);
+
+/*
  * Shared-node predictor: the per-rank LSTM encoder-decoder of Tools/DNN_tools.py:16-98 (2-layer bidirectional encoder of
  * width hidden_size, decoder LSTM of width 2*hidden_size + Linear) evaluated for all filter_size phase offsets of one
  * prediction window - what Tools/DNN_prediction.py:38-55 (`encoder_decoder_predictor`) computes with filter_size

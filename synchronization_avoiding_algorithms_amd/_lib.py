@@ -18,13 +18,16 @@ LIB_PATH = os.environ.get("SAA_LIB_PATH") or os.path.join(_HERE, "libsaa_hip.so"
 DIAG_LIB_PATH = os.path.join(_HERE, "libsaa_hip_diag.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "saa_hip.h")
 SOURCES = ["saa_plan.cpp", "saa_partition.cpp", "saa_kernels.hip", "saa_setup.hip", "saa_predictor.hip", "saa_topology.hip", "saa_modal.hip",
-           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_api.cpp"]
+           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_stress_fs.hip",
+           "saa_api.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-ldl"]
 
 ABI_VERSION = 16  # what saa_abi_version() of a matching library returns (include/saa_hip.h)
 SAA_OK, SAA_E_ARG, SAA_E_HIP, SAA_E_STATE, SAA_E_CAPACITY = 0, -1, -2, -3, -4
 #: SAA_MATERIAL_* of include/saa_hip.h by the names the Python layer and the driver use
 MATERIALS = {"linear": 0, "svk": 1, "neo_hookean": 2}
+#: SAA_STRESS_* of include/saa_hip.h
+MEASURES = {"pk2": 0, "cauchy": 1}
 
 
 def material_id(name) -> int:
@@ -177,6 +180,9 @@ SIGNATURES = {
     "saa_operator_stepper_set_energy": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),
     "saa_operator_internal_force": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "saa_operator_tangent_apply": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "saa_operator_stress_finite": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "saa_operator_stepper_set_material": (C.c_int, [_H, C.c_int32]),
     "saa_operator_stepper_inverted": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }

@@ -25,6 +25,7 @@
 #include "saa_plan.h"
 #include "saa_predictor.h"
 #include "saa_stress.h"
+#include "saa_stress_fs.h"
 #include "saa_stress_p2.h"
 #include "saa_setup.h"
 #include "saa_topology.h"
@@ -2181,6 +2182,39 @@ int saa_operator_stress_error_p2(saa_operator *op, int32_t m, const double *sigm
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
   return stress_done(saa::p2_stress_error(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
                                           eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev),
+                     name);
+}
+
+int saa_operator_stress_finite(saa_operator *op, int32_t material, int32_t measure, int32_t m, const double *x_dev, int64_t ldx,
+                               double *stress_dev, int64_t ld_stress, double *von_mises_dev, int64_t ld_vm, double *det_f_dev,
+                               int64_t ld_det, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
+                               double *von_mises_max_dev, int32_t *von_mises_argmax_dev, int64_t *n_inverted) {
+  static const std::string name = "saa_operator_stress_finite";
+  if (material != SAA_MATERIAL_SVK && material != SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, name + ": material " + std::to_string(material) +
+                               " is neither 1 (svk) nor 2 (neo_hookean); the linear material has saa_operator_stress and "
+                               "saa_operator_stress_p2");
+  if (measure != SAA_STRESS_PK2 && measure != SAA_STRESS_CAUCHY)
+    return fail(SAA_E_ARG, name + ": measure " + std::to_string(measure) + " is neither 0 (pk2) nor 1 (cauchy)");
+  if (!op) return fail(SAA_E_ARG, name + ": null handle");
+  if (!x_dev) return fail(SAA_E_ARG, name + ": null displacement x_dev");
+  if (const int rc = stress_columns(m, name)) return rc;
+  if (!op->impl) return fail(SAA_E_ARG, name + ": null handle");  // (the first look at what op points to)
+  const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
+  const int64_t n_points = (saa::modal_order(op->impl) == 2 ? 4 : 1) * static_cast<int64_t>(saa::modal_n_elems(op->impl));
+  if (const int rc = stress_ld(name, "ldx", ldx, "3 * n_nodes", n_dof)) return rc;
+  if (stress_dev)
+    if (const int rc = stress_ld(name, "ld_stress", ld_stress, "6 * nq * n_elems", 6 * n_points)) return rc;
+  if (von_mises_dev)
+    if (const int rc = stress_ld(name, "ld_vm", ld_vm, "nq * n_elems", n_points)) return rc;
+  if (det_f_dev)
+    if (const int rc = stress_ld(name, "ld_det", ld_det, "nq * n_elems", n_points)) return rc;
+  if (energy_dev)
+    if (const int rc = stress_ld(name, "ld_elem", ld_elem, "n_elems", saa::modal_n_elems(op->impl))) return rc;
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  return stress_done(saa::stress_finite(op->impl, material, measure, m, x_dev, ldx, stress_dev, ld_stress, von_mises_dev, ld_vm,
+                                        det_f_dev, ld_det, energy_dev, ld_elem, energy_total_dev, von_mises_max_dev,
+                                        von_mises_argmax_dev, n_inverted),
                      name);
 }
 

@@ -41,6 +41,7 @@ struct ModalOp {
   double *geom = nullptr;    // [40][n_elems]
   uint32_t *bits = nullptr;  // n_elems
   unsigned long long *fs_count = nullptr;  // saa_operator_internal_force: the two counter words of the call (saa_opfs.hip)
+  unsigned long long *st_inverted = nullptr;  // saa_operator_stress_finite: inverted elements per column (saa_stress_fs.hip)
 };
 
 // The node pass of saa_modal.hip on any [column][pair][3] contributions of this handle's CSR: y[j][3v + c] = sum of node

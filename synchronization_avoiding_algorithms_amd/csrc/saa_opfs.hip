@@ -34,27 +34,6 @@ namespace saa {
 
 namespace {
 
-// y - log1p(y) of y > -1, log1p_y = log1p(y) as the caller has it.  Below |y| = 1/16 the difference cancels (relative error
-// 2 eps/|y|): there the series y^2 (1/2 - y/3 + ... - y^13/15) by Horner's rule, whose first dropped term is 2^-59 of y^2/2.
-__device__ __forceinline__ double opfs_x_minus_log1p(double y, double log1p_y) {
-  if (!(fabs(y) < 0.0625)) return y - log1p_y;
-  double p = -1.0 / 15.0;
-  p = p * y + 1.0 / 14.0;
-  p = p * y - 1.0 / 13.0;
-  p = p * y + 1.0 / 12.0;
-  p = p * y - 1.0 / 11.0;
-  p = p * y + 1.0 / 10.0;
-  p = p * y - 1.0 / 9.0;
-  p = p * y + 1.0 / 8.0;
-  p = p * y - 1.0 / 7.0;
-  p = p * y + 1.0 / 6.0;
-  p = p * y - 1.0 / 5.0;
-  p = p * y + 1.0 / 4.0;
-  p = p * y - 1.0 / 3.0;
-  p = p * y + 0.5;
-  return y * y * p;
-}
-
 // P (first Piola-Kirchhoff) and, with ENERGY, W of the material MAT at displacement gradient h.  false: MAT is neo-Hooke and
 // !(det F > 0); P and W are then not to be used.
 template <int MAT, bool ENERGY>

@@ -5,7 +5,8 @@
 reference's ``Eigen_mode``), :func:`dynamics` (the explicit run of one whole mesh on one GPU for either element order;
 the reference has none for ``p = 2``), :func:`stress` (stress recovery from the saved trajectories) and :func:`estimate` (the
 Zienkiewicz-Zhu estimate of the stress error of the mesh, the scale for the error of the modelled run; neither has a
-counterpart in the reference); same artefact names under ``Results/`` and
+counterpart in the reference; :func:`stress_finite` and :func:`estimate_finite` are the two at finite strain, on the run of
+:func:`dynamics` with a nonlinear material); same artefact names under ``Results/`` and
 ``Distributed_save/``, same constants by default.  Launch like the reference's
 ``mpirun -np P python3 X.py``:
 
@@ -48,7 +49,10 @@ PATHS = dict(local_nodes="Results/Rankwised_Data/Rank={r}_local_nodes.csv",
              estimate_vtk="Results/Stress/Estimate-col-{j}.vtk",
              stress_vtk_p2="Results/Stress/Stress-order2-col-{j}.vtk",
              stress_history_p2="Results/Stress/history-order2.npz",
-             estimate_vtk_p2="Results/Stress/Estimate-order2-col-{j}.vtk")
+             estimate_vtk_p2="Results/Stress/Estimate-order2-col-{j}.vtk",
+             stress_vtk_fs="Results/Stress/Stress-{material}-order{p}-col-{j}.vtk",
+             stress_history_fs="Results/Stress/history-{material}-order{p}.npz",
+             estimate_vtk_fs="Results/Stress/Estimate-{material}-order{p}-col-{j}.vtk")
 
 
 def _dist_env():
@@ -205,7 +209,10 @@ def steady_state_nonlinear(mesh, out_dir=".", device=0, material="svk", order=1,
     ``steady_state --order 2``): Newton-PCG on the operator handle (:func:`steady.newton_solve_operator`), written to
     ``Results/Static/steady_distributed.vtk`` like the linear solution.  Returns ``(path, d (3n, 1), report)``; the report
     holds the order, the sizes, the material, the solver's ``info`` without its history, ``max_abs_d`` and the mean
-    ``tip_deflection``, and under ``linear`` the same two figures of ``K d = F``.  Raises :class:`NotConverged` (after writing
+    ``tip_deflection``, and under ``linear`` the same two figures of ``K d = F``; of the converged state also the largest
+    point von Mises value of the Cauchy stress (``von_mises_max``) with its ``element``, the stored energy
+    (``strain_energy``) and ``min_det_f`` (:mod:`stress`), and the file holds the recovered Cauchy stress ``sigma-xx .. -xy``
+    and its ``von-mises`` as point data after the displacement.  Raises :class:`NotConverged` (after writing
     nothing) when the iteration does not reach ``tol``.  The default ``tol`` is 1e-8 of ``|F|`` in the TRUE residual (the
     linear driver's 1e-12 is the residual of the CG recurrence): on the 25 : 1 beam ``f_int`` itself is only good to about
     ``eps (L/h)^4`` = 1e-9 of ``|F|`` in float64, because an element's nodal displacements are mostly its rigid motion."""
@@ -213,6 +220,7 @@ def steady_state_nonlinear(mesh, out_dir=".", device=0, material="svk", order=1,
     from .mesh import plane_nodes
     from .modal import ModalOperator
     from .steady import newton_solve_operator, steady_solve_operator, write_vtk_point_data
+    from .stress import VOIGT, QuadraticStressRecovery, StressRecovery, von_mises
 
     if order not in (1, 2):
         raise ValueError("order must be 1 or 2")
@@ -239,12 +247,23 @@ def steady_state_nonlinear(mesh, out_dir=".", device=0, material="svk", order=1,
         report = {"order": op.order, "n_nodes": op.n_nodes, "n_elems": op.n_elems, "n_free_dofs": int(op.free.sum().item()),
                   "material": str(material).replace("-", "_"), "fz": float(fz),
                   **{k: v for k, v in info.items() if k != "residual_history"}, **figures(d), "linear": figures(d_lin)}
+        if info["converged"]:
+            import torch
+
+            rec = (QuadraticStressRecovery if order == 2 else StressRecovery)(None, None, None, None, operator=op)
+            el = rec.element(torch.as_tensor(np.asarray(d, dtype=np.float64).reshape(-1), device=op.torch_device),
+                             energy=False, material=material, measure="cauchy")
+            nodal = rec.nodal(el["sigma"]).cpu().numpy()
+            report.update({"von_mises_max": float(el["von_mises_max"]),
+                           "element": int(el["von_mises_argmax"]) // (4 if order == 2 else 1),
+                           "strain_energy": float(el["energy_total"]), "min_det_f": float(el["det_f"].min())})
     if not info["converged"]:
         raise NotConverged(f"steady_state --material {material}: Newton stopped after {info['newton_iterations']} iterations at "
                            f"a relative residual of {info['residual']:.3e} (tolerance {tol:g}, {info['n_inverted']} inverted "
                            "elements); try more --load-steps", report)
     d = d.reshape(-1, 1)
-    return write_vtk_point_data(os.path.join(out_dir, STEADY_PATH), points, cells, d), d, report
+    extra = {**{f"sigma-{c}": nodal[:, a] for a, c in enumerate(VOIGT)}, "von-mises": von_mises(nodal)}
+    return write_vtk_point_data(os.path.join(out_dir, STEADY_PATH), points, cells, d, extra), d, report
 
 
 def shared_extraction(out_dir=".", rank=0):
@@ -354,12 +373,18 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     return path, report
 
 
+def _host_value(v):
+    """A tensor of a recovery's result as a NumPy array; anything else (``measure``) as it is."""
+    return v.cpu().numpy() if hasattr(v, "cpu") else v
+
+
 def _device_recovery(device=0):
     """The GPU side of :func:`stress` and :func:`estimate`, and its only one: a factory ``make(points, cells, lmd, mu)`` of
     objects with NumPy-in / NumPy-out ``element(X (m, n_dof))`` (the dict of :meth:`stress.StressRecovery.element`),
     ``nodal(E (m, n_elems, k))``, ``error(sigma_elem, nodal=None, other=None)`` (the dict of
     :meth:`stress.StressRecovery.error`), ``history(traj (n_dof, n_cols))`` and ``close()`` on
-    :class:`stress.StressRecovery`.  Tests pass a NumPy stand-in with the same methods."""
+    :class:`stress.StressRecovery`.  Tests pass a NumPy stand-in with the same methods.  ``element`` and ``history`` hand
+    ``material=`` and ``measure=`` on; only :func:`stress_finite` and :func:`estimate_finite` give them."""
     import torch
 
     from .stress import StressRecovery
@@ -371,8 +396,8 @@ def _device_recovery(device=0):
         def _dev(self, a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.rec.torch_device)
 
-        def element(self, X):
-            return {k: v.cpu().numpy() for k, v in self.rec.element(self._dev(X)).items()}
+        def element(self, X, **finite):
+            return {k: _host_value(v) for k, v in self.rec.element(self._dev(X), **finite).items()}
 
         def nodal(self, E):
             return self.rec.nodal(self._dev(E)).cpu().numpy()
@@ -382,8 +407,8 @@ def _device_recovery(device=0):
                                  other=None if other is None else self._dev(other))
             return {k: v.cpu().numpy() for k, v in res.items()}
 
-        def history(self, traj):
-            return {k: v.cpu().numpy() for k, v in self.rec.history(traj).items()}
+        def history(self, traj, **finite):
+            return {k: _host_value(v) for k, v in self.rec.history(traj, **finite).items()}
 
         def close(self):
             self.rec.close()
@@ -676,8 +701,8 @@ def _device_recovery_p2(device=0):
         def _dev(self, a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.rec.torch_device)
 
-        def element(self, X):
-            return {k: v.cpu().numpy() for k, v in self.rec.element(self._dev(X)).items()}
+        def element(self, X, **finite):
+            return {k: _host_value(v) for k, v in self.rec.element(self._dev(X), **finite).items()}
 
         def nodal(self, sigma):
             return self.rec.nodal(self._dev(sigma)).cpu().numpy()
@@ -687,8 +712,8 @@ def _device_recovery_p2(device=0):
                                  other=None if other is None else self._dev(other))
             return {k: v.cpu().numpy() for k, v in res.items()}
 
-        def history(self, traj):
-            return {k: v.cpu().numpy() for k, v in self.rec.history(traj).items()}
+        def history(self, traj, **finite):
+            return {k: _host_value(v) for k, v in self.rec.history(traj, **finite).items()}
 
         def close(self):
             self.rec.close()
@@ -696,21 +721,22 @@ def _device_recovery_p2(device=0):
     return _Host
 
 
-def _load_p2_run(mesh, out_dir, columns):
-    """What :func:`stress_p2` and :func:`estimate_p2` read: the mesh with 10-node cells (elevated like ``dynamics --order
-    2``), the trajectory ``Results/Dynamics/Displacement_order2.hdf5`` under ``out_dir`` with 3 rows per node, and
-    ``columns`` resolved against its saved columns (negative = from the end)."""
-    mesh = _quadratic(mesh)
+def _load_run(mesh, out_dir, columns, order):
+    """The whole-mesh run of ``dynamics --order {order}``: the mesh with its 4- or 10-node cells (order 2: elevated like
+    ``dynamics --order 2``), the trajectory ``Results/Dynamics/Displacement_order{order}.hdf5`` under ``out_dir`` with 3 rows
+    per node, and ``columns`` resolved against its saved columns (negative = from the end)."""
+    if order == 2:
+        mesh = _quadratic(mesh)
     points = np.asarray(mesh.points, dtype=np.float64)
-    cells = np.asarray(mesh.tets10, dtype=np.int64)
-    path = os.path.join(out_dir, PATHS["dynamics"].format(p=2))
+    cells = np.asarray(mesh.tets10 if order == 2 else mesh.tets, dtype=np.int64)
+    path = os.path.join(out_dir, PATHS["dynamics"].format(p=order))
     try:
         traj = np.asarray(rio.load_displacement(path), dtype=np.float64)
     except FileNotFoundError as exc:
-        raise FileNotFoundError(f"{exc}: run dynamics --order 2 first") from None
+        raise FileNotFoundError(f"{exc}: run dynamics --order {order} first") from None
     if traj.ndim != 2 or traj.shape[0] != 3 * len(points):
         raise ValueError(f"{path}: {traj.shape[0] if traj.ndim else 0} rows, expected 3 * {len(points)} = {3 * len(points)} "
-                         "(3 per node of the elevated mesh)")
+                         + ("(3 per node of the elevated mesh)" if order == 2 else "(3 per node)"))
     n_cols = traj.shape[1]
     cols = []
     for j in columns:
@@ -719,6 +745,11 @@ def _load_p2_run(mesh, out_dir, columns):
             raise ValueError(f"column {j} out of range for {n_cols} saved columns")
         cols.append(jj)
     return points, cells, traj, n_cols, cols
+
+
+def _load_p2_run(mesh, out_dir, columns):
+    """What :func:`stress_p2` and :func:`estimate_p2` read: :func:`_load_run` of order 2."""
+    return _load_run(mesh, out_dir, columns, 2)
 
 
 def _p2_point_data(traj_cols, nodal):
@@ -823,6 +854,139 @@ def estimate_p2(mesh, out_dir=".", columns=(-1,), vtk=True, device=0, E=None, nu
     return report
 
 
+def _finite_setup(mesh, out_dir, columns, material, order, device, E, nu, recovery):
+    """What :func:`stress_finite` and :func:`estimate_finite` share: the material's name, the Lame constants, the recovery
+    factory of ``order``, the run of ``dynamics --order {order}`` and the output paths."""
+    from . import fem_setup as fs
+    from ._lib import material_id
+
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    if material_id(material) == 0:
+        raise ValueError("stress_finite / estimate_finite are for svk and neo_hookean; the linear material has stress, "
+                         "stress_p2, estimate and estimate_p2")
+    material = str(material).replace("-", "_")
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    make = recovery if recovery is not None else (_device_recovery_p2 if order == 2 else _device_recovery)(device)
+    run = _load_run(mesh, out_dir, columns, order)
+    paths = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+    return material, lmd, mu, make, run, paths
+
+
+def _finite_column(res, i, j, order, points, cells, centroid, shape4):
+    """The report entry of column ``j`` (row ``i`` of ``res``): the keys of the linear driver of that order, then ``material``'s
+    companions ``measure``, ``n_inverted`` and ``min_det_f``."""
+    nq = 4 if order == 2 else 1
+    e, q = divmod(int(res["von_mises_argmax"][i]), nq)
+    entry = {"column": j, "strain_energy": float(res["energy_total"][i]), "von_mises_max": float(res["von_mises_max"][i]),
+             "element": e}
+    if order == 2:
+        entry.update({"gauss_point": q, "position": [float(c) for c in shape4[q] @ points[cells[e]]]})
+    entry.update({"centroid": [float(c) for c in centroid[e]], "measure": res["measure"],
+                  "n_inverted": int(res["n_inverted"][i]), "min_det_f": float(np.min(res["det_f"][i]))})
+    return entry
+
+
+def _finite_cell_data(res, i, ne):
+    """Cell data of one column: the largest point von Mises, ``W_e`` and the smallest ``det F`` of every element."""
+    return {"von-mises-max": np.asarray(res["von_mises"][i]).reshape(ne, -1).max(axis=1), "energy": res["energy"][i],
+            "det-f-min": np.asarray(res["det_f"][i]).reshape(ne, -1).min(axis=1)}
+
+
+def stress_finite(mesh, out_dir=".", columns=(-1,), material="svk", measure="cauchy", order=1, history=False, vtk=True,
+                  device=0, E=None, nu=None, recovery=None):
+    """:func:`stress` at finite strain (``material``: ``svk`` or ``neo_hookean``; ``measure``: ``cauchy`` or ``pk2``), for
+    either element order: the whole mesh on one GPU, the displacement of ``dynamics --order {order} --material ...``
+    (``Results/Dynamics/Displacement_order{order}.hdf5`` under ``out_dir``).  For every saved column in ``columns`` reports
+    the stored energy (``strain_energy``), the largest point von Mises stress of ``measure`` with its element (order 2: Gauss
+    point and position too), the number of inverted elements and the smallest ``det F``, and writes
+    ``Results/Stress/Stress-{material}-order{order}-col-{j}.vtk`` (point data: displacement, the recovered stress and its von
+    Mises; cell data: the largest point von Mises, ``W_e`` and the smallest ``det F``) unless ``vtk`` is False; ``history``
+    writes every column's stored energy, von Mises maximum, inverted count and smallest ``det F`` to
+    ``Results/Stress/history-{material}-order{order}.npz``.  There is no modelled finite-strain run.  Returns the report that
+    the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` and :func:`_device_recovery_p2` (default: the GPU)."""
+    from .Tools.Qudrature import Gauss_Legendre
+    from .Tools.Shape_function_Deriv import Shape_Function
+
+    material, lmd, mu, make, (points, cells, traj, n_cols, cols), p = _finite_setup(mesh, out_dir, columns, material, order,
+                                                                                     device, E, nu, recovery)
+    ne, nn, m, nq = len(cells), len(points), len(cols), 4 if order == 2 else 1
+    shape4 = np.array([Shape_Function(2, x) for x in Gauss_Legendre(2)[0]]) if order == 2 else None
+    centroid = points[cells[:, :4]].mean(axis=1)
+    names = dict(material=material, p=order)
+
+    report = {"order": order, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "material": material,
+              "measure": str(measure), "columns": [], "files": [], "history": None}
+    rec = make(points, cells, lmd, mu)
+    try:
+        if m:
+            X = np.ascontiguousarray(traj[:, cols].T)
+            res = rec.element(X, material=material, measure=measure)
+            nodal = rec.nodal(res["sigma"]) if vtk else None
+            for i, j in enumerate(cols):
+                report["columns"].append({**_finite_column(res, i, j, order, points, cells, centroid, shape4),
+                                          "material": material})
+                if vtk:
+                    report["files"].append(rio.write_vtk_fields(p["stress_vtk_fs"].format(j=j, **names), points, cells,
+                                                                _p2_point_data(X[i], nodal[i]), _finite_cell_data(res, i, ne),
+                                                                title=f"{measure} stress, {material}, order {order}, saved column {j}"))
+        if history:
+            h = rec.history(traj, material=material, measure=measure)
+            arg = np.asarray(h["von_mises_argmax"], dtype=np.int64)
+            path = p["stress_history_fs"].format(**names)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            np.savez(path, columns=np.arange(n_cols), strain_energy=h["energy_total"], von_mises_max=h["von_mises_max"],
+                     von_mises_element=arg // nq, von_mises_gauss_point=arg % nq, n_inverted=h["n_inverted"],
+                     min_det_f=h["min_det_f"])
+            report["history"] = path
+    finally:
+        rec.close()
+    return report
+
+
+def estimate_finite(mesh, out_dir=".", columns=(-1,), material="svk", order=1, vtk=True, device=0, E=None, nu=None,
+                    recovery=None):
+    """:func:`estimate` at finite strain, on the run that :func:`stress_finite` reads, always with the second
+    Piola-Kirchhoff stress over the reference configuration: ``eta_e^2 = integral_0 (S* - S_h)^T D^-1 (S* - S_h) dV`` with
+    the recovered nodal field ``S*`` (the kernels of the linear estimate of that order).  For ``svk`` this is exactly the
+    energy norm of the Green-strain error; for ``neo_hookean`` ``D`` is the linearised material and ``eta`` a scale in its
+    norm.  For every saved column in ``columns`` reports ``eta``, ``energy_norm = sqrt(2 * stored energy)``, ``relative`` and
+    the element of the largest ``eta_e^2`` with its centroid, ``n_inverted`` and ``min_det_f``, and writes
+    ``Results/Stress/Estimate-{material}-order{order}-col-{j}.vtk`` (point data as :func:`stress_finite`, of PK2; cell data:
+    the largest point von Mises, ``W_e``, the smallest ``det F`` and ``eta2``) unless ``vtk`` is False."""
+    material, lmd, mu, make, (points, cells, traj, n_cols, cols), p = _finite_setup(mesh, out_dir, columns, material, order,
+                                                                                     device, E, nu, recovery)
+    ne, nn, m = len(cells), len(points), len(cols)
+    centroid = points[cells[:, :4]].mean(axis=1)
+
+    report = {"order": order, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "material": material,
+              "measure": "pk2", "columns": [], "files": []}
+    if not m:
+        return report
+    rec = make(points, cells, lmd, mu)
+    try:
+        X = np.ascontiguousarray(traj[:, cols].T)
+        res = rec.element(X, material=material, measure="pk2")
+        nodal = rec.nodal(res["sigma"])
+        zz = rec.error(res["sigma"], nodal=nodal)
+    finally:
+        rec.close()
+    for i, j in enumerate(cols):
+        eta2, w2 = float(zz["eta2_total"][i]), 2.0 * float(res["energy_total"][i])
+        e = int(zz["eta2_argmax"][i])
+        report["columns"].append({"column": j, "eta": float(np.sqrt(eta2)), "energy_norm": float(np.sqrt(w2)),
+                                  "relative": float(np.sqrt(eta2 / (w2 + eta2))) if w2 + eta2 > 0 else 0.0, "element": e,
+                                  "eta2_max": float(zz["eta2_max"][i]), "centroid": [float(c) for c in centroid[e]],
+                                  "material": material, "measure": "pk2", "n_inverted": int(res["n_inverted"][i]),
+                                  "min_det_f": float(np.min(res["det_f"][i]))})
+        if vtk:
+            cd = {**_finite_cell_data(res, i, ne), "eta2": zz["eta2"][i]}
+            report["files"].append(rio.write_vtk_fields(p["estimate_vtk_fs"].format(j=j, material=material, p=order), points,
+                                                        cells, _p2_point_data(X[i], nodal[i]), cd,
+                                                        title=f"stress error estimate, {material}, order {order}, saved column {j}"))
+    return report
+
+
 def _has_gpu():
     import torch
 
@@ -853,7 +1017,11 @@ def main(argv=None):
                     help="dynamics: the element pass - small-strain linear elasticity, or finite strain with the St. "
                          "Venant-Kirchhoff or the compressible neo-Hookean material.  dt stays gamma * 2/omega_max of the linear "
                          "operator at the reference configuration: under large stretch the stability limit moves and the "
-                         "stepper does not follow it")
+                         "stepper does not follow it.  stress, estimate: the finite-strain stress of that material on the "
+                         "whole-mesh run of dynamics (either order)")
+    ap.add_argument("--measure", choices=["cauchy", "pk2"], default="cauchy",
+                    help="stress --material svk / neo-hookean: the Cauchy or the second Piola-Kirchhoff stress (estimate "
+                         "always uses pk2)")
     ap.add_argument("--fz", type=float, default=0.5,
                     help="dynamics, steady_state --material: the amplitude of the load (0, -fz, -fz); at the default nothing "
                          "is nonlinear")
@@ -895,6 +1063,9 @@ def main(argv=None):
                      "on the whole mesh")
     if args.command == "steady_state" and args.load_steps < 1:
         ap.error("steady_state --load-steps must be >= 1")
+    if args.command in ("stress", "estimate") and args.material != "linear" and args.modeled:
+        ap.error(f"{args.command} --material {args.material} --modeled: there is no modelled finite-strain run (the predictor "
+                 "drives the linear material)")
     if args.command in ("stress", "estimate") and args.order == 2 and args.modeled:
         ap.error(f"{args.command} --order 2 --modeled: there is no modelled p = 2 run (the predictor drives linear elements)")
     rank, world, local = _dist_env()
@@ -917,12 +1088,20 @@ def main(argv=None):
             print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
+            if args.material != "linear":
+                print(json.dumps(estimate_finite(mesh, args.out, cols, material=args.material, order=args.order,
+                                                 vtk=not args.no_vtk, device=local)))
+                return
             if args.order == 2:
                 print(json.dumps(estimate_p2(mesh, args.out, cols, vtk=not args.no_vtk, device=local)))
                 return
             print(json.dumps(estimate(mesh, args.out, cols, modeled=args.modeled, vtk=not args.no_vtk, device=local)))
         else:
             cols = [int(c) for c in args.columns.split(",") if c.strip()]
+            if args.material != "linear":
+                print(json.dumps(stress_finite(mesh, args.out, cols, material=args.material, measure=args.measure,
+                                               order=args.order, history=args.history, vtk=not args.no_vtk, device=local)))
+                return
             if args.order == 2:
                 print(json.dumps(stress_p2(mesh, args.out, cols, history=args.history, vtk=not args.no_vtk, device=local)))
                 return

@@ -261,10 +261,11 @@ def newton_solve_operator(op, b, material, u0=None, tol=1e-10, max_newton=50, lo
     return u.cpu().numpy(), info
 
 
-def write_vtk_point_data(path, points, cells, displacement):
+def write_vtk_point_data(path, points, cells, displacement, extra=None):
     """Legacy-VTK file with the mesh and the point data ``displacement-x/-y/-z`` - the arrays the reference hands to
     ``meshio.write_points_cells`` at ``Data_prepare.py:165-168`` (ASCII here).  4-column cells are written as VTK type 10,
-    10-column cells (quadratic tetrahedra) as type 24."""
+    10-column cells (quadratic tetrahedra) as type 24.  ``extra``: further point scalars ``{name: (n,) array}``, written
+    after the displacement, which stays what it is without them."""
     import os
 
     points, cells = np.asarray(points, dtype=np.float64), np.asarray(cells)
@@ -283,4 +284,7 @@ def write_vtk_point_data(path, points, cells, displacement):
         for c, name in enumerate(("displacement-x", "displacement-y", "displacement-z")):
             fh.write(f"SCALARS {name} double 1\nLOOKUP_TABLE default\n")
             np.savetxt(fh, d[:, c], fmt="%.17g")
+        for name, a in (extra or {}).items():
+            fh.write(f"SCALARS {name} double 1\nLOOKUP_TABLE default\n")
+            np.savetxt(fh, np.asarray(a, dtype=np.float64).reshape(len(points)), fmt="%.17g")
     return path

@@ -22,6 +22,13 @@ column per row, as in :mod:`modal`.  The reference has no counterpart: it stores
 :class:`QuadraticStressRecovery` is the same for quadratic tetrahedra on an order-2 handle: stress at the four Gauss points
 of every element, the recovered nodal stress and the error estimate (``saa_operator_stress_p2``,
 ``saa_operator_nodal_stress_p2``, ``saa_operator_stress_error_p2``).
+
+Finite strain.  ``element``, ``estimate`` and ``history`` of both classes take ``material="svk"`` or ``"neo_hookean"`` and
+``measure="cauchy"`` or ``"pk2"``: the element pass is then ``saa_operator_stress_finite`` (``include/saa_hip.h`` has the
+definitions: the second Piola-Kirchhoff stress ``S`` or the Cauchy stress ``sigma`` of the material, its von Mises value,
+``det F`` and the stored energy), the layouts are unchanged, and ``nodal`` and ``error`` run the same kernels on the new
+fields with the volume weights of the reference configuration.  The default ``material="linear"`` launches exactly what it
+always launched.
 """
 from __future__ import annotations
 
@@ -84,7 +91,29 @@ class _Recovery:
         """``(first column, columns)`` of the launches that cover ``m`` columns."""
         return [(j, min(self.MAX_COLUMNS, m - j)) for j in range(0, m, self.MAX_COLUMNS)]
 
-    def _element(self, X, sigma, von_mises, energy) -> dict:
+    def stress_finite_raw(self, material, measure, m, x, ldx, stress=None, ld_stress=0, von_mises=None, ld_vm=0, det_f=None,
+                          ld_det=0, energy=None, ld_elem=0, energy_total=None, von_mises_max=None, von_mises_argmax=None,
+                          n_inverted=False):
+        """``saa_operator_stress_finite`` with SAA_MATERIAL_* ``material`` and SAA_STRESS_* ``measure`` as integers (any
+        value, m and leading dimension: the library checks them).  ``n_inverted=True`` asks for the inverted elements of
+        every column, which synchronises the stream, and returns them as a list of ``m`` ints; otherwise None."""
+        count = (C.c_int64 * max(int(m), 1))() if n_inverted else None
+        _lib.check(self._lib.saa_operator_stress_finite(self.op._h, int(material), int(measure), int(m), _ptr(x), int(ldx),
+                                                        _ptr(stress), int(ld_stress), _ptr(von_mises), int(ld_vm),
+                                                        _ptr(det_f), int(ld_det), _ptr(energy), int(ld_elem),
+                                                        _ptr(energy_total), _ptr(von_mises_max), _ptr(von_mises_argmax),
+                                                        count))
+        return [int(c) for c in count[:int(m)]] if n_inverted else None
+
+    @staticmethod
+    def _finite(material, measure):
+        """``None`` for the linear material, otherwise ``(SAA_MATERIAL_*, SAA_STRESS_*, measure name)``."""
+        mat = _lib.material_id(material)
+        if str(measure) not in _lib.MEASURES:
+            raise ValueError(f"unknown measure {measure!r}: one of {', '.join(_lib.MEASURES)}")
+        return None if mat == 0 else (mat, _lib.MEASURES[str(measure)], str(measure))
+
+    def _element(self, X, sigma, von_mises, energy, finite=None) -> dict:
         import torch
 
         self._check(X, "X")
@@ -104,11 +133,23 @@ class _Recovery:
         out["energy_total"] = torch.empty(m, dtype=torch.float64, device=dev)
         out["von_mises_max"] = torch.empty(m, dtype=torch.float64, device=dev)
         out["von_mises_argmax"] = torch.empty(m, dtype=torch.int32, device=dev)
+        if finite:
+            out["det_f"] = torch.empty((m, ne, *self._ROW), dtype=torch.float64, device=dev)
+        inverted = []
         for j, c in self._chunks(m):
             g = {k: v[j] for k, v in out.items()}
-            self._stress_columns(c, X[j], g.get("sigma"), 6 * per * ne, g.get("von_mises"), per * ne, g.get("energy"), ne,
-                                 g["energy_total"], g["von_mises_max"], g["von_mises_argmax"])
-        return {k: v[0] for k, v in out.items()} if vec else out
+            if finite:
+                inverted += self.stress_finite_raw(finite[0], finite[1], c, X[j], self.n_dof, g.get("sigma"), 6 * per * ne,
+                                                   g.get("von_mises"), per * ne, g["det_f"], per * ne, g.get("energy"), ne,
+                                                   g["energy_total"], g["von_mises_max"], g["von_mises_argmax"], n_inverted=True)
+            else:
+                self._stress_columns(c, X[j], g.get("sigma"), 6 * per * ne, g.get("von_mises"), per * ne, g.get("energy"), ne,
+                                     g["energy_total"], g["von_mises_max"], g["von_mises_argmax"])
+        out = {k: v[0] for k, v in out.items()} if vec else out
+        if finite:
+            out["n_inverted"] = inverted[0] if vec else torch.tensor(inverted, dtype=torch.int64)
+            out["measure"] = finite[2]
+        return out
 
     def _error(self, S, O, nodal, vec) -> dict:
         """The error of checked, contiguous ``S (m, n_elems, *row, 6)`` against ``O``: ``(m, n_nodes, 6)`` if ``nodal``,
@@ -127,24 +168,40 @@ class _Recovery:
                            out["eta2_max"][j:], out["eta2_argmax"][j:])
         return {k: v[0] for k, v in out.items()} if vec else out
 
-    def estimate(self, X) -> dict:
+    def estimate(self, X, material="linear") -> dict:
         """Zienkiewicz-Zhu estimate of the stress error of displacement columns ``(m, n_dof)`` (or one ``(n_dof,)``
         vector): :meth:`element` stress -> :meth:`nodal` stress -> :meth:`error`.  Returns the dict of :meth:`error` plus
-        ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish)."""
+        ``energy_total`` and ``relative = sqrt(eta2_total / (2 energy_total + eta2_total))`` (0 where both vanish).
+
+        With a finite-strain ``material`` the stress is always the second Piola-Kirchhoff stress, over the reference
+        configuration: ``eta_e^2 = integral_0 (S* - S_h)^T D^-1 (S* - S_h) dV``.  For ``svk``, ``S = D E`` and this is
+        exactly the energy norm of the Green-strain error.  For ``neo_hookean`` ``D`` is only the linearisation of the
+        material at the reference configuration, so ``eta`` is a scale in that norm, not an energy of the material.
+        ``relative`` keeps its formula with the stored energy in the place of the strain energy; the result gains
+        ``n_inverted`` (inverted elements hold ``S_h = 0``)."""
         import torch
 
-        el = self.element(X, von_mises=False, energy=False)
+        if self._finite(material, "pk2"):
+            el = self.element(X, von_mises=False, energy=False, material=material, measure="pk2")
+        else:
+            el = self.element(X, von_mises=False, energy=False)
         out = self.error(el["sigma"], nodal=self.nodal(el["sigma"]))
+        if "n_inverted" in el:
+            out["n_inverted"] = el["n_inverted"]
         out["energy_total"] = el["energy_total"]
         den = 2.0 * el["energy_total"] + out["eta2_total"]
         out["relative"] = torch.where(den > 0, out["eta2_total"] / den, torch.zeros_like(den)).sqrt()
         return out
 
-    def history(self, traj) -> dict:
+    def history(self, traj, material="linear", measure="cauchy") -> dict:
         """``energy_total``, ``von_mises_max`` and ``von_mises_argmax`` of every column of a row-major
         ``(n_dof, n_cols)`` trajectory (the recorder's and the HDF5 layout), host array or device tensor.  Only the
-        reductions are computed; no per-element field is written."""
+        reductions are computed; no per-element field is written.  With a finite-strain ``material`` they are those of
+        ``measure`` and of the stored energy, and the result gains ``n_inverted`` and ``min_det_f`` per column (``det F`` of
+        one launch's columns is written for that, and reduced)."""
         import torch
+
+        finite = self._finite(material, measure)
 
         if traj.shape[0] != self.n_dof:
             raise ValueError(f"expected {self.n_dof} rows, got {traj.shape[0]}")
@@ -153,13 +210,27 @@ class _Recovery:
         out = {"energy_total": torch.empty(n, dtype=torch.float64, device=dev),
                "von_mises_max": torch.empty(n, dtype=torch.float64, device=dev),
                "von_mises_argmax": torch.empty(n, dtype=torch.int32, device=dev)}
+        if finite:
+            points = (4 if self._ROW else 1) * self.n_elems
+            det = torch.empty((min(n, self.MAX_COLUMNS), points), dtype=torch.float64, device=dev)
+            out["min_det_f"] = torch.empty(n, dtype=torch.float64, device=dev)
+            inverted = []
         for j, c in self._chunks(n):
             if isinstance(traj, torch.Tensor):
                 blk = traj[:, j:j + c].to(device=dev, dtype=torch.float64).T.contiguous()
             else:
                 blk = torch.from_numpy(np.ascontiguousarray(np.asarray(traj[:, j:j + c], dtype=np.float64).T)).to(dev)
+            if finite:
+                inverted += self.stress_finite_raw(finite[0], finite[1], c, blk, self.n_dof, det_f=det, ld_det=points,
+                                                   energy_total=out["energy_total"][j:], von_mises_max=out["von_mises_max"][j:],
+                                                   von_mises_argmax=out["von_mises_argmax"][j:], n_inverted=True)
+                if points:
+                    out["min_det_f"][j:j + c] = det[:c].amin(dim=1)
+                continue
             self.stress_raw(c, blk, self.n_dof, energy_total=out["energy_total"][j:], von_mises_max=out["von_mises_max"][j:],
                             von_mises_argmax=out["von_mises_argmax"][j:])
+        if finite:
+            out["n_inverted"] = torch.tensor(inverted, dtype=torch.int64)
         return out
 
 
@@ -196,11 +267,16 @@ class StressRecovery(_Recovery):
         self.stress_raw(c, x, self.n_dof, sigma, ld_sigma, von_mises, energy, ld_elem, *reductions)  # (ld_vm == ld_elem)
 
     # ---- tensors -------------------------------------------------------------------------------------------------
-    def element(self, X, sigma=True, von_mises=True, energy=True) -> dict:
+    def element(self, X, sigma=True, von_mises=True, energy=True, material="linear", measure="cauchy") -> dict:
         """Element fields of a ``(n_dof,)`` vector or an ``(m, n_dof)`` block, in launches of at most 16 columns:
         ``sigma (m, n_elems, 6)``, ``von_mises``, ``energy (m, n_elems)`` (those asked for) and ``energy_total``,
-        ``von_mises_max``, ``von_mises_argmax (m,)``.  A vector input drops the leading ``m``."""
-        return self._element(X, sigma, von_mises, energy)
+        ``von_mises_max``, ``von_mises_argmax (m,)``.  A vector input drops the leading ``m``.
+
+        ``material="svk"`` or ``"neo_hookean"``: ``sigma`` is the stress of ``measure`` (``"cauchy"`` or ``"pk2"``) at finite
+        strain, ``von_mises`` its von Mises value and ``energy`` the stored energy, and the result gains ``det_f (m,
+        n_elems)``, ``n_inverted`` (a CPU int64 tensor ``(m,)``, an int for a vector; reading it synchronises) and
+        ``measure``.  An inverted element holds 0 in ``sigma``, ``von_mises`` and ``energy``."""
+        return self._element(X, sigma, von_mises, energy, self._finite(material, measure))
 
     def nodal(self, E):
         """Volume-weighted nodal average of element fields ``(m, n_elems, k)`` (or ``(n_elems, k)``) ->
@@ -302,12 +378,17 @@ class QuadraticStressRecovery(_Recovery):
             raise ValueError(f"expected {name} of shape (m, {self.n_elems}, 4, 6), got {tuple(S.shape)}")
         return S, vec
 
-    def element(self, X, sigma=True, von_mises=True, energy=True) -> dict:
+    def element(self, X, sigma=True, von_mises=True, energy=True, material="linear", measure="cauchy") -> dict:
         """Gauss-point fields of a ``(n_dof,)`` vector or an ``(m, n_dof)`` block, in launches of at most 16 columns:
         ``sigma (m, n_elems, 4, 6)``, ``von_mises (m, n_elems, 4)``, ``energy (m, n_elems)`` (those asked for) and
         ``energy_total``, ``von_mises_max``, ``von_mises_argmax (m,)`` (a point index ``4 e + q``).  A vector input drops
-        the leading ``m``."""
-        return self._element(X, sigma, von_mises, energy)
+        the leading ``m``.
+
+        ``material="svk"`` or ``"neo_hookean"``: ``sigma`` is the stress of ``measure`` (``"cauchy"`` or ``"pk2"``) at finite
+        strain, ``von_mises`` its von Mises value and ``energy`` the stored energy, and the result gains ``det_f (m,
+        n_elems, 4)``, ``n_inverted`` (a CPU int64 tensor ``(m,)``, an int for a vector; reading it synchronises) and
+        ``measure``.  An inverted element holds 0 in ``sigma``, ``von_mises`` and ``energy``."""
+        return self._element(X, sigma, von_mises, energy, self._finite(material, measure))
 
     def nodal(self, sigma):
         """Recovered nodal stress of Gauss-point stresses ``(m, n_elems, 4, 6)`` (or ``(n_elems, 4, 6)``) ->
