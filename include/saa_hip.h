@@ -671,7 +671,10 @@ int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int6
  *                             W = mu/2 (F:F - 3) - mu ln J + lambda/2 (ln J)^2, evaluated as saa_operator_internal_force does
  * measure = SAA_STRESS_PK2 writes S (second Piola-Kirchhoff, reference configuration), SAA_STRESS_CAUCHY sigma; F S = P of
  * saa_operator_internal_force and P F^T / J = sigma.  Both vanish under a rigid motion to the rounding of x.  von_mises is
- * sqrt(((s_xx - s_yy)^2 + (s_yy - s_zz)^2 + (s_zz - s_xx)^2)/2 + 3 (s_yz^2 + s_xz^2 + s_xy^2)) of the chosen measure, and
+ * sqrt(((s_xx - s_yy)^2 + (s_yy - s_zz)^2 + (s_zz - s_xx)^2)/2 + 3 (s_yz^2 + s_xz^2 + s_xy^2)) of the chosen measure.  The
+ * three differences are formed before the pressure that the normal stresses share is added, for every material and measure
+ * (for the Cauchy stress of SVK from (2 mu F E F^T + lambda tr(E) (H + H^T + H H^T)) / J), so that von_mises keeps its
+ * digits where lambda is many times mu and the stress nearly hydrostatic.
  * energy[e] = sum_q w_q |detJ_q| W(F_q), the stored energy of the element (that of saa_operator_internal_force).
  *
  * Layouts are those of the linear entries, so that saa_operator_nodal_average / saa_operator_stress_error (order 1) and

@@ -11,8 +11,11 @@
 //      neo-Hooke:             S = -mu M + lam ln J (I + M) with M = G + G^T + G^T G (= C^-1 - I),
 //                             sigma = (mu (H + H^T + H H^T) + lam ln J I) / J
 //    and W as opfs_stress has it.  Under a rigid rotation E, M and H + H^T + H H^T vanish to the rounding of H, so both
-//    measures do.  The von Mises value is that of the chosen measure; where the normal stresses are a multiple of a strain
-//    plus a common pressure, their differences are taken from the strain.
+//    measures do.  The von Mises value is that of the chosen measure, and in all four instantiations the differences of
+//    the normal stresses are taken before the common pressure is added: 2 mu (E_ii - E_jj), (lam ln J - mu)(M_ii - M_jj) and
+//    mu (B_ii - B_jj) / J with B = H + H^T + H H^T where the normal stresses are a multiple of a strain plus a pressure, and
+//    for the Cauchy stress of St. Venant-Kirchhoff those of (2 mu F E F^T + lam tr(E) B) / J, to which lam tr(E) / J is added
+//    on the diagonal afterwards (F F^T = I + B).  Differences of the finished stresses lose lam / mu times the rounding.
 //  * Layouts are those of the linear passes (saa_stress.hip, saa_stress_p2.hip), so that their nodal and error kernels read
 //    the fields unchanged: stress [column][6 (nq e + q) + c], von_mises and det_f [column][nq e + q], energy [column][e];
 //    the (sum W_e, max von Mises, lowest point index) partials per workgroup and stress_final_kernel are theirs too.
@@ -89,24 +92,32 @@ __device__ __forceinline__ bool fs_point(const double h[3][3], double lam, doubl
       for (int c = 0; c < 6; ++c) s[c] = mu2 * E[vi(c)][vk(c)] + (c < 3 ? ltr : 0.0);
       d01 = mu2 * (E[0][0] - E[1][1]), d12 = mu2 * (E[1][1] - E[2][2]), d20 = mu2 * (E[2][2] - E[0][0]);
     } else {
-      double F[3][3], FS[3][3];
+      // F S F^T = 2 mu F E F^T + lam tr(E) (I + B) with B = F F^T - I = h + h^T + h h^T: the common pressure lam tr(E) / J goes
+      // on the diagonal last, after the differences are taken (it is lam / mu times the rest at small strain)
+      // (one row of F E at a time, E scaled by 2 mu / J first: three values live where the whole product was nine)
+      const double p = ltr * rJ, f = mu2 * rJ;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          F[i][k] = h[i][k] + (i == k ? 1.0 : 0.0);
-          E[i][k] = mu2 * E[i][k] + (i == k ? ltr : 0.0);  // S
+        for (int k = i; k < 3; ++k) {
+          E[i][k] *= f;
+          E[k][i] = E[i][k];
         }
+      double t[6];
 #pragma unroll
-      for (int i = 0; i < 3; ++i)
+      for (int i = 0; i < 3; ++i) {
+        double r[3];  // row i of (I + h) E
 #pragma unroll
-        for (int k = 0; k < 3; ++k) FS[i][k] = F[i][0] * E[0][k] + F[i][1] * E[1][k] + F[i][2] * E[2][k];
+        for (int k = 0; k < 3; ++k) r[k] = E[i][k] + (h[i][0] * E[0][k] + h[i][1] * E[1][k] + h[i][2] * E[2][k]);
 #pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        const int i = vi(c), k = vk(c);
-        s[c] = (FS[i][0] * F[k][0] + FS[i][1] * F[k][1] + FS[i][2] * F[k][2]) * rJ;
+        for (int k = i; k < 3; ++k) {
+          const double B = (h[i][k] + h[k][i]) + (h[i][0] * h[k][0] + h[i][1] * h[k][1] + h[i][2] * h[k][2]);
+          t[i == k ? i : 6 - i - k] = (r[k] + (r[0] * h[k][0] + r[1] * h[k][1] + r[2] * h[k][2])) + p * B;
+        }
       }
-      d01 = s[0] - s[1], d12 = s[1] - s[2], d20 = s[2] - s[0];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s[c] = t[c] + (c < 3 ? p : 0.0);
+      d01 = t[0] - t[1], d12 = t[1] - t[2], d20 = t[2] - t[0];
     }
   } else {
     const double lnJ = log1p(x);

@@ -420,7 +420,12 @@ def test_drivers_end_to_end(tmp_path, order, capsys):
     assert rep["material"] == "svk" and rep["measure"] == "cauchy" and rep["order"] == order
     assert e_w <= TOL and e_v <= TOL and col["n_inverted"] == 0
     assert abs(col["min_det_f"] - float(want["det_f"].min())) <= TOL
-    assert col["element"] == want["von_mises_argmax"] // ld.nq
+    # (the reported element holds the double's maximum to the bar: 50 steps into the run the largest values of the structured
+    # beam lie in elements that the load treats alike, and the last bit decides between them)
+    vm = np.asarray(want["von_mises"], dtype=np.float64)
+    print(f"order {order}: element {col['element']} holds {vm[col['element']].max():.17e}, the double's element",
+          f"{want['von_mises_argmax'] // ld.nq} holds {vm.max():.17e}")
+    assert vm[col["element"]].max() >= vm.max() * (1.0 - TOL)
     pk2 = ld.recover(traj[:, -1], "svk", "pk2")
     ecol = est["columns"][0]
     assert est["measure"] == "pk2" and abs(ecol["energy_norm"] ** 2 / 2 - float(pk2["energy_total"])) <= TOL * float(pk2["energy_total"])

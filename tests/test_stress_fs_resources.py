@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRESS_FS_ROWS = {
     "void saa::stress_fs_p2_kernel<1, 0>": (87, 204, 0, 0, 0, 2),
     "void saa::stress_fs_p1_kernel<1, 0>": (56, 98, 0, 0, 0, 4),
-    "void saa::stress_fs_p2_kernel<1, 1>": (91, 216, 0, 0, 0, 2),
-    "void saa::stress_fs_p1_kernel<1, 1>": (60, 114, 0, 0, 0, 4),
+    "void saa::stress_fs_p2_kernel<1, 1>": (93, 242, 0, 0, 0, 2),
+    "void saa::stress_fs_p1_kernel<1, 1>": (62, 138, 0, 0, 0, 3),
     "void saa::stress_fs_p2_kernel<2, 0>": (106, 252, 0, 0, 0, 2),
     "void saa::stress_fs_p1_kernel<2, 0>": (76, 153, 0, 0, 0, 3),
     "void saa::stress_fs_p2_kernel<2, 1>": (106, 252, 0, 0, 0, 2),
