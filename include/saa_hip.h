@@ -626,7 +626,9 @@ int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev
  *   LINEAR operator at the reference configuration.  Under large stretch the tangent stiffens and the stability limit
  *   moves below that; watch the displacements (and, under neo-Hooke, the inversion counters).  The limit at a state can
  *   be MEASURED: 2/omega_max of M_L^-1 K_T(d) by Lanczos on saa_operator_tangent_apply (modal.stable_time_step_operator,
- *   OperatorStepper.stable_time_step, drivers dynamics --dt-check-every); the step itself is never changed.
+ *   OperatorStepper.stable_time_step, drivers dynamics --dt-check-every); the stepper never changes the step by itself.
+ *   A caller can FOLLOW the limit with saa_operator_tangent_bound and saa_operator_stepper_set_dt (below;
+ *   OperatorStepper.follow_time_step, drivers dynamics --dt-follow).
  * saa_operator_tangent_apply: kv_dev = K_T(u_dev) v_dev, the tangent of saa_operator_internal_force at u applied to one
  *   column v, K_T(u) v = d/ds f_int(u + s v) at s = 0 (csrc/saa_optan.hip): one column of 3*n_nodes doubles, 0 on Dirichlet
  *   dofs.  u and v are both masked to 0 on Dirichlet dofs on input, exactly as saa_operator_internal_force masks x.  At each
@@ -656,6 +658,59 @@ int saa_operator_tangent_apply(saa_operator *op, int32_t material, const double 
                                double *kv_dev, int64_t *n_inverted /* host, or NULL */);
 int saa_operator_stepper_set_material(saa_operator_stepper *st, int32_t material);
 int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int64_t *first_step /* -1: none */);
+
+/*
+ * Following the stable time step at finite strain (csrc/saa_opdt.hip).  Under stretch the tangent stiffens and the limit
+ * 2/omega_max of M_L^-1 K_T(d) moves below the step a stepper was created with; these two entries let a caller recompute the
+ * step as it runs - a one-pass element bound of omega_max at a state, and an exact change of dt between two steps.  Nothing
+ * else of the stepper changes: a caller that uses neither launches exactly the kernels it launched before.
+ *
+ * saa_operator_tangent_bound: omega_e, an upper bound per element of the highest frequency at the state u, on a handle of
+ *   either order and for all three materials; SAA_MATERIAL_LINEAR is the St. Venant-Kirchhoff law at H = 0 and u_dev is then
+ *   not read (it may be NULL).  One element per lane; at each point q of the K rule (order 1: one; order 2: the four Gauss
+ *   points) H = grad_X u is formed exactly as the force pass of that order forms it, u masked to 0 on Dirichlet dofs (order 2
+ *   reads the handle's geometry table, made on first need).  With g_a = grad_X N_a(q) and m_a the element's share of the
+ *   handle's lumped mass (order 1: rho |V_e| / 4; order 2: the HRZ share of saa_operator_lumped_mass):
+ *     C_q = sum_a g_a g_a^T / m_a = R R^T (3x3, Cholesky),   A_q = dP/dF at H, the 9x9 symmetric material tangent (never stored),
+ *     T_q = (I_3 (x) R)^T A_q (I_3 (x) R), built from nine evaluations of the point law of saa_operator_tangent_apply,
+ *     mu_q = w_q |detJ_q| max(lambda_max(T_q), 0) by cyclic Jacobi in registers,   omega_e = sqrt(sum_q mu_q).
+ *   max_e omega_e >= omega_max(M_L^-1 K_T(u)): the Irons-Treharne argument per quadrature point (the nonzero spectrum of
+ *   M_e^-1 G_q^T A_q G_q is that of T_q; lambda_max of a sum is at most the sum of the lambda_max; the Dirichlet mask only
+ *   removes rows and columns).  At order 1 and u = 0 it is the quantity of saa_operator_element_bound, reached another way.
+ *   It is a BOUND, typically 1.4 to 2.3 times omega_max on well-shaped meshes and more on slivers: 2/max_e omega_e is a
+ *   certified step, not a sharp one.
+ *   omega_e_dev: n_elems device doubles, or NULL.  *omega_max, *argmax: the maximum and its element, ties to the lowest
+ *   index, by a two-stage reduction in a fixed order (no floating-point atomics: bitwise repeatable); 0 and -1 when no
+ *   element enters the maximum.  counts (3 host words, or NULL): [0] elements with detJ <= 0 at a point - the bound is
+ *   certified only when this is 0; [1] elements with !(J > 0) at a point under neo-Hooke, NaN included: their omega_e is 0 and
+ *   they leave the maximum, as the force pass drops them; [2] elements whose omega_e is not finite: the stored value stays as
+ *   computed, they are left out of the maximum and counted, never dropped silently.
+ *   An order-2 call uses the element contributions scratch for the mass shares.  Synchronises the stream, like
+ *   saa_operator_element_bound.  SAA_E_ARG, before the handle or the device is looked at: a material outside {0, 1, 2}; then a
+ *   null handle, null omega_max or argmax, null u_dev with a nonlinear material.
+ * saa_operator_stepper_set_dt: an exact change of the step.  With v- = (d0 - dn)/dt_old, h = (dt_old + dt_new)/2 and
+ *   a = (scale f - s)/m, s = f_int(d0) of the stepper's current material and scale the ramp factor at the current tn (the one
+ *   the next step will use), the variable-step central-difference scheme is
+ *     m (v+ - v-)/h + alpha m (v+ + v-)/2 + s = scale f,   d1 = d0 + dt_new v+ ,
+ *   and the unchanged constant-step update of saa_operator_stepper_step with dt_new gives that same d1 when dn is replaced by
+ *   dn' = d0 - dt_new v',
+ *     v+ = ((1/h - alpha/2) v- + a) / (1/h + alpha/2),   v' = ((1/dt_new + alpha/2) v+ - a) / (1/dt_new - alpha/2).
+ *   The call runs the stepper's own element pass at d0 into the contributions scratch (the pass set_material selected, the
+ *   linear one included), one node pass that sums a node's contributions in ascending element order and overwrites dn with
+ *   dn' (0 on Dirichlet dofs and at nodes without elements), and stores dt_new.  tn, the step index, the recorder and the
+ *   stepper's inversion counters are left alone: the element pass of this call counts into the handle's scratch counter.
+ *   dt_new == dt launches nothing and leaves the state bit-equal.  Enqueued: no host synchronisation.
+ *   SAA_E_ARG: a null handle; dt_new not finite or <= 0; alpha > 0 and dt_new >= 2/alpha.  SAA_E_STATE: between step_begin and
+ *   step_finish; with a shared set (a rank holds only its share of s); while the energy balance is on (its identity assumes
+ *   one dt); with the "passes" option not at 3.
+ *   WHICH dt to set is the caller's policy.  2/max_e omega_e of saa_operator_tangent_bound is certified and pessimistic;
+ *   scaling the Lanczos step of the linear operator by min(1, bound(0)/bound(d)) (OperatorStepper.follow_time_step,
+ *   "anchored") follows the stiffening without the pessimism but is a HEURISTIC, not a certificate.
+ */
+int saa_operator_tangent_bound(saa_operator *op, int32_t material, const double *u_dev /* NULL allowed with LINEAR */,
+                               double *omega_e_dev /* n_elems, or NULL */, double *omega_max, int32_t *argmax,
+                               int64_t *counts /* host, 3 words, or NULL */);
+int saa_operator_stepper_set_dt(saa_operator_stepper *st, double dt_new);
 
 /*
  * Finite-strain stress recovery (csrc/saa_stress_fs.hip): what saa_operator_stress / saa_operator_stress_p2 are to the linear

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SAA_LIB_PATH") or os.path.join(_HERE, "libsaa_hip.so"
 DIAG_LIB_PATH = os.path.join(_HERE, "libsaa_hip_diag.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "saa_hip.h")
 SOURCES = ["saa_plan.cpp", "saa_partition.cpp", "saa_kernels.hip", "saa_setup.hip", "saa_predictor.hip", "saa_topology.hip", "saa_modal.hip",
-           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_stress_fs.hip",
+           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_opdt.hip", "saa_stress_fs.hip",
            "saa_api.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-ldl"]
 
@@ -185,6 +185,8 @@ SIGNATURES = {
                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "saa_operator_stepper_set_material": (C.c_int, [_H, C.c_int32]),
     "saa_operator_stepper_inverted": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "saa_operator_tangent_bound": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, _dp, _ip, C.POINTER(C.c_int64)]),
+    "saa_operator_stepper_set_dt": (C.c_int, [_H, C.c_double]),
 }
 
 _lib = None

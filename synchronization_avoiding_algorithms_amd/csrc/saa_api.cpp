@@ -2461,6 +2461,39 @@ int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int6
   return SAA_OK;
 }
 
+int saa_operator_tangent_bound(saa_operator *op, int32_t material, const double *u_dev, double *omega_e_dev, double *omega_max,
+                               int32_t *argmax, int64_t *counts) {
+  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, "saa_operator_tangent_bound: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_tangent_bound: null handle");
+  if (!omega_max || !argmax) return fail(SAA_E_ARG, "saa_operator_tangent_bound: null omega_max or argmax");
+  if (!u_dev && material != SAA_MATERIAL_LINEAR)
+    return fail(SAA_E_ARG, "saa_operator_tangent_bound: null u_dev with a nonlinear material");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_tangent_bound(op->impl, material, u_dev, omega_e_dev, omega_max, argmax, counts);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_tangent_bound: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_stepper_set_dt(saa_operator_stepper *st, double dt_new) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_dt: null handle");
+  if (!(std::isfinite(dt_new) && dt_new > 0.0)) return fail(SAA_E_ARG, "saa_operator_stepper_set_dt: dt_new must be finite and > 0");
+  const double alpha = saa::opstep_alpha(st->impl);
+  if (alpha > 0.0 && dt_new >= 2.0 / alpha)
+    return fail(SAA_E_ARG, "saa_operator_stepper_set_dt: dt_new must be below 2/alpha (the update that continues the scheme divides by 1/dt_new - alpha/2)");
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: a synchronised step is in flight");
+  if (saa::opstep_has_shared_set(st->impl))
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: a shared set is in place (a rank holds only its share of the internal force)");
+  if (saa::opstep_energy_on(st->impl))
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: the energy balance is recorded (its identity assumes one dt)");
+  if (saa::opstep_passes(st->impl) != 3)
+    return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: the passes option is 1 or 2 (a measurement aid that does not advance the state)");
+  HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
+  const hipError_t e = saa::opstep_set_dt(st->impl, dt_new);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_dt: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
 int saa_operator_stepper_destroy(saa_operator_stepper *st) {
   if (!st) return SAA_OK;
   saa::opfs_release(st->impl);

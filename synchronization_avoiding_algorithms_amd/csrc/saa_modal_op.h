@@ -42,6 +42,7 @@ struct ModalOp {
   uint32_t *bits = nullptr;  // n_elems
   unsigned long long *fs_count = nullptr;  // saa_operator_internal_force: the two counter words of the call (saa_opfs.hip)
   unsigned long long *st_inverted = nullptr;  // saa_operator_stress_finite: inverted elements per column (saa_stress_fs.hip)
+  int32_t *dt_cnt = nullptr;  // saa_operator_tangent_bound: [workgroup][3] partial counts, then the three totals (saa_opdt.hip)
 };
 
 // The node pass of saa_modal.hip on any [column][pair][3] contributions of this handle's CSR: y[j][3v + c] = sum of node

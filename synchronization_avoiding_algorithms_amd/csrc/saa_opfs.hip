@@ -299,6 +299,14 @@ hipError_t opfs_element_pass(OpStepper *st, const double *x, double *contrib) {
   return launch<kNeo, false>(op, x, contrib, nullptr, st->inverted, st->step_index);
 }
 
+hipError_t opfs_element_pass_scratch(OpStepper *st, const double *x, double *contrib) {
+  ModalOp *op = st->op;
+  SAA_HIP_TRY(alloc_counters(&op->fs_count, op->stream));
+  SAA_HIP_TRY(reset_counters(op->fs_count, op->stream));
+  if (st->material == kSvk) return launch<kSvk, false>(op, x, contrib, nullptr, op->fs_count, 0);
+  return launch<kNeo, false>(op, x, contrib, nullptr, op->fs_count, 0);
+}
+
 hipError_t operator_internal_force(ModalOp *op, int material, const double *x, double *f, double *energy_elem, int64_t *n_inverted) {
   double *contrib = nullptr;
   SAA_HIP_TRY(operator_scratch(op, 1, &contrib));

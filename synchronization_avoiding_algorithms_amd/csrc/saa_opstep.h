@@ -99,4 +99,18 @@ hipError_t opstep_inverted(OpStepper *st, int64_t *count, int64_t *first_step);
 hipError_t opstep_clear_inverted(OpStepper *st);  // enqueued
 void opfs_release(OpStepper *st);                 // frees the counters; before opstep_destroy
 
+
+// Following the time step at finite strain (saa_opdt.hip, which states the bound and the change of step).
+// omega_e (n_elems device doubles or NULL), *omega_max and *argmax (0 and -1 when no element enters the maximum), counts (3
+// host words or NULL: detJ <= 0 at a point; neo-Hooke !(J > 0) at a point; omega_e not finite) of the per-element bound of
+// omega_max(M_L^-1 K_T(u)); material validated by the caller, 0 ignores u.  An order-2 handle makes its geometry table on
+// first need and uses the contributions scratch for the HRZ shares.  Synchronises the stream.
+hipError_t operator_tangent_bound(ModalOp *op, int material, const double *u, double *omega_e, double *omega_max, int32_t *argmax,
+                                  int64_t *counts);
+// dn <- dn' such that the unchanged step kernels with dt_new continue the variable-step scheme; dt_new == dt: nothing.  The
+// stepper's element pass at d0 (inversions into the handle's scratch counter) and one node pass; enqueued.
+hipError_t opstep_set_dt(OpStepper *st, double dt_new);
+bool opstep_has_shared_set(const OpStepper *st);
+double opstep_alpha(const OpStepper *st);
+
 }  // namespace saa

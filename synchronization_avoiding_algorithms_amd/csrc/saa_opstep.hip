@@ -677,6 +677,24 @@ hipError_t opstep_step(OpStepper *st, int32_t nsteps) {
   return hipSuccess;
 }
 
+hipError_t opstep_element_pass_at_d0(OpStepper *st, double *contrib) {
+  if (st->material != 0) return opfs_element_pass_scratch(st, st->buf[st->cur], contrib);
+  return element_pass(st, st->buf[st->cur], contrib);
+}
+
+double opstep_ramp_scale(const OpStepper *st) { return ramp_scale(st); }
+
+hipError_t operator_element_masses(ModalOp *op, double *out) {
+  if (op->n_elems == 0) return hipSuccess;
+  if (op->order == 2)
+    hipLaunchKernelGGL(opstep_hrz_mass_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
+                       op->rho, out);
+  else
+    hipLaunchKernelGGL(opstep_p1_mass_kernel, opstep_grid(op->n_elems), dim3(kThreads), 0, op->stream, op->n_elems, op->xyz, op->tets,
+                       op->rho, out);
+  return hipGetLastError();
+}
+
 bool opstep_pending(const OpStepper *st) { return st->pending; }
 int32_t opstep_n_shared(const OpStepper *st) { return st->n_shared; }
 bool opstep_lacks_interface_buffer(const OpStepper *st) { return st->n_global_shared > 0 && !st->iface; }

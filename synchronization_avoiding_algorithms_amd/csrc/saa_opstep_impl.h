@@ -47,6 +47,15 @@ hipError_t operator_geometry(ModalOp *op);
 // saa_opfs.hip: the finite-strain element pass of the stepper's material (!= 0) for one column x into contrib; an inverted
 // element is counted at st->step_index.
 hipError_t opfs_element_pass(OpStepper *st, const double *x, double *contrib);
+// saa_opfs.hip: that pass for a caller that is not a step (saa_operator_stepper_set_dt): an inverted element is counted in the
+// handle's scratch counter (op->fs_count, cleared first), not in the stepper's.
+hipError_t opfs_element_pass_scratch(OpStepper *st, const double *x, double *contrib);
+// saa_opstep.hip: the element pass the stepper is set to (material, "stored_geometry") at its d0 into contrib, inversions
+// counted as above; the ramp factor of the next step; the element's shares of the lumped mass, out[npe e + corner] (the
+// element pass of operator_lumped_mass).
+hipError_t opstep_element_pass_at_d0(OpStepper *st, double *contrib);
+double opstep_ramp_scale(const OpStepper *st);
+hipError_t operator_element_masses(ModalOp *op, double *out);
 // saa_optan.hip: the tangent element pass of `material` (!= 0) at u for one column v into contrib; an inverted element writes
 // zeros and is counted in cnt (the two words of saa_opfs.hip) at step 0.  The handle's geometry table must exist.
 hipError_t optan_element_pass(ModalOp *op, int material, const double *u, const double *v, double *contrib,

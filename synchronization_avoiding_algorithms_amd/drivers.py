@@ -40,6 +40,7 @@ PATHS = dict(local_nodes="Results/Rankwised_Data/Rank={r}_local_nodes.csv",
              truth="Results/Dynamics/Local-rank-{r}.hdf5",
              dynamics="Results/Dynamics/Displacement_order{p}.hdf5",
              energy="Results/Dynamics/Energy_order{p}.hdf5",
+             time="Results/Dynamics/Time_order{p}.npz",
              modeled="Results/Dynamics/Modeled_Local-rank-{r}.hdf5",
              shared_traj="Results/sol_on_shared/rank={r}-shared_dof.hdf5",
              model="Distributed_save/Rank-{r}/nB-{nB}-nH-{nH}-Lr-{lr}-filter={ns}/model.pth",
@@ -335,7 +336,8 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
 
 
 def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1, E=None, nu=None, rho=None, fz=None,
-             alpha=None, gamma=None, parts=0, partition="slab", energy_every=0, material="linear", dt_check_every=0):
+             alpha=None, gamma=None, parts=0, partition="slab", energy_every=0, material="linear", dt_check_every=0,
+             dt_follow=None, dt_follow_every=10):
     """The explicit run of the whole mesh on one GPU through the operator handle (:func:`dynamics.run_dynamics`), for
     linear (``order=1``) or quadratic tetrahedra (``order=2``: the mesh is elevated like ``steady_state --order 2``),
     clamped on every node of ``x = 0``: lumped mass of the handle (HRZ for order 2), the reference load ``(0, -fz, -fz)``
@@ -348,10 +350,14 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     ``material``: ``linear``, ``svk`` (St. Venant-Kirchhoff) or ``neo_hookean`` - the finite-strain element pass
     (``include/saa_hip.h``); with a nonlinear one the report gains ``material``, ``inverted`` and ``first_inverted_step``.  ``dt`` stays that of
     the LINEAR operator at the reference configuration: under large stretch the tangent stiffens, the stability limit moves,
-    and the stepper does not follow it.  The energy balance is defined for ``linear`` only (ValueError otherwise).
+    and the stepper does not follow it unless ``dt_follow`` asks for it.  The energy balance is defined for ``linear`` only (ValueError otherwise).
     ``dt_check_every = S > 0`` (a nonlinear material, no ``parts``): the limit ``2/omega_max`` of the tangent at the current
     state is measured every ``S`` steps and the report gains ``dt_check`` (:func:`dynamics.run_dynamics`); ``dt`` itself is
-    not changed."""
+    not changed.  ``dt_follow = "certified"`` or ``"anchored"`` (a nonlinear material, no ``parts``, no energy balance): the step
+    is checked before step 0 and after every ``dt_follow_every`` steps and changed by the rule of
+    :meth:`dynamics.OperatorStepper.follow_time_step`; the report gains ``dt_follow`` and ``time_path``,
+    ``Results/Dynamics/Time_order{p}.npz`` with ``t`` per saved column - the columns are no longer equidistant in time - and the
+    ``(step, dt)`` list of the run.  The HDF5 container is what it was."""
     from .dynamics import run_dynamics
     from .mesh import plane_nodes
 
@@ -365,8 +371,13 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     epart = make_partition(mesh, int(parts), partition) if parts and int(parts) > 0 else None
     store, report, *table = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device,
                                          epart=epart, energy_every=int(energy_every or 0), material=material,
-                                         dt_check_every=int(dt_check_every or 0), **p)
+                                         dt_check_every=int(dt_check_every or 0),
+                                         **({"dt_follow": dt_follow, "dt_follow_every": dt_follow_every} if dt_follow else {}), **p)
     path = rio.save_displacement(os.path.join(out_dir, PATHS["dynamics"].format(p=order)), store)
+    if dt_follow:
+        times = table.pop()
+        report["time_path"] = os.path.join(out_dir, PATHS["time"].format(p=order))
+        np.savez(report["time_path"], **times)
     if table:
         report["energy_path"] = rio.save_displacement(os.path.join(out_dir, PATHS["energy"].format(p=order)), table[0],
                                                       dataset=rio.ENERGY_DATASET)
@@ -1017,7 +1028,7 @@ def main(argv=None):
                     help="dynamics: the element pass - small-strain linear elasticity, or finite strain with the St. "
                          "Venant-Kirchhoff or the compressible neo-Hookean material.  dt stays gamma * 2/omega_max of the linear "
                          "operator at the reference configuration: under large stretch the stability limit moves and the "
-                         "stepper does not follow it.  stress, estimate: the finite-strain stress of that material on the "
+                         "stepper does not follow it unless --dt-follow asks for it.  stress, estimate: the finite-strain stress of that material on the "
                          "whole-mesh run of dynamics (either order)")
     ap.add_argument("--measure", choices=["cauchy", "pk2"], default="cauchy",
                     help="stress --material svk / neo-hookean: the Cauchy or the second Piola-Kirchhoff stress (estimate "
@@ -1030,6 +1041,12 @@ def main(argv=None):
     ap.add_argument("--dt-check-every", type=int, default=0,
                     help="dynamics --material svk / neo-hookean: every so many steps measure 2/omega_max of the tangent at the "
                          "current state and report it against dt (dt_check); dt is not changed")
+    ap.add_argument("--dt-follow", choices=["certified", "anchored"], default=None,
+                    help="dynamics --material svk / neo-hookean: follow the stable step - before step 0 and after every "
+                         "--dt-follow-every steps bound omega_max of the tangent at the current state in one element pass and "
+                         "change dt exactly.  certified: gamma * 2/bound (safe, pessimistic); anchored: the linear operator's "
+                         "step scaled by bound(0)/bound(state) (a heuristic, never above today's dt)")
+    ap.add_argument("--dt-follow-every", type=int, default=10, help="dynamics --dt-follow: every so many steps")
     ap.add_argument("--n-past", type=int, default=20)
     ap.add_argument("--n-future", type=int, default=20)
     ap.add_argument("--filter-size", type=int, default=150)
@@ -1061,6 +1078,17 @@ def main(argv=None):
         if args.parts and args.parts > 0:
             ap.error("dynamics --dt-check-every --parts: a rank's operator is only its share of the tangent; run the check "
                      "on the whole mesh")
+    if args.command == "dynamics" and args.dt_follow:
+        if args.dt_follow_every < 1:
+            ap.error("dynamics --dt-follow-every must be >= 1")
+        if args.material == "linear":
+            ap.error("dynamics --dt-follow: following the step is for --material svk or neo-hookean (the linear operator's limit "
+                     "does not move)")
+        if args.parts and args.parts > 0:
+            ap.error("dynamics --dt-follow --parts: a rank holds only its share of the internal force; follow the step on the "
+                     "whole mesh")
+        if args.energy:
+            ap.error("dynamics --dt-follow --energy: the identity of the energy balance assumes one dt")
     if args.command == "steady_state" and args.load_steps < 1:
         ap.error("steady_state --load-steps must be >= 1")
     if args.command in ("stress", "estimate") and args.material != "linear" and args.modeled:
@@ -1084,7 +1112,8 @@ def main(argv=None):
             path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order,
                                     parts=args.parts, partition=args.partition,
                                     energy_every=max(args.energy_every, 1) if args.energy else 0, fz=args.fz,
-                                    material=args.material, dt_check_every=args.dt_check_every)
+                                    material=args.material, dt_check_every=args.dt_check_every, dt_follow=args.dt_follow,
+                                    dt_follow_every=args.dt_follow_every)
             print(json.dumps({**report, "path": path}))
         elif args.command == "estimate":
             cols = [int(c) for c in args.columns.split(",") if c.strip()]

@@ -48,6 +48,8 @@ class OperatorStepper:
         _lib.check(self._lib.saa_operator_stepper_create(op._h, _dev(m), _dev(f), float(dt), float(alpha), 1 if ramp else 0,
                                                          C.byref(self._h)))
         self._mass = m                    # (for stable_time_step; the library has its own copy)
+        self.steps_done = 0               # (the step count of follow_time_step's records)
+        self._anchor = None               # follow_time_step "anchored": (omega_L, Omega(0)), made once
         self.material = "linear"
         if _lib.material_id(material) != 0:
             self.set_material(material)
@@ -66,10 +68,62 @@ class OperatorStepper:
         out["dt_over_dt_crit"] = self.dt / out["dt_crit"]
         return out
 
+    def set_dt(self, dt):
+        """An exact change of the step between two steps (``saa_operator_stepper_set_dt``): ``dn`` is replaced so that the
+        unchanged step kernels with the new ``dt`` continue the variable-step central-difference scheme; the time, the
+        recorder and the inversion counters are left alone.  ``dt`` equal to the current one does nothing.  Enqueued.  Not
+        with a shared set, the energy balance or between ``step_begin`` and ``step_finish``."""
+        _lib.check(self._lib.saa_operator_stepper_set_dt(self._h, float(dt)))
+        self.dt = float(dt)
+
+    def follow_time_step(self, mode, gamma=0.9, grow=1.05, omega_linear=None):
+        """One check of the time step at the current state ``d0``: the element bound ``Omega(d0) = max_e omega_e`` of
+        :meth:`modal.ModalOperator.tangent_bound` for the stepper's material, a target step from it, and :meth:`set_dt` when
+        the target asks for it.  Returns the record ``(step, Omega, target, dt)`` with the steps done and the ``dt`` now in use.
+
+        * ``certified``: ``target = gamma * 2/Omega(d0)``.  ``Omega`` bounds ``omega_max`` of ``M_L^-1 K_T(d0)`` from above (when no
+          element has ``detJ <= 0``), so the linearised update at this state is stable - at the price of the bound's pessimism,
+          typically a factor 1.4 to 2.3 on well-shaped meshes, more on slivers.
+        * ``anchored``: ``target = gamma * (2/omega_L) * min(1, Omega(0)/Omega(d0))`` with ``omega_L`` the Lanczos value of the
+          LINEAR operator (``omega_linear``; None: measured once by :func:`modal.stable_time_step_operator`) and ``Omega(0)`` the
+          bound at ``u = 0``, computed once.  It follows the stiffening without paying for the pessimism and never exceeds the
+          linear operator's step - but it is a HEURISTIC, not a certificate: it assumes that the bound overestimates by the same
+          factor at ``d0`` as at 0.
+
+        A target below ``dt`` is taken at once; a target above ``grow * dt`` raises ``dt`` to ``grow * dt``; inside that band nothing
+        changes.  RuntimeError if an element's bound is not finite (the state holds NaN or has overflowed).  Synchronises."""
+        if mode not in ("certified", "anchored"):
+            raise ValueError(f"unknown mode {mode!r}: certified or anchored")
+        if not (gamma > 0 and grow >= 1.0):
+            raise ValueError("need gamma > 0 and grow >= 1")
+        mat = _lib.material_id(self.material)
+        bound = self.op.tangent_bound(None if mat == 0 else self.state()[0], self.material)
+        if bound["n_nonfinite"] > 0:
+            raise RuntimeError(f"follow_time_step: the bound is not finite on {bound['n_nonfinite']} element(s) at step "
+                               f"{self.steps_done}: the state holds NaN or has overflowed")
+        omega = bound["omega_max"]
+        if mode == "certified":
+            target = gamma * 2.0 / omega if omega > 0 else float("inf")
+        else:
+            if self._anchor is None:
+                if omega_linear is None:
+                    from .modal import stable_time_step_operator
+
+                    omega_linear = stable_time_step_operator(self.op, self._mass, gamma)["omega_max"]
+                self._anchor = (float(omega_linear), self.op.tangent_bound(None, "linear")["omega_max"])
+            omega_l, omega_0 = self._anchor
+            target = gamma * (2.0 / omega_l) * (min(1.0, omega_0 / omega) if omega > 0 else 1.0)
+        if target < self.dt:
+            self.set_dt(target)
+        elif target > grow * self.dt:
+            self.set_dt(grow * self.dt)
+        return self.steps_done, omega, target, self.dt
+
     def set_material(self, name):
         """The element pass becomes the finite-strain pass of ``svk`` / ``neo_hookean``, or the linear pass again
-        (``saa_operator_stepper_set_material``); clears the inversion counters.  ``dt`` is NOT adapted: it stays what the
-        stepper was made with, and under large stretch the stability limit moves below the linear operator's."""
+        (``saa_operator_stepper_set_material``); clears the inversion counters.  ``dt`` is NOT adapted by the stepper itself: it
+        stays what it was, and under large stretch the stability limit moves below the linear operator's
+        (:meth:`follow_time_step` adapts it on request)."""
         _lib.check(self._lib.saa_operator_stepper_set_material(self._h, _lib.material_id(name)))
         self.material = str(name).replace("-", "_")
 
@@ -110,6 +164,7 @@ class OperatorStepper:
 
     def step(self, n=1):
         _lib.check(self._lib.saa_operator_stepper_step(self._h, int(n)))
+        self.steps_done += int(n)
 
     def state(self):
         """``(d0, dn, tn)``: two new ``(n_dof,)`` CUDA tensors and the time, after everything enqueued has finished."""
@@ -207,12 +262,14 @@ class OperatorStepper:
     def step_finish(self, hist=None, hist_row=0):
         self._rows(hist, "hist", hist_row, 1)
         _lib.check(self._lib.saa_operator_stepper_step_finish(self._h, _dev(hist), int(hist_row)))
+        self.steps_done += 1
 
     def step_predicted(self, n, table, table_row0=0, hist=None, hist_row0=0):
         self._rows(table, "table", table_row0, n)
         self._rows(hist, "hist", hist_row0, n)
         _lib.check(self._lib.saa_operator_stepper_step_predicted(self._h, int(n), _dev(table), int(table_row0), _dev(hist),
                                                                  int(hist_row0)))
+        self.steps_done += int(n)
 
     def halo_gather(self, row):
         self._rows(row, "row", 0, 1)
@@ -471,7 +528,8 @@ def energy_report(rows):
 
 
 def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5,
-                 gamma=0.9, device=0, epart=None, energy_every=0, material="linear", dt_check_every=0):
+                 gamma=0.9, device=0, epart=None, energy_every=0, material="linear", dt_check_every=0, dt_follow=None,
+                 dt_follow_every=10):
     """What ``drivers dynamics`` computes: the operator of ``cells`` (4 columns: order 1, 10: order 2) clamped on
     ``dirichlet_nodes``, its lumped mass, the reference load ``(0, -fz, -fz)`` ramped over ``t < 1``, ``dt = gamma *
     2/omega_max`` and ``n_steps`` steps recorded every ``save_every``.  Returns ``(trajectory (n_dof, n_cols) array,
@@ -487,11 +545,30 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
     each, the last included, :meth:`OperatorStepper.stable_time_step` measures the limit at the current state; the report
     gains ``dt_check``: ``every``, ``n_checks``, ``dt_crit_min`` and the step count ``dt_crit_min_step`` at which it was seen,
     ``dt_over_dt_crit_max`` and ``first_exceeded_step`` (the step count of the first check with ``dt > dt_crit``, -1: never).
-    ``dt`` is not changed during the run."""
+    ``dt`` is not changed during the run - unless ``dt_follow`` is ``"certified"`` or ``"anchored"`` (a nonlinear material on
+    the whole mesh without the energy balance, ValueError otherwise): then :meth:`OperatorStepper.follow_time_step` checks the
+    step before step 0 and after every ``dt_follow_every`` steps and changes it by that method's rule, ``dt_check`` reports
+    against the ``dt`` in use at each check, the report gains ``dt_follow`` (``mode``, ``every``, ``n_checks``, ``n_changes``,
+    ``dt_first``, ``dt_min``, ``dt_last``, ``omega_bound_0``, ``omega_bound_max`` and ``bound_over_lanczos_0``, the bound at ``u = 0``
+    over the Lanczos ``omega_max`` of the linear operator) and the return value a third member, ``{"t", "step", "dt"}``: the time
+    of every saved column - they are no longer equidistant - and the ``(step, dt)`` list of the run, the first entry the step
+    it began with.  Without ``dt_follow`` the report and the return value are what they were, key for key."""
     import torch
 
     mat = _lib.material_id(material)
     material = str(material).replace("-", "_")
+    dt_follow_every = int(dt_follow_every or 0)
+    if dt_follow is not None:
+        if dt_follow not in ("certified", "anchored"):
+            raise ValueError(f"dt_follow must be None, 'certified' or 'anchored', not {dt_follow!r}")
+        if dt_follow_every < 1:
+            raise ValueError("dt_follow_every must be >= 1")
+        if mat == 0:
+            raise ValueError("following the time step is for a nonlinear material: the linear operator's limit does not move")
+        if epart is not None:
+            raise ValueError("following the time step is not defined for a partition: a rank holds only its share of the internal force")
+        if energy_every:
+            raise ValueError("following the time step is not defined with the energy balance: its identity assumes one dt")
     if mat != 0 and energy_every:
         raise ValueError("the energy balance is defined for the linear material only: its identity needs a symmetric constant K")
     dt_check_every = int(dt_check_every or 0)
@@ -519,7 +596,21 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
         with OperatorStepper(op, mass, op.load((0.0, -fz, -fz)), ts["dt"], alpha, ramp=True, material=material) as st:
             traj = st.record(n_cols, save_every) if n_cols > 0 else None
             rows = st.record_energy(n_rows, energy_every) if n_rows > 0 else None
-            if dt_check_every:
+            if dt_follow is not None:
+                # follow before step 0 and after every dt_follow_every steps, measure after every dt_check_every steps
+                checks, follows, done, total = [], [], 0, int(n_steps)
+                while done < total:
+                    if done % dt_follow_every == 0:
+                        follows.append(st.follow_time_step(dt_follow, gamma, omega_linear=ts["omega_max"]))
+                    stops = [total, (done // dt_follow_every + 1) * dt_follow_every]
+                    if dt_check_every:
+                        stops.append((done // dt_check_every + 1) * dt_check_every)
+                    n = min(stops) - done
+                    st.step(n)
+                    done += n
+                    if dt_check_every and (done % dt_check_every == 0 or done == total):
+                        checks.append((done, st.stable_time_step(gamma)))
+            elif dt_check_every:
                 checks, done = [], 0
                 while done < int(n_steps):
                     n = min(dt_check_every, int(n_steps) - done)
@@ -544,7 +635,13 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
             report.update(material=material, inverted=inverted, first_inverted_step=first_inverted)
         if dt_check_every:
             report["dt_check"] = dt_check_report(checks, dt_check_every)
+        if dt_follow is not None:
+            omega_0 = op.tangent_bound(None, "linear")["omega_max"]
+            report["dt_follow"], times = dt_follow_report(follows, dt_follow, dt_follow_every, ts["dt"], omega_0, ts["omega_max"],
+                                                          int(n_steps), int(save_every), n_cols)
     torch.cuda.synchronize(device)
+    if dt_follow is not None:
+        return store, report, times
     if energy_every:
         report["energy"] = energy_report(table)
         return store, report, table
@@ -561,6 +658,28 @@ def dt_check_report(checks, every):
                    dt_over_dt_crit_max=max(c[1]["dt_over_dt_crit"] for c in checks),
                    first_exceeded_step=next((s for s, c in checks if c["dt_over_dt_crit"] > 1.0), -1))
     return out
+
+
+def dt_follow_report(follows, mode, every, dt_created, omega_bound_0, omega_lanczos_0, n_steps, save_every, n_cols):
+    """What ``drivers dynamics --dt-follow`` prints of the records ``[(step, Omega, target, dt)]`` of
+    :meth:`OperatorStepper.follow_time_step`, and the times of the run: ``(report, {"t": (n_cols,), "step": (k,), "dt": (k,)})``
+    with ``t[c]`` the time of saved column ``c`` (the state after step ``c * save_every``, the ramp's clock starting at 0) and
+    ``(step[j], dt[j])`` the step in use from step ``step[j]`` on, the first entry the step of the first check."""
+    dts = [r[3] for r in follows]
+    steps = np.array([r[0] for r in follows], dtype=np.int64)
+    per_step = np.zeros(int(n_steps))
+    for j, r in enumerate(follows):
+        per_step[r[0]:(follows[j + 1][0] if j + 1 < len(follows) else int(n_steps))] = r[3]
+    after = np.cumsum(per_step)                                       # the time after step i
+    t = after[np.arange(int(n_cols), dtype=np.int64) * int(save_every)] if n_cols > 0 else np.zeros(0)
+    changed = [0] + [j for j in range(1, len(dts)) if dts[j] != dts[j - 1]]   # the first check, then every check that moved dt
+    report = {"mode": mode, "every": int(every), "n_checks": len(follows),
+              "n_changes": sum(a != b for a, b in zip([dt_created] + dts[:-1], dts)),
+              "dt_first": dts[0] if dts else None, "dt_min": min(dts) if dts else None, "dt_last": dts[-1] if dts else None,
+              "omega_bound_0": omega_bound_0, "omega_bound_max": max((r[1] for r in follows), default=None),
+              "bound_over_lanczos_0": omega_bound_0 / omega_lanczos_0}
+    keep = np.array(changed, dtype=np.int64)
+    return report, {"t": t, "step": steps[keep] if dts else steps, "dt": np.array(dts)[keep] if dts else np.zeros(0)}
 
 
 def _run_dynamics_parts(points, cells, dirichlet_nodes, epart, n_steps, save_every, E, nu, rho, fz, alpha, gamma, device,

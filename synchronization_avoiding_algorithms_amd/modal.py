@@ -246,6 +246,34 @@ class ModalOperator:
             out["omega_e"] = om
         return out
 
+    def tangent_bound(self, u, material="svk", return_omega=False) -> dict:
+        """An upper bound of ``omega_max`` of ``M_L^-1 K_T(u)`` from one element pass (``saa_operator_tangent_bound``, either
+        order): ``omega_max = max_e omega_e`` and its ``element`` (ties: the lowest index; 0 and -1 when no element enters the
+        maximum), ``n_nonpositive`` (elements with ``detJ <= 0`` at a point: the bound is ``certified`` only when 0),
+        ``n_inverted`` (neo-Hooke elements with ``!(J > 0)`` at a point: ``omega_e = 0``, left out of the maximum) and
+        ``n_nonfinite`` (elements whose ``omega_e`` is not finite: left out and counted); ``omega_e`` (a CUDA tensor) on request.
+        ``u``: an ``(n_dof,)`` float64 CUDA tensor, masked on Dirichlet dofs on input; None with ``linear``, whose operator does
+        not depend on it.  A bound, not an estimate: ``include/saa_hip.h`` has the definition.  Synchronises."""
+        import torch
+
+        mat = _lib.material_id(material)
+        if u is None:
+            if mat != 0:
+                raise ValueError("a nonlinear material needs the state at which its tangent is taken")
+        elif not (torch.is_tensor(u) and u.is_cuda and u.dtype == torch.float64 and u.numel() == self.n_dof):
+            raise ValueError(f"u must be a float64 CUDA tensor of {self.n_dof} values")
+        u = u.reshape(-1).contiguous() if u is not None else None
+        om = torch.empty(self.n_elems, dtype=torch.float64, device=self.torch_device) if return_omega else None
+        wmax, arg, counts = C.c_double(), C.c_int32(), (C.c_int64 * 3)()
+        _lib.check(self._lib.saa_operator_tangent_bound(self._h, mat, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                        C.c_void_p(om.data_ptr()) if om is not None else None, C.byref(wmax),
+                                                        C.byref(arg), counts))
+        out = {"omega_max": wmax.value, "element": arg.value, "n_nonpositive": int(counts[0]), "n_inverted": int(counts[1]),
+               "n_nonfinite": int(counts[2]), "certified": int(counts[0]) == 0}
+        if return_omega:
+            out["omega_e"] = om
+        return out
+
 
 # ------------------------------------------------------------------------------------------------------------------
 # Solvers on plain callables
