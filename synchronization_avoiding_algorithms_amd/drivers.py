@@ -6,7 +6,9 @@ reference's ``Eigen_mode``), :func:`dynamics` (the explicit run of one whole mes
 the reference has none for ``p = 2``), :func:`stress` (stress recovery from the saved trajectories) and :func:`estimate` (the
 Zienkiewicz-Zhu estimate of the stress error of the mesh, the scale for the error of the modelled run; neither has a
 counterpart in the reference; :func:`stress_finite` and :func:`estimate_finite` are the two at finite strain, on the run of
-:func:`dynamics` with a nonlinear material); same artefact names under ``Results/`` and
+:func:`dynamics` with a nonlinear material, :func:`stress_p2` and :func:`estimate_p2` the two for quadratic tetrahedra; these
+four are thin calls into one whole-mesh stress driver and one whole-mesh estimate driver, :func:`_whole_stress` and
+:func:`_whole_estimate`, which take the order and the material); same artefact names under ``Results/`` and
 ``Distributed_save/``, same constants by default.  Launch like the reference's
 ``mpirun -np P python3 X.py``:
 
@@ -389,20 +391,23 @@ def _host_value(v):
     return v.cpu().numpy() if hasattr(v, "cpu") else v
 
 
-def _device_recovery(device=0):
-    """The GPU side of :func:`stress` and :func:`estimate`, and its only one: a factory ``make(points, cells, lmd, mu)`` of
+def _device_recovery(device=0, order=1):
+    """The GPU side of the stress and estimate drivers, and its only one: a factory ``make(points, cells, lmd, mu)`` of
     objects with NumPy-in / NumPy-out ``element(X (m, n_dof))`` (the dict of :meth:`stress.StressRecovery.element`),
     ``nodal(E (m, n_elems, k))``, ``error(sigma_elem, nodal=None, other=None)`` (the dict of
     :meth:`stress.StressRecovery.error`), ``history(traj (n_dof, n_cols))`` and ``close()`` on
-    :class:`stress.StressRecovery`.  Tests pass a NumPy stand-in with the same methods.  ``element`` and ``history`` hand
-    ``material=`` and ``measure=`` on; only :func:`stress_finite` and :func:`estimate_finite` give them."""
+    :class:`stress.StressRecovery` (``order=1``, 4-node cells) or :class:`stress.QuadraticStressRecovery` (``order=2``,
+    10-node cells).  Tests pass a NumPy stand-in with the same methods.  ``element`` and ``history`` hand ``material=`` and
+    ``measure=`` on; only :func:`stress_finite` and :func:`estimate_finite` give them."""
     import torch
 
-    from .stress import StressRecovery
+    from .stress import QuadraticStressRecovery, StressRecovery
+
+    Recovery = QuadraticStressRecovery if order == 2 else StressRecovery
 
     class _Host:
         def __init__(self, points, cells, lmd, mu):
-            self.rec = StressRecovery(points, cells, lmd, mu, device=device)
+            self.rec = Recovery(points, cells, lmd, mu, device=device)
 
         def _dev(self, a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.rec.torch_device)
@@ -437,6 +442,38 @@ def _abs_volumes(points, tets):
     vol = np.abs(np.einsum("ij,ij->i", points[tets[:, 1]] - points[tets[:, 0]],
                            np.cross(points[tets[:, 2]] - points[tets[:, 0]], points[tets[:, 3]] - points[tets[:, 0]])))
     return vol / 6.0
+
+
+def _resolve_columns(columns, n_cols):
+    """``columns`` as indices into ``n_cols`` saved columns (negative = from the end)."""
+    cols = []
+    for j in columns:
+        jj = int(j) + n_cols if int(j) < 0 else int(j)
+        if not 0 <= jj < n_cols:
+            raise ValueError(f"column {j} out of range for {n_cols} saved columns")
+        cols.append(jj)
+    return cols
+
+
+def _zz_entry(zz, energy_total, i, centroid):
+    """The Zienkiewicz-Zhu figures of row ``i`` of ``zz`` (the dict of ``error``) and of the strain energies: ``eta``,
+    ``energy_norm = sqrt(2 W)``, ``relative = eta / sqrt(energy_norm^2 + eta^2)`` and the element of the largest ``eta_e^2``."""
+    eta2, w2 = float(zz["eta2_total"][i]), 2.0 * float(energy_total[i])
+    e = int(zz["eta2_argmax"][i])
+    return {"eta": float(np.sqrt(eta2)), "energy_norm": float(np.sqrt(w2)),
+            "relative": float(np.sqrt(eta2 / (w2 + eta2))) if w2 + eta2 > 0 else 0.0, "element": e,
+            "eta2_max": float(zz["eta2_max"][i]), "centroid": [float(c) for c in centroid[e]]}
+
+
+def _point_data(disp, nodal):
+    """Point data of one column, either order: the displacement ``(3 n,)`` or ``(n, 3)``, the recovered stress ``sigma*
+    (n, 6)`` and its von Mises value."""
+    from .stress import VOIGT, von_mises
+
+    pd = {f"displacement-{c}": disp.reshape(-1, 3)[:, a] for a, c in enumerate("xyz")}
+    pd.update({f"sigma-{c}": nodal[:, a] for a, c in enumerate(VOIGT)})
+    pd["von-mises"] = von_mises(nodal)
+    return pd
 
 
 def _load_recovery_tree(p, tets, nn, runs, columns):
@@ -492,13 +529,37 @@ def _load_recovery_tree(p, tets, nn, runs, columns):
         for r, data in enumerate(trajs[run]):
             if data.shape[1] != n_cols:
                 raise ValueError(f"{p[run].format(r=r)}: {data.shape[1]} saved columns, rank 0 has {n_cols}")
-    cols = []
-    for j in columns:
-        jj = int(j) + n_cols if int(j) < 0 else int(j)
-        if not 0 <= jj < n_cols:
-            raise ValueError(f"column {j} out of range for {n_cols} saved columns")
-        cols.append(jj)
-    return ranks, local_cells, trajs, n_cols, cols
+    return ranks, local_cells, trajs, n_cols, _resolve_columns(columns, n_cols)
+
+
+def _tree_setup(mesh, out_dir, columns, modeled, device, E, nu, recovery):
+    """What :func:`stress` and :func:`estimate` open with: the recovery factory with the Lame constants bound
+    (``make(points, cells)``), the mesh's points and cells, ``PATHS`` under ``out_dir`` and :func:`_load_recovery_tree` of
+    the synchronised run (``truth``) and, with ``modeled``, the modelled one."""
+    from . import fem_setup as fs
+
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    factory = _device_recovery(device) if recovery is None else recovery
+    points = np.asarray(mesh.points, dtype=np.float64)
+    tets = np.asarray(mesh.tets, dtype=np.int64)
+    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+    runs = ["truth"] + (["modeled"] if modeled else [])
+    return (lambda pts, cells: factory(pts, cells, lmd, mu), points, tets, p,
+            *_load_recovery_tree(p, tets, len(points), runs, columns))
+
+
+def _each_rank(make, points, ranks, local_cells, trajs, visit):
+    """The per-rank loop of :func:`stress` and :func:`estimate`: for every rank that owns elements one recovery on its local
+    nodes and cells, and ``visit(run, rec, T, elems)`` per run with the rank's trajectory ``T`` and its element ids."""
+    for r, (nodes, elems) in enumerate(ranks):
+        if not len(elems):
+            continue
+        rec = make(points[nodes], local_cells[r])
+        try:
+            for run in trajs:
+                visit(run, rec, trajs[run][r], elems)
+        finally:
+            rec.close()
 
 
 def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=True, device=0, E=None, nu=None,
@@ -510,46 +571,34 @@ def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=T
     ``Results/Stress/Stress-col-{j}.vtk`` (and ``Modeled_Stress-col-{j}.vtk`` with ``modeled``) unless ``vtk`` is
     False; ``history`` writes every column's strain energy and von Mises maximum to ``Results/Stress/history.npz``.
     Returns the report that the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` (default: the GPU)."""
-    from . import fem_setup as fs
-    from .stress import VOIGT, von_mises
+    from .stress import VOIGT
 
-    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
-    make = _device_recovery(device) if recovery is None else recovery
-    points = np.asarray(mesh.points, dtype=np.float64)
-    tets = np.asarray(mesh.tets, dtype=np.int64)
-    ne, nn = len(tets), len(points)
-    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
+    make, points, tets, p, ranks, local_cells, trajs, n_cols, cols = _tree_setup(mesh, out_dir, columns, modeled, device, E,
+                                                                                 nu, recovery)
+    ne, nn, m, runs = len(tets), len(points), len(cols), list(trajs)
 
-    runs = ["truth"] + (["modeled"] if modeled else [])
-    ranks, local_cells, trajs, n_cols, cols = _load_recovery_tree(p, tets, nn, runs, columns)
-    m = len(cols)
+    def extremes(n):
+        return dict(total=np.zeros(n), vmax=np.full(n, -np.inf), arg=np.full(n, -1, dtype=np.int64))
 
-    fields = {run: dict(sigma=np.zeros((m, ne, 6)), von_mises=np.zeros((m, ne)), energy=np.zeros((m, ne)),
-                        total=np.zeros(m), vmax=np.full(m, -np.inf), arg=np.full(m, -1, dtype=np.int64)) for run in runs}
-    hist = {run: dict(total=np.zeros(n_cols), vmax=np.full(n_cols, -np.inf), arg=np.full(n_cols, -1, dtype=np.int64))
-            for run in runs}
-    for r, (nodes, elems) in enumerate(ranks):
-        if not len(elems):
-            continue
-        rec = make(points[nodes], local_cells[r], lmd, mu)
-        try:
-            for run in runs:
-                T = trajs[run][r]
-                f = fields[run]
-                if m:
-                    res = rec.element(np.ascontiguousarray(T[:, cols].T))
-                    for k in ("sigma", "von_mises", "energy"):
-                        f[k][:, elems] = res[k]
-                    f["total"] += res["energy_total"]
-                    f["vmax"], f["arg"] = _merge_max(f["vmax"], f["arg"], res["von_mises_max"],
-                                                     elems[np.asarray(res["von_mises_argmax"], dtype=np.int64)])
-                if history:
-                    h, hr = hist[run], rec.history(T)
-                    h["total"] += hr["energy_total"]
-                    h["vmax"], h["arg"] = _merge_max(h["vmax"], h["arg"], hr["von_mises_max"],
-                                                     elems[np.asarray(hr["von_mises_argmax"], dtype=np.int64)])
-        finally:
-            rec.close()
+    fields = {run: dict(sigma=np.zeros((m, ne, 6)), von_mises=np.zeros((m, ne)), energy=np.zeros((m, ne)), **extremes(m))
+              for run in runs}
+    hist = {run: extremes(n_cols) for run in runs}
+
+    def merge(f, res, elems):  # a rank's energy and von Mises maximum into those of the whole mesh
+        f["total"] += res["energy_total"]
+        f["vmax"], f["arg"] = _merge_max(f["vmax"], f["arg"], res["von_mises_max"],
+                                         elems[np.asarray(res["von_mises_argmax"], dtype=np.int64)])
+
+    def visit(run, rec, T, elems):
+        if m:
+            res = rec.element(np.ascontiguousarray(T[:, cols].T))
+            for k in ("sigma", "von_mises", "energy"):
+                fields[run][k][:, elems] = res[k]
+            merge(fields[run], res, elems)
+        if history:
+            merge(hist[run], rec.history(T), elems)
+
+    _each_rank(make, points, ranks, local_cells, trajs, visit)
 
     centroid = points[tets].mean(axis=1)
     interface = np.isin(tets, rio.load_int_list(p["global_shared"])).any(axis=1) if modeled else None
@@ -577,7 +626,7 @@ def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=T
 
     if vtk and m:
         vol = _abs_volumes(points, tets)
-        whole = make(points, tets, lmd, mu)
+        whole = make(points, tets)
         try:
             nodal = {run: whole.nodal(fields[run]["sigma"]) for run in runs}
         finally:
@@ -588,14 +637,12 @@ def stress(mesh, out_dir=".", columns=(-1,), modeled=False, history=False, vtk=T
                 disp[:, ranks[r][0]] = trajs[run][r][:, cols].T.reshape(m, -1, 3)
             for i, j in enumerate(cols):
                 f = fields[run]
-                pd = {f"displacement-{c}": disp[i, :, a] for a, c in enumerate("xyz")}
-                pd.update({f"sigma-{c}": nodal[run][i, :, a] for a, c in enumerate(VOIGT)})
-                pd["von-mises"] = von_mises(nodal[run][i])
                 cd = {f"sigma-{c}": f["sigma"][i, :, a] for a, c in enumerate(VOIGT)}
                 cd["von-mises"] = f["von_mises"][i]
                 cd["energy-density"] = np.divide(f["energy"][i], vol, out=np.zeros(ne), where=vol > 0)
                 key = "stress_vtk" if run == "truth" else "modeled_stress_vtk"
-                report["files"].append(rio.write_vtk_fields(p[key].format(j=j), points, tets, pd, cd,
+                report["files"].append(rio.write_vtk_fields(p[key].format(j=j), points, tets,
+                                                            _point_data(disp[i], nodal[run][i]), cd,
                                                             title=f"stress, saved column {j} ({run})"))
     if history:
         out = {"columns": np.arange(n_cols)}
@@ -621,34 +668,22 @@ def estimate(mesh, out_dir=".", columns=(-1,), modeled=False, vtk=True, device=0
     ``Results/Stress/Estimate-col-{j}.vtk`` (cell data ``eta2``, ``error-density = eta2 / |V_e|`` and, with ``modeled``,
     ``model-error2``) unless ``vtk`` is False.  Returns the report that the CLI prints as JSON.  ``recovery``: see
     :func:`_device_recovery` (default: the GPU)."""
-    from . import fem_setup as fs
-
-    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
-    make = _device_recovery(device) if recovery is None else recovery
-    points = np.asarray(mesh.points, dtype=np.float64)
-    tets = np.asarray(mesh.tets, dtype=np.int64)
-    ne, nn = len(tets), len(points)
-    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
-    runs = ["truth"] + (["modeled"] if modeled else [])
-    ranks, local_cells, trajs, n_cols, cols = _load_recovery_tree(p, tets, nn, runs, columns)
-    m = len(cols)
+    make, points, tets, p, ranks, local_cells, trajs, n_cols, cols = _tree_setup(mesh, out_dir, columns, modeled, device, E,
+                                                                                 nu, recovery)
+    ne, nn, m, runs = len(tets), len(points), len(cols), list(trajs)
 
     sigma = {run: np.zeros((m, ne, 6)) for run in runs}
     energy = {run: np.zeros(m) for run in runs}
-    for r, (nodes, elems) in enumerate(ranks):
-        if not len(elems) or not m:
-            continue
-        rec = make(points[nodes], local_cells[r], lmd, mu)
-        try:
-            for run in runs:
-                res = rec.element(np.ascontiguousarray(trajs[run][r][:, cols].T))
-                sigma[run][:, elems] = res["sigma"]
-                energy[run] += res["energy_total"]
-        finally:
-            rec.close()
+
+    def visit(run, rec, T, elems):
+        res = rec.element(np.ascontiguousarray(T[:, cols].T))
+        sigma[run][:, elems] = res["sigma"]
+        energy[run] += res["energy_total"]
+
     zz, model = {}, None
     if m:
-        whole = make(points, tets, lmd, mu)
+        _each_rank(make, points, ranks, local_cells, trajs, visit)
+        whole = make(points, tets)
         try:
             for run in runs:
                 zz[run] = whole.error(sigma[run], nodal=whole.nodal(sigma[run]))
@@ -660,20 +695,13 @@ def estimate(mesh, out_dir=".", columns=(-1,), modeled=False, vtk=True, device=0
     centroid = points[tets].mean(axis=1)
     interface = np.isin(tets, rio.load_int_list(p["global_shared"])).any(axis=1) if modeled else None
 
-    def summary(run, i):
-        eta2, w2 = float(zz[run]["eta2_total"][i]), 2.0 * float(energy[run][i])
-        e = int(zz[run]["eta2_argmax"][i])
-        return {"eta": float(np.sqrt(eta2)), "energy_norm": float(np.sqrt(w2)),
-                "relative": float(np.sqrt(eta2 / (w2 + eta2))) if w2 + eta2 > 0 else 0.0, "element": e,
-                "eta2_max": float(zz[run]["eta2_max"][i]), "centroid": [float(c) for c in centroid[e]]}
-
     report = {"n_elems": ne, "n_nodes": nn, "n_ranks": len(ranks), "n_saved": n_cols, "columns": [], "files": []}
     for i, j in enumerate(cols):
-        entry = {"column": j, **summary("truth", i)}
+        entry = {"column": j, **_zz_entry(zz["truth"], energy["truth"], i, centroid)}
         if modeled:
             eta2, me2 = zz["truth"]["eta2"][i], model["eta2"][i]
             above = me2 > eta2
-            entry["modeled"] = summary("modeled", i)
+            entry["modeled"] = _zz_entry(zz["modeled"], energy["modeled"], i, centroid)
             entry.update({"model_error": float(np.sqrt(model["eta2_total"][i])),
                           "model_over_discretisation": float(np.sqrt(model["eta2_total"][i])) / entry["eta"]
                           if entry["eta"] > 0 else None,
@@ -697,45 +725,18 @@ def estimate(mesh, out_dir=".", columns=(-1,), modeled=False, vtk=True, device=0
     return report
 
 
-def _device_recovery_p2(device=0):
-    """The GPU side of :func:`stress_p2` and :func:`estimate_p2`: a factory ``make(points, cells10, lmd, mu)`` of objects
-    with NumPy-in / NumPy-out ``element``, ``nodal``, ``error``, ``history`` and ``close()`` on
-    :class:`stress.QuadraticStressRecovery`.  Tests pass a NumPy stand-in with the same methods."""
-    import torch
-
-    from .stress import QuadraticStressRecovery
-
-    class _Host:
-        def __init__(self, points, cells10, lmd, mu):
-            self.rec = QuadraticStressRecovery(points, cells10, lmd, mu, device=device)
-
-        def _dev(self, a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.rec.torch_device)
-
-        def element(self, X, **finite):
-            return {k: _host_value(v) for k, v in self.rec.element(self._dev(X), **finite).items()}
-
-        def nodal(self, sigma):
-            return self.rec.nodal(self._dev(sigma)).cpu().numpy()
-
-        def error(self, sigma, nodal=None, other=None):
-            res = self.rec.error(self._dev(sigma), nodal=None if nodal is None else self._dev(nodal),
-                                 other=None if other is None else self._dev(other))
-            return {k: v.cpu().numpy() for k, v in res.items()}
-
-        def history(self, traj, **finite):
-            return {k: _host_value(v) for k, v in self.rec.history(traj, **finite).items()}
-
-        def close(self):
-            self.rec.close()
-
-    return _Host
-
-
-def _load_run(mesh, out_dir, columns, order):
-    """The whole-mesh run of ``dynamics --order {order}``: the mesh with its 4- or 10-node cells (order 2: elevated like
+def _whole_setup(mesh, out_dir, columns, order, material, measure, device, E, nu, recovery):
+    """What the whole-mesh drivers open with.  ``make()`` builds the recovery of ``order`` on the mesh (``recovery``, or the
+    GPU's).  The run of ``dynamics --order {order}``: the mesh's points and its 4- or 10-node cells (order 2: elevated like
     ``dynamics --order 2``), the trajectory ``Results/Dynamics/Displacement_order{order}.hdf5`` under ``out_dir`` with 3 rows
-    per node, and ``columns`` resolved against its saved columns (negative = from the end)."""
+    per node, and ``columns`` resolved against its saved columns.  ``kernels``: the keywords of ``element`` and ``history``,
+    none for ``material = "linear"`` - the linear kernels take neither ``material`` nor ``measure``.  ``path(key, j=...)``: the
+    entry ``key + "_p2"`` (linear) or ``key + "_fs"`` of ``PATHS`` under ``out_dir``.  The report up to ``files``; ``material``
+    and ``measure`` are in it only at finite strain."""
+    from . import fem_setup as fs
+
+    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
+    factory = _device_recovery(device, order) if recovery is None else recovery
     if order == 2:
         mesh = _quadratic(mesh)
     points = np.asarray(mesh.points, dtype=np.float64)
@@ -748,29 +749,124 @@ def _load_run(mesh, out_dir, columns, order):
     if traj.ndim != 2 or traj.shape[0] != 3 * len(points):
         raise ValueError(f"{path}: {traj.shape[0] if traj.ndim else 0} rows, expected 3 * {len(points)} = {3 * len(points)} "
                          + ("(3 per node of the elevated mesh)" if order == 2 else "(3 per node)"))
-    n_cols = traj.shape[1]
-    cols = []
-    for j in columns:
-        jj = int(j) + n_cols if int(j) < 0 else int(j)
-        if not 0 <= jj < n_cols:
-            raise ValueError(f"column {j} out of range for {n_cols} saved columns")
-        cols.append(jj)
-    return points, cells, traj, n_cols, cols
+    cols = _resolve_columns(columns, traj.shape[1])
+    finite = material != "linear"
+    kernels = {"material": material, "measure": measure} if finite else {}
+    key, names = ("_fs", {"material": material, "p": order}) if finite else ("_p2", {})
+    report = {"order": order, "n_elems": len(cells), "n_nodes": len(points), "n_ranks": 1, "n_saved": traj.shape[1],
+              **({"material": material, "measure": str(measure)} if finite else {}), "columns": [], "files": []}
+    return (lambda: factory(points, cells, lmd, mu), points, cells, traj, cols, kernels,
+            lambda k, **j: os.path.join(out_dir, PATHS[k + key]).format(**names, **j), report)
 
 
-def _load_p2_run(mesh, out_dir, columns):
-    """What :func:`stress_p2` and :func:`estimate_p2` read: :func:`_load_run` of order 2."""
-    return _load_run(mesh, out_dir, columns, 2)
+def _finite_material(material, order):
+    """The material's name as :func:`stress_finite` and :func:`estimate_finite` report it; they refuse an ``order`` that is
+    not 1 or 2 and the linear material."""
+    from ._lib import material_id
+
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    if material_id(material) == 0:
+        raise ValueError("stress_finite / estimate_finite are for svk and neo_hookean; the linear material has stress, "
+                         "stress_p2, estimate and estimate_p2")
+    return str(material).replace("-", "_")
 
 
-def _p2_point_data(traj_cols, nodal):
-    """Point data of one column: the displacement, the recovered stress ``sigma*`` and its von Mises value."""
-    from .stress import VOIGT, von_mises
+def _cell_data(res, i, finite):
+    """Cell data of one column: the largest point von Mises and ``W_e`` of every element, at finite strain also its smallest
+    ``det F``."""
+    ne = len(res["energy"][i])
+    cd ={"von-mises-max": np.asarray(res["von_mises"][i]).reshape(ne, -1).max(axis=1), "energy": res["energy"][i]}
+    if finite:
+        cd["det-f-min"] = np.asarray(res["det_f"][i]).reshape(ne, -1).min(axis=1)
+    return cd
 
-    pd = {f"displacement-{c}": traj_cols.reshape(-1, 3)[:, a] for a, c in enumerate("xyz")}
-    pd.update({f"sigma-{c}": nodal[:, a] for a, c in enumerate(VOIGT)})
-    pd["von-mises"] = von_mises(nodal)
-    return pd
+
+def _finite_figures(res, i, measure):
+    """What a column's entry holds at finite strain next to the material: the measure, the inverted elements, the smallest
+    ``det F``."""
+    return {"measure": measure, "n_inverted": int(res["n_inverted"][i]), "min_det_f": float(np.min(res["det_f"][i]))}
+
+
+def _whole_stress(mesh, out_dir, columns, order, material, measure, history, vtk, device, E, nu, recovery):
+    """The whole-mesh stress driver behind :func:`stress_p2` (order 2, ``material = "linear"``: the linear kernels, which
+    are given neither ``material`` nor ``measure``) and :func:`stress_finite` (either order, the material's name).  Linear
+    elements with the linear material are :func:`stress`'s, on the partitioned tree."""
+    from .Tools.Qudrature import Gauss_Legendre
+    from .Tools.Shape_function_Deriv import Shape_Function
+
+    make, points, cells, traj, cols, kernels, path, report = _whole_setup(mesh, out_dir, columns, order, material, measure,
+                                                                          device, E, nu, recovery)
+    finite, nq = material != "linear", 4 if order == 2 else 1
+    # (4, 10): N_a at the Gauss points
+    shape4 = np.array([Shape_Function(2, x) for x in Gauss_Legendre(2)[0]]) if order == 2 else None
+    centroid = points[cells[:, :4]].mean(axis=1)
+    report["history"] = None
+    rec = make()
+    try:
+        if cols:
+            X = np.ascontiguousarray(traj[:, cols].T)
+            res = rec.element(X, **kernels)
+            nodal = rec.nodal(res["sigma"]) if vtk else None
+            for i, j in enumerate(cols):
+                e, q = divmod(int(res["von_mises_argmax"][i]), nq)
+                entry = {"column": j, "strain_energy": float(res["energy_total"][i]),
+                         "von_mises_max": float(res["von_mises_max"][i]), "element": e}
+                if order == 2:
+                    entry.update({"gauss_point": q, "position": [float(c) for c in shape4[q] @ points[cells[e]]]})
+                entry["centroid"] = [float(c) for c in centroid[e]]
+                if finite:
+                    entry.update({**_finite_figures(res, i, res["measure"]), "material": material})
+                report["columns"].append(entry)
+                if vtk:
+                    title = f"{measure} stress, {material}, order {order}" if finite else "stress, quadratic tetrahedra"
+                    report["files"].append(rio.write_vtk_fields(path("stress_vtk", j=j), points, cells,
+                                                                _point_data(X[i], nodal[i]), _cell_data(res, i, finite),
+                                                                title=f"{title}, saved column {j}"))
+        if history:
+            h = rec.history(traj, **kernels)
+            arg = np.asarray(h["von_mises_argmax"], dtype=np.int64)
+            out = dict(columns=np.arange(traj.shape[1]), strain_energy=h["energy_total"], von_mises_max=h["von_mises_max"],
+                       von_mises_element=arg // nq, von_mises_gauss_point=arg % nq)
+            if finite:
+                out.update(n_inverted=h["n_inverted"], min_det_f=h["min_det_f"])
+            report["history"] = path("stress_history")
+            os.makedirs(os.path.dirname(report["history"]), exist_ok=True)
+            np.savez(report["history"], **out)
+    finally:
+        rec.close()
+    return report
+
+
+def _whole_estimate(mesh, out_dir, columns, order, material, vtk, device, E, nu, recovery):
+    """The whole-mesh estimate driver behind :func:`estimate_p2` (order 2, ``material = "linear"``) and
+    :func:`estimate_finite` (either order, the material's name: the second Piola-Kirchhoff stress), on the run and with the
+    rules of :func:`_whole_stress`."""
+    make, points, cells, traj, cols, kernels, path, report = _whole_setup(mesh, out_dir, columns, order, material, "pk2",
+                                                                          device, E, nu, recovery)
+    finite = material != "linear"
+    centroid = points[cells[:, :4]].mean(axis=1)
+    if not cols:
+        return report
+    rec = make()
+    try:
+        X = np.ascontiguousarray(traj[:, cols].T)
+        res = rec.element(X, **kernels)
+        nodal = rec.nodal(res["sigma"])
+        zz = rec.error(res["sigma"], nodal=nodal)
+    finally:
+        rec.close()
+    for i, j in enumerate(cols):
+        entry = {"column": j, **_zz_entry(zz, res["energy_total"], i, centroid)}
+        if finite:
+            entry.update({"material": material, **_finite_figures(res, i, "pk2")})
+        report["columns"].append(entry)
+        if vtk:
+            title = f"{material}, order {order}" if finite else "quadratic tetrahedra"
+            report["files"].append(rio.write_vtk_fields(path("estimate_vtk", j=j), points, cells, _point_data(X[i], nodal[i]),
+                                                        {**_cell_data(res, i, finite), "eta2": zz["eta2"][i]},
+                                                        title=f"stress error estimate, {title}, saved column {j}"))
+    return report
 
 
 def stress_p2(mesh, out_dir=".", columns=(-1,), history=False, vtk=True, device=0, E=None, nu=None, recovery=None):
@@ -780,48 +876,8 @@ def stress_p2(mesh, out_dir=".", columns=(-1,), history=False, vtk=True, device=
     ``Results/Stress/Stress-order2-col-{j}.vtk`` (type-24 cells; point data: displacement, the recovered stress ``sigma*``
     and its von Mises; cell data: the largest Gauss-point von Mises and ``W_e``) unless ``vtk`` is False; ``history`` writes
     every column's strain energy and von Mises maximum to ``Results/Stress/history-order2.npz``.  Returns the report that
-    the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery_p2` (default: the GPU)."""
-    from . import fem_setup as fs
-    from .Tools.Qudrature import Gauss_Legendre
-    from .Tools.Shape_function_Deriv import Shape_Function
-
-    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
-    make = _device_recovery_p2(device) if recovery is None else recovery
-    points, cells, traj, n_cols, cols = _load_p2_run(mesh, out_dir, columns)
-    ne, nn, m = len(cells), len(points), len(cols)
-    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
-    shape4 = np.array([Shape_Function(2, x) for x in Gauss_Legendre(2)[0]])      # (4, 10): N_a at the Gauss points
-    centroid = points[cells[:, :4]].mean(axis=1)
-
-    report = {"order": 2, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "columns": [], "files": [],
-              "history": None}
-    rec = make(points, cells, lmd, mu)
-    try:
-        if m:
-            X = np.ascontiguousarray(traj[:, cols].T)
-            res = rec.element(X)
-            nodal = rec.nodal(res["sigma"]) if vtk else None
-            for i, j in enumerate(cols):
-                e, q = divmod(int(res["von_mises_argmax"][i]), 4)
-                report["columns"].append({"column": j, "strain_energy": float(res["energy_total"][i]),
-                                          "von_mises_max": float(res["von_mises_max"][i]), "element": e, "gauss_point": q,
-                                          "position": [float(c) for c in shape4[q] @ points[cells[e]]],
-                                          "centroid": [float(c) for c in centroid[e]]})
-                if vtk:
-                    cd = {"von-mises-max": res["von_mises"][i].max(axis=1), "energy": res["energy"][i]}
-                    report["files"].append(rio.write_vtk_fields(p["stress_vtk_p2"].format(j=j), points, cells,
-                                                                _p2_point_data(X[i], nodal[i]), cd,
-                                                                title=f"stress, quadratic tetrahedra, saved column {j}"))
-        if history:
-            h = rec.history(traj)
-            arg = np.asarray(h["von_mises_argmax"], dtype=np.int64)
-            os.makedirs(os.path.dirname(p["stress_history_p2"]), exist_ok=True)
-            np.savez(p["stress_history_p2"], columns=np.arange(n_cols), strain_energy=h["energy_total"],
-                     von_mises_max=h["von_mises_max"], von_mises_element=arg // 4, von_mises_gauss_point=arg % 4)
-            report["history"] = p["stress_history_p2"]
-    finally:
-        rec.close()
-    return report
+    the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` of order 2 (default: the GPU)."""
+    return _whole_stress(mesh, out_dir, columns, 2, "linear", None, history, vtk, device, E, nu, recovery)
 
 
 def estimate_p2(mesh, out_dir=".", columns=(-1,), vtk=True, device=0, E=None, nu=None, recovery=None):
@@ -830,78 +886,8 @@ def estimate_p2(mesh, out_dir=".", columns=(-1,), vtk=True, device=0, E=None, nu
     the quadratic field ``sigma*`` of its recovered nodal values.  For every saved column in ``columns`` reports ``eta``,
     ``energy_norm``, ``relative`` and the element of the largest ``eta_e^2`` with its centroid, and writes
     ``Results/Stress/Estimate-order2-col-{j}.vtk`` (type-24 cells; point data as :func:`stress_p2`; cell data: the largest
-    Gauss-point von Mises, ``W_e`` and ``eta2``) unless ``vtk`` is False.  ``recovery``: see :func:`_device_recovery_p2`."""
-    from . import fem_setup as fs
-
-    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
-    make = _device_recovery_p2(device) if recovery is None else recovery
-    points, cells, traj, n_cols, cols = _load_p2_run(mesh, out_dir, columns)
-    ne, nn, m = len(cells), len(points), len(cols)
-    p = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
-    centroid = points[cells[:, :4]].mean(axis=1)
-
-    report = {"order": 2, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "columns": [], "files": []}
-    if not m:
-        return report
-    rec = make(points, cells, lmd, mu)
-    try:
-        X = np.ascontiguousarray(traj[:, cols].T)
-        res = rec.element(X)
-        nodal = rec.nodal(res["sigma"])
-        zz = rec.error(res["sigma"], nodal=nodal)
-    finally:
-        rec.close()
-    for i, j in enumerate(cols):
-        eta2, w2 = float(zz["eta2_total"][i]), 2.0 * float(res["energy_total"][i])
-        e = int(zz["eta2_argmax"][i])
-        report["columns"].append({"column": j, "eta": float(np.sqrt(eta2)), "energy_norm": float(np.sqrt(w2)),
-                                  "relative": float(np.sqrt(eta2 / (w2 + eta2))) if w2 + eta2 > 0 else 0.0, "element": e,
-                                  "eta2_max": float(zz["eta2_max"][i]), "centroid": [float(c) for c in centroid[e]]})
-        if vtk:
-            cd = {"von-mises-max": res["von_mises"][i].max(axis=1), "energy": res["energy"][i], "eta2": zz["eta2"][i]}
-            report["files"].append(rio.write_vtk_fields(p["estimate_vtk_p2"].format(j=j), points, cells,
-                                                        _p2_point_data(X[i], nodal[i]), cd,
-                                                        title=f"stress error estimate, quadratic tetrahedra, saved column {j}"))
-    return report
-
-
-def _finite_setup(mesh, out_dir, columns, material, order, device, E, nu, recovery):
-    """What :func:`stress_finite` and :func:`estimate_finite` share: the material's name, the Lame constants, the recovery
-    factory of ``order``, the run of ``dynamics --order {order}`` and the output paths."""
-    from . import fem_setup as fs
-    from ._lib import material_id
-
-    if order not in (1, 2):
-        raise ValueError("order must be 1 or 2")
-    if material_id(material) == 0:
-        raise ValueError("stress_finite / estimate_finite are for svk and neo_hookean; the linear material has stress, "
-                         "stress_p2, estimate and estimate_p2")
-    material = str(material).replace("-", "_")
-    lmd, mu = fs.lame(DEFAULTS["E"] if E is None else E, DEFAULTS["nu"] if nu is None else nu)
-    make = recovery if recovery is not None else (_device_recovery_p2 if order == 2 else _device_recovery)(device)
-    run = _load_run(mesh, out_dir, columns, order)
-    paths = {k: os.path.join(out_dir, v) for k, v in PATHS.items()}
-    return material, lmd, mu, make, run, paths
-
-
-def _finite_column(res, i, j, order, points, cells, centroid, shape4):
-    """The report entry of column ``j`` (row ``i`` of ``res``): the keys of the linear driver of that order, then ``material``'s
-    companions ``measure``, ``n_inverted`` and ``min_det_f``."""
-    nq = 4 if order == 2 else 1
-    e, q = divmod(int(res["von_mises_argmax"][i]), nq)
-    entry = {"column": j, "strain_energy": float(res["energy_total"][i]), "von_mises_max": float(res["von_mises_max"][i]),
-             "element": e}
-    if order == 2:
-        entry.update({"gauss_point": q, "position": [float(c) for c in shape4[q] @ points[cells[e]]]})
-    entry.update({"centroid": [float(c) for c in centroid[e]], "measure": res["measure"],
-                  "n_inverted": int(res["n_inverted"][i]), "min_det_f": float(np.min(res["det_f"][i]))})
-    return entry
-
-
-def _finite_cell_data(res, i, ne):
-    """Cell data of one column: the largest point von Mises, ``W_e`` and the smallest ``det F`` of every element."""
-    return {"von-mises-max": np.asarray(res["von_mises"][i]).reshape(ne, -1).max(axis=1), "energy": res["energy"][i],
-            "det-f-min": np.asarray(res["det_f"][i]).reshape(ne, -1).min(axis=1)}
+    Gauss-point von Mises, ``W_e`` and ``eta2``) unless ``vtk`` is False.  ``recovery``: see :func:`_device_recovery`."""
+    return _whole_estimate(mesh, out_dir, columns, 2, "linear", vtk, device, E, nu, recovery)
 
 
 def stress_finite(mesh, out_dir=".", columns=(-1,), material="svk", measure="cauchy", order=1, history=False, vtk=True,
@@ -915,44 +901,9 @@ def stress_finite(mesh, out_dir=".", columns=(-1,), material="svk", measure="cau
     Mises; cell data: the largest point von Mises, ``W_e`` and the smallest ``det F``) unless ``vtk`` is False; ``history``
     writes every column's stored energy, von Mises maximum, inverted count and smallest ``det F`` to
     ``Results/Stress/history-{material}-order{order}.npz``.  There is no modelled finite-strain run.  Returns the report that
-    the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` and :func:`_device_recovery_p2` (default: the GPU)."""
-    from .Tools.Qudrature import Gauss_Legendre
-    from .Tools.Shape_function_Deriv import Shape_Function
-
-    material, lmd, mu, make, (points, cells, traj, n_cols, cols), p = _finite_setup(mesh, out_dir, columns, material, order,
-                                                                                     device, E, nu, recovery)
-    ne, nn, m, nq = len(cells), len(points), len(cols), 4 if order == 2 else 1
-    shape4 = np.array([Shape_Function(2, x) for x in Gauss_Legendre(2)[0]]) if order == 2 else None
-    centroid = points[cells[:, :4]].mean(axis=1)
-    names = dict(material=material, p=order)
-
-    report = {"order": order, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "material": material,
-              "measure": str(measure), "columns": [], "files": [], "history": None}
-    rec = make(points, cells, lmd, mu)
-    try:
-        if m:
-            X = np.ascontiguousarray(traj[:, cols].T)
-            res = rec.element(X, material=material, measure=measure)
-            nodal = rec.nodal(res["sigma"]) if vtk else None
-            for i, j in enumerate(cols):
-                report["columns"].append({**_finite_column(res, i, j, order, points, cells, centroid, shape4),
-                                          "material": material})
-                if vtk:
-                    report["files"].append(rio.write_vtk_fields(p["stress_vtk_fs"].format(j=j, **names), points, cells,
-                                                                _p2_point_data(X[i], nodal[i]), _finite_cell_data(res, i, ne),
-                                                                title=f"{measure} stress, {material}, order {order}, saved column {j}"))
-        if history:
-            h = rec.history(traj, material=material, measure=measure)
-            arg = np.asarray(h["von_mises_argmax"], dtype=np.int64)
-            path = p["stress_history_fs"].format(**names)
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-            np.savez(path, columns=np.arange(n_cols), strain_energy=h["energy_total"], von_mises_max=h["von_mises_max"],
-                     von_mises_element=arg // nq, von_mises_gauss_point=arg % nq, n_inverted=h["n_inverted"],
-                     min_det_f=h["min_det_f"])
-            report["history"] = path
-    finally:
-        rec.close()
-    return report
+    the CLI prints as JSON.  ``recovery``: see :func:`_device_recovery` of that order (default: the GPU)."""
+    return _whole_stress(mesh, out_dir, columns, order, _finite_material(material, order), measure, history, vtk, device, E,
+                         nu, recovery)
 
 
 def estimate_finite(mesh, out_dir=".", columns=(-1,), material="svk", order=1, vtk=True, device=0, E=None, nu=None,
@@ -965,37 +916,7 @@ def estimate_finite(mesh, out_dir=".", columns=(-1,), material="svk", order=1, v
     the element of the largest ``eta_e^2`` with its centroid, ``n_inverted`` and ``min_det_f``, and writes
     ``Results/Stress/Estimate-{material}-order{order}-col-{j}.vtk`` (point data as :func:`stress_finite`, of PK2; cell data:
     the largest point von Mises, ``W_e``, the smallest ``det F`` and ``eta2``) unless ``vtk`` is False."""
-    material, lmd, mu, make, (points, cells, traj, n_cols, cols), p = _finite_setup(mesh, out_dir, columns, material, order,
-                                                                                     device, E, nu, recovery)
-    ne, nn, m = len(cells), len(points), len(cols)
-    centroid = points[cells[:, :4]].mean(axis=1)
-
-    report = {"order": order, "n_elems": ne, "n_nodes": nn, "n_ranks": 1, "n_saved": n_cols, "material": material,
-              "measure": "pk2", "columns": [], "files": []}
-    if not m:
-        return report
-    rec = make(points, cells, lmd, mu)
-    try:
-        X = np.ascontiguousarray(traj[:, cols].T)
-        res = rec.element(X, material=material, measure="pk2")
-        nodal = rec.nodal(res["sigma"])
-        zz = rec.error(res["sigma"], nodal=nodal)
-    finally:
-        rec.close()
-    for i, j in enumerate(cols):
-        eta2, w2 = float(zz["eta2_total"][i]), 2.0 * float(res["energy_total"][i])
-        e = int(zz["eta2_argmax"][i])
-        report["columns"].append({"column": j, "eta": float(np.sqrt(eta2)), "energy_norm": float(np.sqrt(w2)),
-                                  "relative": float(np.sqrt(eta2 / (w2 + eta2))) if w2 + eta2 > 0 else 0.0, "element": e,
-                                  "eta2_max": float(zz["eta2_max"][i]), "centroid": [float(c) for c in centroid[e]],
-                                  "material": material, "measure": "pk2", "n_inverted": int(res["n_inverted"][i]),
-                                  "min_det_f": float(np.min(res["det_f"][i]))})
-        if vtk:
-            cd = {**_finite_cell_data(res, i, ne), "eta2": zz["eta2"][i]}
-            report["files"].append(rio.write_vtk_fields(p["estimate_vtk_fs"].format(j=j, material=material, p=order), points,
-                                                        cells, _p2_point_data(X[i], nodal[i]), cd,
-                                                        title=f"stress error estimate, {material}, order {order}, saved column {j}"))
-    return report
+    return _whole_estimate(mesh, out_dir, columns, order, _finite_material(material, order), vtk, device, E, nu, recovery)
 
 
 def _has_gpu():
@@ -1115,27 +1036,18 @@ def main(argv=None):
                                     material=args.material, dt_check_every=args.dt_check_every, dt_follow=args.dt_follow,
                                     dt_follow_every=args.dt_follow_every)
             print(json.dumps({**report, "path": path}))
-        elif args.command == "estimate":
-            cols = [int(c) for c in args.columns.split(",") if c.strip()]
+        else:  # stress, estimate: the driver of (material, order); only stress has a history and a choice of measure
+            only_stress = args.command == "stress"
+            kw = {"vtk": not args.no_vtk, "device": local, **({"history": args.history} if only_stress else {})}
             if args.material != "linear":
-                print(json.dumps(estimate_finite(mesh, args.out, cols, material=args.material, order=args.order,
-                                                 vtk=not args.no_vtk, device=local)))
-                return
-            if args.order == 2:
-                print(json.dumps(estimate_p2(mesh, args.out, cols, vtk=not args.no_vtk, device=local)))
-                return
-            print(json.dumps(estimate(mesh, args.out, cols, modeled=args.modeled, vtk=not args.no_vtk, device=local)))
-        else:
-            cols = [int(c) for c in args.columns.split(",") if c.strip()]
-            if args.material != "linear":
-                print(json.dumps(stress_finite(mesh, args.out, cols, material=args.material, measure=args.measure,
-                                               order=args.order, history=args.history, vtk=not args.no_vtk, device=local)))
-                return
-            if args.order == 2:
-                print(json.dumps(stress_p2(mesh, args.out, cols, history=args.history, vtk=not args.no_vtk, device=local)))
-                return
-            print(json.dumps(stress(mesh, args.out, cols, modeled=args.modeled, history=args.history, vtk=not args.no_vtk,
-                                    device=local)))
+                driver = stress_finite if only_stress else estimate_finite
+                kw.update({"material": args.material, "order": args.order, **({"measure": args.measure} if only_stress else {})})
+            elif args.order == 2:
+                driver = stress_p2 if only_stress else estimate_p2
+            else:
+                driver = stress if only_stress else estimate
+                kw["modeled"] = args.modeled
+            print(json.dumps(driver(mesh, args.out, [int(c) for c in args.columns.split(",") if c.strip()], **kw)))
         return
     if args.command == "data_prepare":
         path, _ = data_prepare(_load_mesh(args), args.steps, args.save_every, args.out, rank, world,

@@ -252,7 +252,7 @@ def test_cli_refuses_modeled_and_linear_changes_nothing(tmp_path, monkeypatch, c
         with pytest.raises(SystemExit):
             drivers.main([command, "--synthetic", "1", "--material", "svk", "--modeled"])
         assert "no modelled finite-strain run" in capsys.readouterr().err
-    monkeypatch.setattr(drivers, "_device_recovery_p2", lambda device=0: sd.standin(2))
+    monkeypatch.setattr(drivers, "_device_recovery", lambda device=0, order=1: sd.standin(order))
     monkeypatch.setattr(drivers, "_dist_env", lambda: (0, 1, 0))
     q = to_quadratic(structured_beam(1))
     u = 1e-3 * fd.smooth_random_field(q.points, 3)
