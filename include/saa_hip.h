@@ -645,6 +645,23 @@ int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev
  *   contributions scratch and the node sum of the force; H(u) is recomputed on every call and nothing is stored per point.
  *   No floating-point atomics: bitwise repeatable.  SAA_E_ARG, before the handle or the device is looked at: a material
  *   outside {0, 1, 2}; then a null handle, null v_dev or kv_dev, null u_dev with a nonlinear material.
+ * saa_operator_tangent_apply_block: the same operator on 1 <= m <= 16 column-major columns of 3*n_nodes dofs in one call
+ *   (csrc/saa_optan_block.hip): column j of kv_dev (leading dimension ldkv) = K_T(u_dev) applied to column j of v_dev
+ *   (leading dimension ldv), both leading dimensions >= 3*n_nodes as for saa_operator_apply.  Every column is defined exactly
+ *   as above - the same point law, H and dH, weights, sign and masks - and does not depend on m, on the other columns of the
+ *   call or on its place among them; it is a different kernel from the one-column entry, so the two agree to round-off, not
+ *   bit for bit.  What does not depend on the column is done once per call: at order 1 the element's gradients, H(u) and the
+ *   state of the point law are formed once per element and the columns loop inside the lane; at order 2 (the one-column pass
+ *   already fills the register file) the column is the second grid index and each recomputes its element's state, so there
+ *   the call saves launches and shares the one node sum over all columns.  Nothing is stored per point between calls.  The
+ *   element pass writes m columns of the contributions scratch, which the node sum of saa_operator_apply adds up; no
+ *   floating-point atomics, bitwise repeatable.  SAA_MATERIAL_LINEAR runs the K kernels of saa_operator_apply on the m
+ *   columns (bit-equal to it); u_dev may then be NULL.  Inversion as above, for all columns at once: the element contributes
+ *   0 to every column and is counted once per call, not once per column.  n_inverted (host, or NULL) = that count; asking for
+ *   it synchronises the stream, otherwise the call is enqueued.  SAA_E_ARG, before the handle or the device is looked at: a
+ *   material outside {0, 1, 2}, m outside 1..16, a negative ldv or ldkv; then a null handle, null v_dev or kv_dev, null u_dev
+ *   with a nonlinear material, a leading dimension below 3*n_nodes.  Its user is modal.prestressed_modes, the natural
+ *   frequencies of a loaded structure about its equilibrium, K_T(u*) x = omega^2 M x (drivers modal --material).
  * saa_operator_stepper_inverted: count = the number of (element, step) inversion events since the counters were cleared,
  *   first_step = the lowest step index (the recorder's, saa_operator_stepper_set_recorder) at which one occurred, -1 when
  *   none did.  set_material and set_state clear them.  Synchronises the stream.  Either output may be NULL.
@@ -656,6 +673,9 @@ int saa_operator_internal_force(saa_operator *op, int32_t material, const double
                                 double *energy_elem_dev /* n_elems or NULL */, int64_t *n_inverted /* or NULL */);
 int saa_operator_tangent_apply(saa_operator *op, int32_t material, const double *u_dev, const double *v_dev,
                                double *kv_dev, int64_t *n_inverted /* host, or NULL */);
+int saa_operator_tangent_apply_block(saa_operator *op, int32_t material, const double *u_dev /* NULL allowed with LINEAR */,
+                                     int32_t m, const double *v_dev, int64_t ldv, double *kv_dev, int64_t ldkv,
+                                     int64_t *n_inverted /* host, or NULL */);
 int saa_operator_stepper_set_material(saa_operator_stepper *st, int32_t material);
 int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int64_t *first_step /* -1: none */);
 

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SAA_LIB_PATH") or os.path.join(_HERE, "libsaa_hip.so"
 DIAG_LIB_PATH = os.path.join(_HERE, "libsaa_hip_diag.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "saa_hip.h")
 SOURCES = ["saa_plan.cpp", "saa_partition.cpp", "saa_kernels.hip", "saa_setup.hip", "saa_predictor.hip", "saa_topology.hip", "saa_modal.hip",
-           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_opdt.hip", "saa_stress_fs.hip",
+           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_optan_block.hip", "saa_opdt.hip", "saa_stress_fs.hip",
            "saa_api.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-ldl"]
 
@@ -180,6 +180,8 @@ SIGNATURES = {
     "saa_operator_stepper_set_energy": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),
     "saa_operator_internal_force": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "saa_operator_tangent_apply": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "saa_operator_tangent_apply_block": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                   C.c_int64, C.POINTER(C.c_int64)]),
     "saa_operator_stress_finite": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),

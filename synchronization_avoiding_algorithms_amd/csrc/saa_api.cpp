@@ -2263,6 +2263,26 @@ int saa_operator_tangent_apply(saa_operator *op, int32_t material, const double 
   return SAA_OK;
 }
 
+int saa_operator_tangent_apply_block(saa_operator *op, int32_t material, const double *u_dev, int32_t m, const double *v_dev,
+                                     int64_t ldv, double *kv_dev, int64_t ldkv, int64_t *n_inverted) {
+  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+  if (m < 1 || m > saa::kModalMaxColumns)
+    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+  if (ldv < 0 || ldkv < 0) return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: negative leading dimension");
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: null handle");
+  if (!v_dev || !kv_dev) return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: null v_dev or kv_dev");
+  if (!u_dev && material != SAA_MATERIAL_LINEAR)
+    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: null u_dev with a nonlinear material");
+  const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
+  if (ldv < n_dof || ldkv < n_dof)
+    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: leading dimension below 3 * n_nodes");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_tangent_apply_block(op->impl, material, u_dev, m, v_dev, ldv, kv_dev, ldkv, n_inverted);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_tangent_apply_block: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
 struct saa_operator_stepper {
   saa::OpStepper *impl = nullptr;
 };

@@ -343,6 +343,28 @@ hipError_t operator_tangent_apply(ModalOp *op, int material, const double *u, co
   return hipSuccess;
 }
 
+hipError_t operator_tangent_apply_block(ModalOp *op, int material, const double *u, int32_t m, const double *v, int64_t ldv,
+                                        double *kv, int64_t ldkv, int64_t *n_inverted) {
+  if (material == 0) {
+    SAA_HIP_TRY(op->order == 2 ? p2_apply(op, m, v, ldv, kv, nullptr, ldkv) : modal_apply(op, m, v, ldv, kv, nullptr, ldkv));
+    if (n_inverted) {
+      SAA_HIP_TRY(hipStreamSynchronize(op->stream));
+      *n_inverted = 0;
+    }
+    return hipSuccess;
+  }
+  double *contrib = nullptr;
+  SAA_HIP_TRY(operator_scratch(op, m, &contrib));
+  SAA_HIP_TRY(operator_geometry(op));
+  SAA_HIP_TRY(alloc_counters(&op->fs_count, op->stream));
+  SAA_HIP_TRY(reset_counters(op->fs_count, op->stream));
+  const int64_t stride = (op->order == 2 ? 30 : 12) * static_cast<int64_t>(op->n_elems);
+  SAA_HIP_TRY(optan_block_element_pass(op, material, u, m, v, ldv, contrib, stride, op->fs_count));
+  SAA_HIP_TRY(modal_node_sum(op, m, contrib, stride, kv, ldkv));
+  if (n_inverted) SAA_HIP_TRY(read_counters(op, op->fs_count, n_inverted, nullptr));
+  return hipSuccess;
+}
+
 int opstep_material(const OpStepper *st) { return st->material; }
 
 hipError_t opstep_set_material(OpStepper *st, int material) {

@@ -89,6 +89,11 @@ hipError_t operator_internal_force(ModalOp *op, int material, const double *x, d
 // element pass of saa_optan.hip and modal_node_sum.  material 0: operator_internal_force of v (u is not looked at).
 // n_inverted as above.
 hipError_t operator_tangent_apply(ModalOp *op, int material, const double *u, const double *v, double *kv, int64_t *n_inverted);
+// kv + j * ldkv = K_T(u) (v + j * ldv) for the m <= 16 columns of one call: the element pass of saa_optan_block.hip into m
+// columns of the contributions scratch and one modal_node_sum.  material 0: the K passes of saa_operator_apply on the m
+// columns (u is not looked at).  n_inverted as above, an element counted once whatever m.
+hipError_t operator_tangent_apply_block(ModalOp *op, int material, const double *u, int32_t m, const double *v, int64_t ldv,
+                                        double *kv, int64_t ldkv, int64_t *n_inverted);
 // The stepper's element pass becomes that of `material` (0: the linear pass the "stored_geometry" option selects); makes
 // the handle's geometry table and the stepper's two inversion counters on first need and clears the counters.
 hipError_t opstep_set_material(OpStepper *st, int material);

@@ -60,5 +60,9 @@ hipError_t operator_element_masses(ModalOp *op, double *out);
 // zeros and is counted in cnt (the two words of saa_opfs.hip) at step 0.  The handle's geometry table must exist.
 hipError_t optan_element_pass(ModalOp *op, int material, const double *u, const double *v, double *contrib,
                               unsigned long long *cnt);
+// saa_optan_block.hip: that pass for the m columns v + j * ldv into contrib + j * stride; an inverted element writes zeros
+// into every column and is counted once.
+hipError_t optan_block_element_pass(ModalOp *op, int material, const double *u, int32_t m, const double *v, int64_t ldv,
+                                    double *contrib, int64_t stride, unsigned long long *cnt);
 
 }  // namespace saa

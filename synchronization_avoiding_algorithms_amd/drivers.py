@@ -316,15 +316,34 @@ def online_predictor(mesh, n_steps=100000, save_every=1, out_dir=".", rank=0, wo
     return path, store, hist
 
 
-def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1):
+def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1, material="linear", fz=None, fx=0.0,
+          load_steps=1):
     """Stable time step and lowest ``k`` natural frequencies of the whole mesh, clamped on ``x = 0`` like the other
     drivers (``Data_prepare.py:127-136``), on one GPU (:func:`modal.modal_report`).  Does not change how any other
     driver picks ``dt``.  ``order=2``: the frequencies of the quadratic discretisation (:func:`modal.modal_report_p2`),
-    without the time-step figures of the explicit p = 1 solver."""
+    without the time-step figures of the explicit p = 1 solver.
+
+    ``material`` ``svk`` / ``neo_hookean``: the frequencies about the equilibrium under the body force ``(fx, -fz, -fz)``
+    (the Newton solve of ``steady_state --material`` in ``load_steps`` fractions, then ``K_T(u*) x = omega^2 M x``), next to
+    the unstressed ones of the same handle (:func:`modal.prestressed_report`); with ``linear``, whose modes do not depend on
+    the load, ``fz``, ``fx`` and ``load_steps`` are not looked at."""
     from .mesh import clamp_nodes
     from .modal import modal_report
 
     p = {name: DEFAULTS[name] if v is None else v for name, v in (("E", E), ("nu", nu), ("rho", rho), ("gamma", gamma))}
+    if str(material).replace("-", "_") != "linear":
+        from .mesh import plane_nodes
+        from .modal import prestressed_report
+
+        if order not in (1, 2):
+            raise ValueError("order must be 1 or 2")
+        fz = DEFAULTS["fz"] if fz is None else fz
+        p.pop("gamma")
+        if order == 2:
+            mesh = _quadratic(mesh)
+        return prestressed_report(mesh.points, mesh.tets10 if order == 2 else mesh.tets,
+                                  plane_nodes(mesh.points) if order == 2 else clamp_nodes(mesh), material,
+                                  load=(float(fx), -float(fz), -float(fz)), k=k, load_steps=load_steps, device=device, **p)
     if order == 2:
         from .mesh import plane_nodes
         from .modal import modal_report_p2
@@ -955,10 +974,13 @@ def main(argv=None):
                     help="stress --material svk / neo-hookean: the Cauchy or the second Piola-Kirchhoff stress (estimate "
                          "always uses pk2)")
     ap.add_argument("--fz", type=float, default=0.5,
-                    help="dynamics, steady_state --material: the amplitude of the load (0, -fz, -fz); at the default nothing "
-                         "is nonlinear")
+                    help="dynamics, steady_state --material, modal --material: the amplitude of the load (0, -fz, -fz); at the "
+                         "default nothing is nonlinear")
     ap.add_argument("--load-steps", type=int, default=1,
-                    help="steady_state --material svk / neo-hookean: apply the load in this many equal fractions")
+                    help="steady_state, modal --material svk / neo-hookean: apply the load in this many equal fractions")
+    ap.add_argument("--fx", type=float, default=0.0,
+                    help="modal --material svk / neo-hookean: the axial part of the load (fx, -fz, -fz); negative compresses "
+                         "the beam")
     ap.add_argument("--dt-check-every", type=int, default=0,
                     help="dynamics --material svk / neo-hookean: every so many steps measure 2/omega_max of the tangent at the "
                          "current state and report it against dt (dt_check); dt is not changed")
@@ -1012,6 +1034,11 @@ def main(argv=None):
             ap.error("dynamics --dt-follow --energy: the identity of the energy balance assumes one dt")
     if args.command == "steady_state" and args.load_steps < 1:
         ap.error("steady_state --load-steps must be >= 1")
+    if args.command == "modal" and args.load_steps < 1:
+        ap.error("modal --load-steps must be >= 1")
+    if args.command == "modal" and args.material == "linear" and args.fx != 0.0:
+        ap.error("modal --fx: the prestress is for --material svk or neo-hookean (a linear operator's modes do not depend on "
+                 "the load)")
     if args.command in ("stress", "estimate") and args.material != "linear" and args.modeled:
         ap.error(f"{args.command} --material {args.material} --modeled: there is no modelled finite-strain run (the predictor "
                  "drives the linear material)")
@@ -1028,7 +1055,9 @@ def main(argv=None):
         mesh = (delaunay_beam(args.synthetic) if args.delaunay else structured_beam(args.synthetic)) if args.synthetic \
             else read_vtk(args.mesh)
         if args.command == "modal":
-            print(json.dumps(modal(mesh, k=args.k, device=local, order=args.order)))
+            extra = {} if args.material == "linear" else {"material": args.material, "fz": args.fz, "fx": args.fx,
+                                                          "load_steps": args.load_steps}
+            print(json.dumps(modal(mesh, k=args.k, device=local, order=args.order, **extra)))
         elif args.command == "dynamics":
             path, report = dynamics(mesh, args.steps, args.save_every, args.out, device=local, order=args.order,
                                     parts=args.parts, partition=args.partition,

@@ -232,6 +232,38 @@ class ModalOperator:
                                                         C.byref(n_inv) if count else None))
         return (kv, int(n_inv.value)) if count else kv
 
+    def tangent_apply_block(self, u, V, material="svk", count=False):
+        """``K_T(u) v`` for every row ``v`` of the ``(m, n_dof)`` float64 CUDA block ``V`` (or one ``(n_dof,)`` vector), in as
+        many ``saa_operator_tangent_apply_block`` calls of at most 16 columns as it takes: what does not depend on the column
+        is done once per call.  A row's result does not depend on the rows next to it.  ``linear`` is ``apply(V)[0]`` bit for
+        bit and ``u`` may then be None.  ``count=True``: returns ``(KV, n_inverted)`` - the number of elements that neo-Hooke
+        found inverted at ``u`` (the same in every call; elements, not elements times columns) - and synchronises."""
+        import torch
+
+        mat = _lib.material_id(material)
+        if not (torch.is_tensor(V) and V.is_cuda and V.dtype == torch.float64 and V.dim() in (1, 2)):
+            raise ValueError("V must be a float64 CUDA tensor, (m, n_dof) or (n_dof,)")
+        vec = V.dim() == 1
+        X = (V.reshape(1, -1) if vec else V).contiguous()
+        if X.shape[1] != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} dofs per vector, got {X.shape[1]}")
+        if u is None:
+            if mat != 0:
+                raise ValueError("a nonlinear material needs the state at which its tangent is taken")
+        elif not (torch.is_tensor(u) and u.is_cuda and u.dtype == torch.float64 and u.numel() == self.n_dof):
+            raise ValueError(f"u must be a float64 CUDA tensor of {self.n_dof} values")
+        u = u.reshape(-1).contiguous() if u is not None else None
+        KX = torch.empty_like(X)
+        n_inv, worst = C.c_int64(0), 0
+        for j in range(0, X.shape[0], self.MAX_COLUMNS):
+            c = min(self.MAX_COLUMNS, X.shape[0] - j)
+            _lib.check(self._lib.saa_operator_tangent_apply_block(
+                self._h, mat, C.c_void_p(u.data_ptr()) if u is not None else None, c, C.c_void_p(X[j].data_ptr()), self.n_dof,
+                C.c_void_p(KX[j].data_ptr()), self.n_dof, C.byref(n_inv) if count else None))
+            worst = max(worst, int(n_inv.value))
+        KX = KX.reshape(-1) if vec else KX
+        return (KX, worst) if count else KX
+
     def element_bound(self, return_omega=False) -> dict:
         """``omega_max`` bound ``max_e omega_e``, its element, the count of elements with signed volume <= 0 and
         whether the bound is certified (that count is 0); ``omega_e`` (a CUDA tensor) on request."""
@@ -326,10 +358,14 @@ def lanczos_max(apply_k, inv_sqrt_mass, max_iter=300, tol=1e-10, check_every=10,
     return math.sqrt(max(theta, 0.0)), res, it
 
 
-def _block_pcg(apply_k, B, X, dinv, rtol, max_iter, check_every=10):
+def _block_pcg(apply_k, B, X, dinv, rtol, max_iter, check_every=10, curvature=None):
     """Independent Jacobi-PCG solves ``K x_i = b_i`` for the rows of ``B``, batched through the block apply, starting
     from ``X`` (updated in place).  A row stops once its residual fell by ``rtol`` from its start (or to 1e-15 |b_i|).
-    Returns the number of iterations."""
+    Returns the number of iterations.
+
+    ``curvature`` (a dict, for an operator that may be indefinite): the first direction of each active row with ``p . K p
+    <= 0`` is kept on the device (``curvature["found"]`` per row, ``["p"]``, ``["pkp"]``); the host looks at the checks it
+    already makes and the loop ends there once any row has one."""
     import torch
 
     R = B - apply_k(X)
@@ -341,10 +377,17 @@ def _block_pcg(apply_k, B, X, dinv, rtol, max_iter, check_every=10):
     Z = dinv * R
     P = Z.clone()
     rz = (R * Z).sum(dim=1)
+    if curvature is not None:
+        curvature.update({"found": torch.zeros_like(active), "p": torch.zeros_like(P), "pkp": torch.zeros_like(rz)})
     it = 0
     while it < max_iter:
         AP = apply_k(P)
         pap = (P * AP).sum(dim=1)
+        if curvature is not None:
+            new = active & ~(pap > 0) & ~curvature["found"]
+            curvature["p"] = torch.where(new[:, None], P, curvature["p"])
+            curvature["pkp"] = torch.where(new, pap, curvature["pkp"])
+            curvature["found"] = curvature["found"] | new
         alpha = torch.where(active & (pap > 0), rz / torch.where(pap > 0, pap, 1.0), 0.0)
         X += alpha[:, None] * P
         R -= alpha[:, None] * AP
@@ -357,6 +400,8 @@ def _block_pcg(apply_k, B, X, dinv, rtol, max_iter, check_every=10):
         if it % check_every == 0:
             active = active & (torch.linalg.vector_norm(R, dim=1) > target)
             if not bool(active.any()):
+                break
+            if curvature is not None and bool(curvature["found"].any()):
                 break
     return it
 
@@ -384,7 +429,7 @@ def _rayleigh_ritz(Y, KY, MY):
 
 
 def lowest_modes(apply_k, apply_m, k, free, diag_k=None, block=None, tol=1e-8, max_outer=60, inner_rtol=1e-3,
-                 max_inner=20000, seed=0):
+                 max_inner=20000, seed=0, indefinite=False):
     """The ``k`` lowest eigenpairs of ``K x = omega^2 M x`` on the free dofs (``free``: ``(n,)`` tensor, 1 on free dofs,
     0 on Dirichlet dofs; ``apply_k`` / ``apply_m``: ``(m, n) -> (m, n)`` block applies that return 0 on Dirichlet dofs).
 
@@ -398,8 +443,33 @@ def lowest_modes(apply_k, apply_m, k, free, diag_k=None, block=None, tol=1e-8, m
     ``|K x - omega^2 M x| / (omega^2 |M x|)`` per mode (computed, not estimated), ``vectors`` ``(k, n)``,
     ``outer_iterations``, ``inner_iterations`` and ``converged`` (every residual <= ``tol``).  The iteration also ends
 when three sweeps in a row fail to halve the largest residual: on fine meshes round-off in ``K x`` bounds the residual
-from below by about ``eps omega_max^2 / omega_i^2``, and ``converged`` then stays False."""
+from below by about ``eps omega_max^2 / omega_i^2``, and ``converged`` then stays False.
+
+    ``indefinite=True`` is for a ``K`` that need not be positive definite (a tangent at a loaded state,
+    :func:`prestressed_modes`).  Every Rayleigh quotient ``x . K x / x . M x`` bounds the lowest eigenvalue from above, so a
+    non-positive one proves that there is a non-positive eigenvalue, and shift-invert at 0 has nothing to converge to.  The
+    same iteration then stops at the first proof - a Ritz value ``<= 0`` after a Rayleigh-Ritz step, or an active column of
+    the inner PCG with ``p . K p <= 0`` (tested on the device, read at the checks the PCG makes anyway) - and the dict also
+    holds ``stable`` (no proof was met) and ``lowest_ritz`` (stable: the lowest Ritz value; else the most negative Rayleigh
+    quotient formed, finite and ``<= 0``).  An unstable result has ``converged`` False and None for ``omega2``,
+    ``frequencies_hz``, ``residuals`` and ``vectors``: it claims no frequencies."""
     import torch
+
+    def unstable(lowest):
+        return {"omega2": None, "frequencies_hz": None, "residuals": None, "vectors": None, "outer_iterations": outer,
+                "inner_iterations": inner, "converged": False, "stable": False, "lowest_ritz": float(lowest)}
+
+    def inner_solve(Y):
+        """The inner PCG; with ``indefinite`` also the lowest Rayleigh quotient of a direction without curvature, or None."""
+        if not indefinite:
+            return _block_pcg(apply_k, MQ, Y, dinv, inner_rtol, max_inner), None
+        seen = {}
+        its = _block_pcg(apply_k, MQ, Y, dinv, inner_rtol, max_inner, curvature=seen)
+        if not seen or not bool(seen["found"].any()):
+            return its, None
+        pmp = (seen["p"] * apply_m(seen["p"])).sum(dim=1)
+        rq = torch.where(seen["found"] & (pmp > 0), seen["pkp"] / torch.where(pmp > 0, pmp, 1.0), 0.0)
+        return its, float(rq.min())
 
     n = free.numel()
     n_free = int((free != 0).sum())
@@ -410,11 +480,18 @@ from below by about ``eps omega_max^2 / omega_i^2``, and ``converged`` then stay
     Y = (torch.rand((p, n), generator=g, dtype=torch.float64) - 0.5).to(free.device) * free
     theta, Q, KQ, MQ = _rayleigh_ritz(Y, apply_k(Y), apply_m(Y))
     inner, outer, res, best, stalled = 0, 0, None, np.inf, 0
+    if indefinite and not float(np.min(theta)) > 0.0:
+        return unstable(np.min(theta))
     for outer in range(1, max_outer + 1):
         th = torch.as_tensor(theta, dtype=torch.float64, device=free.device)
         Y = Q / th.clamp_min(1e-300)[:, None]
-        inner += _block_pcg(apply_k, MQ, Y, dinv, inner_rtol, max_inner)
+        its, flat = inner_solve(Y)
+        inner += its
+        if flat is not None:
+            return unstable(flat)
         theta, Q, KQ, MQ = _rayleigh_ritz(Y, apply_k(Y), apply_m(Y))
+        if indefinite and not float(np.min(theta)) > 0.0:
+            return unstable(np.min(theta))
         th = torch.as_tensor(theta[:k], dtype=torch.float64, device=free.device)
         R = KQ[:k] - th[:, None] * MQ[:k]
         res = (torch.linalg.vector_norm(R, dim=1) / (th.abs() * torch.linalg.vector_norm(MQ[:k], dim=1))).cpu().numpy()
@@ -426,8 +503,11 @@ from below by about ``eps omega_max^2 / omega_i^2``, and ``converged`` then stay
         if stalled >= 3:
             break
     omega2 = np.asarray(theta[:k], dtype=np.float64)
-    return {"omega2": omega2, "frequencies_hz": np.sqrt(np.maximum(omega2, 0.0)) / (2.0 * np.pi), "residuals": res,
-            "vectors": Q[:k], "outer_iterations": outer, "inner_iterations": inner, "converged": bool((res <= tol).all())}
+    out = {"omega2": omega2, "frequencies_hz": np.sqrt(np.maximum(omega2, 0.0)) / (2.0 * np.pi), "residuals": res,
+           "vectors": Q[:k], "outer_iterations": outer, "inner_iterations": inner, "converged": bool((res <= tol).all())}
+    if indefinite:
+        out.update({"stable": True, "lowest_ritz": float(np.min(theta))})
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -573,4 +653,93 @@ def modal_report(points, cells, dirichlet_nodes, E=1e6, nu=0.3, rho=1.0, gamma=0
                     "modes_converged": modes["converged"], "outer_iterations": modes["outer_iterations"],
                     "inner_iterations": modes["inner_iterations"]})
     out["seconds"] = {"operator_create": t1 - t0, **dt["seconds"], "time_step_total": t2 - t1, "lowest_modes": t3 - t2}
+    return out
+
+
+def prestressed_modes(op: ModalOperator, u, material, k, tol=1e-8, **kw):
+    """The ``k`` lowest pairs of ``K_T(u) x = omega^2 M x`` on the GPU operator: the natural frequencies of the structure
+    about the state ``u`` (an ``(n_dof,)`` displacement, NumPy or a float64 CUDA tensor; an equilibrium of ``material``, e.g.
+    of :func:`steady.newton_solve_operator`).  Tension stiffens, compression softens, and the lowest ``omega^2`` reaches 0 at
+    the buckling load.  ``K_T`` is the block tangent (:meth:`ModalOperator.tangent_apply_block`), ``M`` the handle's consistent
+    mass, the Jacobi preconditioner ``diag K`` of the linear operator, as the Newton solve uses it; the iteration is
+    :func:`lowest_modes` with ``indefinite=True``, to which ``kw`` goes.
+
+    Returns what :func:`lowest_modes` returns, plus ``stable``, ``lowest_ritz``, ``n_inverted`` (elements neo-Hooke dropped
+    from the tangent at ``u``) and ``material``.  At a state that is not a stable equilibrium - a non-positive Rayleigh
+    quotient was met - it returns ``stable = False`` with ``lowest_ritz <= 0``, ``converged = False`` and no frequencies
+    (``frequencies_hz`` is None), and does not raise."""
+    import torch
+
+    mat = _lib.material_id(material)
+    if u is None:
+        if mat != 0:
+            raise ValueError("a nonlinear material needs the state at which its tangent is taken")
+    else:
+        u = u if torch.is_tensor(u) else torch.as_tensor(np.asarray(u, dtype=np.float64))
+        u = (u.to(device=op.torch_device, dtype=torch.float64).reshape(-1) * op.free).contiguous()
+    n_inverted = op.tangent_apply_block(u, torch.zeros((1, op.n_dof), dtype=torch.float64, device=op.torch_device), material,
+                                        count=True)[1]
+    diag = op.diagonal(k=True, m=False)[0]
+    out = lowest_modes(lambda X: op.tangent_apply_block(u, X, material), lambda X: op.apply(X, k=False, m=True)[1], k, op.free,
+                       diag_k=diag * op.free, tol=tol, indefinite=True, **kw)
+    out.update({"n_inverted": int(n_inverted), "material": str(material).replace("-", "_")})
+    return out
+
+
+def prestressed_report(points, cells, dirichlet_nodes, material, load=(0.0, 0.0, 0.0), k=6, load_steps=1, E=1e6, nu=0.3,
+                       rho=1.0, device=0, tol=1e-8) -> dict:
+    """What ``drivers modal --material svk / neo-hookean`` prints: the natural frequencies of the mesh (either order, by the
+    width of ``cells``) about its equilibrium under the body force ``load = (fx, fy, fz)``, next to those of the unloaded
+    structure on the same handle.  :func:`steady.newton_solve_operator` to ``u*`` (``tol`` in the true residual, the load in
+    ``load_steps`` fractions), :func:`prestressed_modes` at ``u*``, :func:`device_lowest_modes` for the unstressed pair.
+
+    The dict: ``order``, the sizes, ``material``, ``load``; ``newton`` (``converged``, ``residual``, ``newton_iterations``,
+    ``cg_iterations``, ``load_steps``, ``n_inverted``, ``tip_deflection`` - the mean of ``-u_y`` over the vertices of ``x = max`` -
+    and ``min_det_f``); ``stable``, ``lowest_ritz``, ``frequencies_hz``, ``residuals``, ``modes_converged``;
+    ``frequencies_hz_unstressed``; ``omega2_ratio`` (prestressed over unstressed, per mode); the iteration counts of both
+    eigen-iterations and ``seconds``.  If Newton does not converge the report says so and holds no modes; at an unstable
+    equilibrium it holds ``stable = False``, ``lowest_ritz`` and no prestressed frequencies."""
+    import torch
+
+    from . import fem_setup as fs
+    from .steady import newton_solve_operator
+    from .stress import QuadraticStressRecovery, StressRecovery
+
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    cells = np.ascontiguousarray(cells, dtype=np.int32)
+    if _lib.material_id(material) == 0:
+        raise ValueError("prestressed_report is for svk and neo_hookean: a linear operator's modes do not depend on the load")
+    lmd, mu = fs.lame(E, nu)
+    dirichlet = fs.node_to_dof(dirichlet_nodes)
+    n_vert = int(cells[:, :4].max()) + 1 if len(cells) else 0
+    tip = np.nonzero(np.abs(points[:n_vert, 0] - points[:, 0].max()) < 1e-9)[0]
+    t0 = time.perf_counter()
+    with ModalOperator(points, cells, dirichlet, lmd, mu, rho, device) as op:
+        t1 = _sync(op.torch_device)
+        u, info = newton_solve_operator(op, op.load(load), material, tol=tol, load_steps=load_steps)
+        d = torch.as_tensor(np.asarray(u, dtype=np.float64).reshape(-1), device=op.torch_device)
+        rec = (QuadraticStressRecovery if op.order == 2 else StressRecovery)(None, None, None, None, operator=op)
+        det_f = rec.element(d, energy=False, material=material, measure="cauchy")["det_f"]
+        out = {"order": op.order, "n_nodes": op.n_nodes, "n_elems": op.n_elems, "n_free_dofs": int(op.free.sum().item()),
+               "material": str(material).replace("-", "_"), "load": [float(c) for c in load],
+               "newton": {**{key: info[key] for key in ("converged", "residual", "newton_iterations", "cg_iterations",
+                                                         "load_steps", "n_inverted")},
+                          "tip_deflection": float(-np.asarray(u).reshape(-1, 3)[tip, 1].mean()),
+                          "min_det_f": float(det_f.min())}}
+        t2 = _sync(op.torch_device)
+        out["seconds"] = {"operator_create": t1 - t0, "newton": t2 - t1}
+        if not info["converged"]:
+            return out
+        modes = prestressed_modes(op, d, material, k)
+        t3 = _sync(op.torch_device)
+        rest = device_lowest_modes(op, points, cells, lmd, mu, k)
+        t4 = _sync(op.torch_device)
+    out.update({"stable": modes["stable"], "lowest_ritz": modes["lowest_ritz"], "n_inverted": modes["n_inverted"],
+                "frequencies_hz": modes["frequencies_hz"].tolist() if modes["stable"] else None,
+                "residuals": modes["residuals"].tolist() if modes["stable"] else None, "modes_converged": modes["converged"],
+                "frequencies_hz_unstressed": rest["frequencies_hz"].tolist(), "residuals_unstressed": rest["residuals"].tolist(),
+                "omega2_ratio": (modes["omega2"] / rest["omega2"]).tolist() if modes["stable"] else None,
+                "outer_iterations": modes["outer_iterations"], "inner_iterations": modes["inner_iterations"],
+                "outer_iterations_unstressed": rest["outer_iterations"], "inner_iterations_unstressed": rest["inner_iterations"]})
+    out["seconds"].update({"prestressed_modes": t3 - t2, "unstressed_modes": t4 - t3})
     return out
