@@ -86,7 +86,7 @@ typedef struct saa_plan_stats {
 } saa_plan_stats;
 
 const char *saa_last_error(void);
-/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration; so did the partition entry points of the operator stepper, saa_operator_stepper_set_shared, _set_interface_buffer, _step_begin, _step_finish, _step_predicted, _halo_gather and _halo_scatter, then saa_operator_stepper_set_energy, the finite-strain entry points and saa_operator_tangent_apply). */
+/* Library / ABI version; bumps when this header changes (2: peer exchange and resident-kernel entry points; 3: loop-back attach; 4: partitioner and set-up kernels; 5: deterministic mode; 6: copy-bandwidth aid; 7: saa_plan_stats grew; 8: saa_predictor_*, saa_topology_*; 9: saa_set_option, saa_plan_stats.n_renumbered; 10: saa_plan_host_check; 11: saa_operator_*; 12: saa_operator_stress, saa_operator_nodal_average; 13: saa_plan_host_block_maxima; 14: saa_operator_stress_error; 15: saa_operator_create_p2, saa_operator_order, saa_operator_load, saa_operator_diagonal; 16: saa_operator_lumped_mass, saa_operator_stepper_*; the p = 2 stress entry points saa_operator_stress_p2, saa_operator_nodal_stress_p2 and saa_operator_stress_error_p2 joined version 16 without a bump: they add symbols and change no declaration; so did the partition entry points of the operator stepper, saa_operator_stepper_set_shared, _set_interface_buffer, _step_begin, _step_finish, _step_predicted, _halo_gather and _halo_scatter, then saa_operator_stepper_set_energy, the finite-strain entry points and saa_operator_tangent_apply, then saa_operator_shifted_apply and saa_operator_implicit_*). */
 int32_t saa_abi_version(void);
 
 /* Element partition, one part per rank / GPU: the role of `_, epart = part_mesh_kway(size, eptr, eind)` (mgmetis /
@@ -731,6 +731,77 @@ int saa_operator_tangent_bound(saa_operator *op, int32_t material, const double 
                                double *omega_e_dev /* n_elems, or NULL */, double *omega_max, int32_t *argmax,
                                int64_t *counts /* host, 3 words, or NULL */);
 int saa_operator_stepper_set_dt(saa_operator_stepper *st, double dt_new);
+
+/*
+ * Implicit dynamics on the operator handle (csrc/saa_opimp.hip): an unconditionally stable time integrator next to the explicit
+ * stepper above, either element order, all three materials.  Newmark with beta = 1/4, gamma = 1/2 (the trapezoidal rule) on the
+ * system the explicit stepper integrates, with the diagonal mass m the caller passes (saa_operator_lumped_mass: HRZ at order 2),
+ * the un-ramped load f, scale(t) = ramp ? min(t, 1) : 1, and mass-proportional damping:
+ *     m a + alpha m v + f_int(d) = scale(t) f   on free dofs;   d = v = a = 0 on Dirichlet dofs and at nodes without elements
+ *     d1 = x,   v1 = 2/dt (x - d) - v,   a1 = 4/dt^2 (x - d - dt v) - a
+ *     r(x) = scale(t + dt) f - f_int(x) - m (a1(x) + alpha v1(x)),   J(x) = K_T(x) + s,   s = (4/dt^2 + 2 alpha/dt) m
+ * A step: the predictor x = d + dt v; full Newton steps x += dx with J dx = r solved by Jacobi-PCG from 0, preconditioner
+ * 1 / (diag K + s), diag K that of the linear operator (saa_operator_diagonal); the PCG runs to eta |r| with the forcing term of
+ * the static Newton, eta = min(0.1, 0.9 (|r_k| / |r_k-1|)^2), 0.1 on a step's first iteration, floored at 0.1 tol scale / |r_k| so
+ * that it never asks for more than the tolerance needs; it stops at the first p . J p <= 0 and hands back the iterate so far, or
+ * the preconditioned residual if it has none.  With SAA_MATERIAL_LINEAR the one system is solved to tol.  A step has converged
+ * when |r| <= tol max(|scale f|, |f_int(x)|, |m (a1 + alpha v1)|), 2-norms over the free dofs - the three terms of the balance,
+ * so that a run at rest or at steady state has a meaningful scale.  NOT provided: a line search, an automatic cut of dt,
+ * HHT-alpha, a consistent mass, partitions, an energy table.
+ * The loops run on the device.  The element passes are those of saa_operator_apply, saa_operator_internal_force and
+ * saa_operator_tangent_apply; the node passes, the PCG vector passes and the reductions are kernels of their own: block partials
+ * and a fixed-order final sum folded into the kernel that needs it, 4 launches per PCG iteration, no floating-point atomics -
+ * every result is bitwise repeatable and independent of how a run is split into calls.  The host reads one small status block
+ * (iteration count, |r|, guard flag, inversion count) once per Newton iteration and every check_every PCG iterations, and once at
+ * the end of the linear material's solve: that step is accepted on the recurrence residual of its PCG, because a residual
+ * evaluated afresh has the round-off floor of f_int (eps times the cancellation inside it), which a tight tol lies below.
+ *
+ * saa_operator_shifted_apply: out = K_T(u) v + shift (.) v, 0 on Dirichlet dofs; u, v are masked on input as
+ *   saa_operator_tangent_apply masks them, u_dev may be NULL with SAA_MATERIAL_LINEAR.  shift_dev: 3 * n_nodes device doubles, or
+ *   NULL - then out is bit-equal to saa_operator_tangent_apply (same element pass, same sum order).  dot_dev: a device double that
+ *   receives v . out over the free dofs, or NULL.  n_inverted (host, or NULL) as saa_operator_tangent_apply; reading it
+ *   synchronises the stream.  SAA_E_ARG, before the device is touched: a material outside {0, 1, 2}, a null handle, v_dev or
+ *   out_dev, null u_dev with a nonlinear material.
+ * saa_operator_implicit_create: borrows the handle, which must outlive the stepper (and serves one stepper at a time: the
+ *   contributions scratch is the handle's).  Copies mass and load (3 * n_nodes device doubles each); the state starts as
+ *   _set_state(NULL, NULL, 0) leaves it: d = v = 0, t = 0, a = scale(0) f / m.  Synchronises once: SAA_E_ARG when the mass is not > 0 at a node that has elements; also for dt or alpha not
+ *   finite, dt <= 0, alpha < 0, a material outside {0, 1, 2}, null pointers - those before the device is touched.
+ * _set_state: d, v (NULL = zeros) are copied with the mask applied, a = (scale(t) f - f_int(d) - alpha m v) / m.  Enqueued.
+ * _get_state: any output may be NULL; synchronises.
+ * _set_recorder: layout and rule of saa_operator_stepper_set_recorder - row-major (3 * n_nodes, n_cols), the d of step index i
+ *   goes to column i / save_every when i % save_every == 0 and the column exists; NULL switches it off.
+ * _set_option: "tol" (1e-10), "max_newton" (25), "max_cg" (20 * 3 * n_nodes, per solve), "check_every" (25).  SAA_E_ARG: unknown
+ *   name, tol outside (0, 1), a count that is not a whole number >= 1.
+ * _set_dt: stores dt and recomputes s and the preconditioner; the scheme is one-step, so the state needs no surgery.
+ * _step: up to nsteps steps.  A step is NOT accepted when max_newton Newton iterations did not converge it (reason 1), a
+ *   residual is not finite (2), or - neo-Hooke - a trial x has an inverted element, by the counter words of the force pass (3).
+ *   Then d, v, a, t and the step index stay those of the last accepted step, bit for bit, and the call returns SAA_OK with
+ *   converged = 0, the reason and the number of steps done.  newton_iterations and cg_iterations are totals of the call;
+ *   residual is the last |r| over its scale.  nsteps == 0 does nothing.  SAA_E_ARG: null handle or info, nsteps < 0.
+ */
+int saa_operator_shifted_apply(saa_operator *op, int32_t material, const double *u_dev /* NULL allowed with LINEAR */,
+                               const double *v_dev, const double *shift_dev /* or NULL */, double *out_dev,
+                               double *dot_dev /* device double, or NULL */, int64_t *n_inverted /* host, or NULL */);
+typedef struct saa_operator_implicit saa_operator_implicit;
+typedef struct saa_implicit_info {
+  int32_t steps_done;         /* accepted steps of this call */
+  int32_t converged;          /* 1: every requested step was accepted */
+  int32_t reason;             /* 0 ok, 1 max_newton reached, 2 residual not finite, 3 inverted element (neo-Hooke) */
+  int32_t reserved;
+  int64_t newton_iterations;  /* of this call */
+  int64_t cg_iterations;      /* of this call */
+  double residual;            /* the last |r| / max(|scale f|, |f_int|, |m (a1 + alpha v1)|) */
+} saa_implicit_info;
+int saa_operator_implicit_create(saa_operator *op, const double *mass_dev, const double *f_ext_dev, double dt, double alpha,
+                                 int32_t ramp, int32_t material, saa_operator_implicit **out);
+int saa_operator_implicit_set_state(saa_operator_implicit *st, const double *d_dev, const double *v_dev, double t);
+int saa_operator_implicit_get_state(saa_operator_implicit *st, double *d_dev, double *v_dev, double *a_dev, double *t);
+int saa_operator_implicit_set_recorder(saa_operator_implicit *st, double *traj_dev, int64_t n_cols, int32_t save_every,
+                                       int64_t next_step_index);
+int saa_operator_implicit_set_option(saa_operator_implicit *st, const char *name, double value);
+int saa_operator_implicit_set_dt(saa_operator_implicit *st, double dt);
+int saa_operator_implicit_step(saa_operator_implicit *st, int32_t nsteps, saa_implicit_info *info);
+int saa_operator_implicit_destroy(saa_operator_implicit *st);
 
 /*
  * Finite-strain stress recovery (csrc/saa_stress_fs.hip): what saa_operator_stress / saa_operator_stress_p2 are to the linear

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SAA_LIB_PATH") or os.path.join(_HERE, "libsaa_hip.so"
 DIAG_LIB_PATH = os.path.join(_HERE, "libsaa_hip_diag.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "saa_hip.h")
 SOURCES = ["saa_plan.cpp", "saa_partition.cpp", "saa_kernels.hip", "saa_setup.hip", "saa_predictor.hip", "saa_topology.hip", "saa_modal.hip",
-           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_optan_block.hip", "saa_opdt.hip", "saa_stress_fs.hip",
+           "saa_stress.hip", "saa_stress_p2.hip", "saa_p2.hip", "saa_opstep.hip", "saa_opfs.hip", "saa_optan.hip", "saa_optan_block.hip", "saa_opdt.hip", "saa_stress_fs.hip", "saa_opimp.hip",
            "saa_api.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-ldl"]
 
@@ -76,6 +76,12 @@ class PlanStats(C.Structure):
     def as_dict(self):
         return {name: (float if name.endswith("conflict_factor") else int)(getattr(self, name))
                 for name, _ in self._fields_ if name != "reserved"}
+
+
+class ImplicitInfo(C.Structure):
+    """``saa_implicit_info`` of include/saa_hip.h."""
+    _fields_ = [("steps_done", C.c_int32), ("converged", C.c_int32), ("reason", C.c_int32), ("reserved", C.c_int32),
+                ("newton_iterations", C.c_int64), ("cg_iterations", C.c_int64), ("residual", C.c_double)]
 
 
 _dp = C.POINTER(C.c_double)
@@ -189,6 +195,17 @@ SIGNATURES = {
     "saa_operator_stepper_inverted": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "saa_operator_tangent_bound": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, _dp, _ip, C.POINTER(C.c_int64)]),
     "saa_operator_stepper_set_dt": (C.c_int, [_H, C.c_double]),
+    "saa_operator_shifted_apply": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_int64)]),
+    "saa_operator_implicit_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                               C.POINTER(_H)]),
+    "saa_operator_implicit_set_state": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double]),
+    "saa_operator_implicit_get_state": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, _dp]),
+    "saa_operator_implicit_set_recorder": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]),
+    "saa_operator_implicit_set_option": (C.c_int, [_H, C.c_char_p, C.c_double]),
+    "saa_operator_implicit_set_dt": (C.c_int, [_H, C.c_double]),
+    "saa_operator_implicit_step": (C.c_int, [_H, C.c_int32, C.POINTER(ImplicitInfo)]),
+    "saa_operator_implicit_destroy": (C.c_int, [_H]),
 }
 
 _lib = None

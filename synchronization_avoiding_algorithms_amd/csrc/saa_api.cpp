@@ -19,6 +19,7 @@
 #include "../../include/saa_hip.h"
 #include "saa_device.h"
 #include "saa_modal.h"
+#include "saa_opimp.h"
 #include "saa_opstep.h"
 #include "saa_p2.h"
 #include "saa_partition.h"
@@ -2518,6 +2519,119 @@ int saa_operator_stepper_destroy(saa_operator_stepper *st) {
   if (!st) return SAA_OK;
   saa::opfs_release(st->impl);
   saa::opstep_destroy(st->impl);
+  delete st;
+  return SAA_OK;
+}
+
+// ---- implicit dynamics on the operator handle (saa_opimp.hip) ----------------------------------------------------
+int saa_operator_shifted_apply(saa_operator *op, int32_t material, const double *u_dev, const double *v_dev, const double *shift_dev,
+                               double *out_dev, double *dot_dev, int64_t *n_inverted) {
+  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, "saa_operator_shifted_apply: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_shifted_apply: null handle");
+  if (!v_dev || !out_dev) return fail(SAA_E_ARG, "saa_operator_shifted_apply: null v_dev or out_dev");
+  if (!u_dev && material != SAA_MATERIAL_LINEAR)
+    return fail(SAA_E_ARG, "saa_operator_shifted_apply: null u_dev with a nonlinear material");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  const hipError_t e = saa::operator_shifted_apply(op->impl, material, u_dev, v_dev, shift_dev, out_dev, dot_dev, n_inverted);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_shifted_apply: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+struct saa_operator_implicit {
+  saa::OpImplicit *impl = nullptr;
+};
+
+int saa_operator_implicit_create(saa_operator *op, const double *mass_dev, const double *f_ext_dev, double dt, double alpha,
+                                 int32_t ramp, int32_t material, saa_operator_implicit **out) {
+  if (!out) return fail(SAA_E_ARG, "saa_operator_implicit_create: null output");
+  *out = nullptr;
+  if (!(std::isfinite(dt) && dt > 0.0)) return fail(SAA_E_ARG, "saa_operator_implicit_create: dt must be finite and > 0");
+  if (!(std::isfinite(alpha) && alpha >= 0.0)) return fail(SAA_E_ARG, "saa_operator_implicit_create: alpha must be finite and >= 0");
+  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
+    return fail(SAA_E_ARG, "saa_operator_implicit_create: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_implicit_create: null handle");
+  if (!mass_dev || !f_ext_dev) return fail(SAA_E_ARG, "saa_operator_implicit_create: null mass_dev or f_ext_dev");
+  HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
+  saa_operator_implicit *st = new (std::nothrow) saa_operator_implicit;
+  if (!st) return fail(SAA_E_HIP, "saa_operator_implicit_create: out of host memory");
+  std::string err;
+  const hipError_t e = saa::opimp_create(op->impl, mass_dev, f_ext_dev, dt, alpha, ramp != 0, material, &st->impl, err);
+  if (e != hipSuccess) {
+    delete st;
+    (void)hipGetLastError();
+    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_implicit_create: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+  }
+  *out = st;
+  return SAA_OK;
+}
+
+int saa_operator_implicit_set_state(saa_operator_implicit *st, const double *d_dev, const double *v_dev, double t) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_set_state: null handle");
+  if (!std::isfinite(t)) return fail(SAA_E_ARG, "saa_operator_implicit_set_state: t must be finite");
+  HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
+  const hipError_t e = saa::opimp_set_state(st->impl, d_dev, v_dev, t);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_set_state: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_implicit_get_state(saa_operator_implicit *st, double *d_dev, double *v_dev, double *a_dev, double *t) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_get_state: null handle");
+  HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
+  const hipError_t e = saa::opimp_get_state(st->impl, d_dev, v_dev, a_dev, t);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_get_state: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_implicit_set_recorder(saa_operator_implicit *st, double *traj_dev, int64_t n_cols, int32_t save_every,
+                                       int64_t next_step_index) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_set_recorder: null handle");
+  if (traj_dev && (n_cols <= 0 || save_every <= 0 || next_step_index < 0))
+    return fail(SAA_E_ARG, "saa_operator_implicit_set_recorder: bad argument");
+  saa::opimp_set_recorder(st->impl, traj_dev, traj_dev ? n_cols : 0, traj_dev ? save_every : 1, traj_dev ? next_step_index : 0);
+  return SAA_OK;
+}
+
+int saa_operator_implicit_set_option(saa_operator_implicit *st, const char *name, double value) {
+  if (!st || !st->impl || !name) return fail(SAA_E_ARG, "saa_operator_implicit_set_option: null handle or name");
+  if (!saa::opimp_set_option(st->impl, name, value))
+    return fail(SAA_E_ARG, std::string("saa_operator_implicit_set_option: unknown option or value: ") + name +
+                               " (tol in (0, 1); max_newton, max_cg, check_every whole numbers >= 1)");
+  return SAA_OK;
+}
+
+int saa_operator_implicit_set_dt(saa_operator_implicit *st, double dt) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_set_dt: null handle");
+  if (!(std::isfinite(dt) && dt > 0.0)) return fail(SAA_E_ARG, "saa_operator_implicit_set_dt: dt must be finite and > 0");
+  HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
+  const hipError_t e = saa::opimp_set_dt(st->impl, dt);
+  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_set_dt: ") + hipGetErrorString(e));
+  return SAA_OK;
+}
+
+int saa_operator_implicit_step(saa_operator_implicit *st, int32_t nsteps, saa_implicit_info *info) {
+  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_step: null handle");
+  if (nsteps < 0) return fail(SAA_E_ARG, "saa_operator_implicit_step: nsteps < 0");
+  if (!info) return fail(SAA_E_ARG, "saa_operator_implicit_step: null info");
+  saa::OpImplicitInfo r;
+  if (nsteps > 0) {
+    HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
+    const hipError_t e = saa::opimp_step(st->impl, nsteps, &r);
+    if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_step: ") + hipGetErrorString(e));
+  }
+  info->steps_done = r.steps_done;
+  info->converged = r.converged;
+  info->reason = r.reason;
+  info->reserved = 0;
+  info->newton_iterations = r.newton_iterations;
+  info->cg_iterations = r.cg_iterations;
+  info->residual = r.residual;
+  return SAA_OK;
+}
+
+int saa_operator_implicit_destroy(saa_operator_implicit *st) {
+  if (!st) return SAA_OK;
+  saa::opimp_destroy(st->impl);
   delete st;
   return SAA_OK;
 }

@@ -272,7 +272,7 @@ void modal_destroy(ModalOp *op) {
   void *bufs[] = {op->xyz, op->tets, op->free_mask, op->offsets, op->pairs, op->scratch_k, op->scratch_m,
                   op->part_val, op->part_idx, op->part_cnt, op->res_val, op->res_int, op->abs_vol, op->node_wsum,
                   op->st_part_w, op->st_part_vm, op->st_part_idx, op->geom, op->bits, op->fs_count, op->st_inverted,
-                  op->dt_cnt};
+                  op->dt_cnt, op->imp_part};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   delete op;

@@ -43,6 +43,7 @@ struct ModalOp {
   unsigned long long *fs_count = nullptr;  // saa_operator_internal_force: the two counter words of the call (saa_opfs.hip)
   unsigned long long *st_inverted = nullptr;  // saa_operator_stress_finite: inverted elements per column (saa_stress_fs.hip)
   int32_t *dt_cnt = nullptr;  // saa_operator_tangent_bound: [workgroup][3] partial counts, then the three totals (saa_opdt.hip)
+  double *imp_part = nullptr;  // saa_operator_shifted_apply: per-workgroup partials of the dot product (saa_opimp.hip)
 };
 
 // The node pass of saa_modal.hip on any [column][pair][3] contributions of this handle's CSR: y[j][3v + c] = sum of node

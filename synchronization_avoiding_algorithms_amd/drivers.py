@@ -358,7 +358,7 @@ def modal(mesh, k=6, device=0, E=None, nu=None, rho=None, gamma=None, order=1, m
 
 def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1, E=None, nu=None, rho=None, fz=None,
              alpha=None, gamma=None, parts=0, partition="slab", energy_every=0, material="linear", dt_check_every=0,
-             dt_follow=None, dt_follow_every=10):
+             dt_follow=None, dt_follow_every=10, scheme="explicit", dt_factor=10.0, newton_tol=1e-10):
     """The explicit run of the whole mesh on one GPU through the operator handle (:func:`dynamics.run_dynamics`), for
     linear (``order=1``) or quadratic tetrahedra (``order=2``: the mesh is elevated like ``steady_state --order 2``),
     clamped on every node of ``x = 0``: lumped mass of the handle (HRZ for order 2), the reference load ``(0, -fz, -fz)``
@@ -378,17 +378,29 @@ def dynamics(mesh, n_steps=100000, save_every=1, out_dir=".", device=0, order=1,
     is checked before step 0 and after every ``dt_follow_every`` steps and changed by the rule of
     :meth:`dynamics.OperatorStepper.follow_time_step`; the report gains ``dt_follow`` and ``time_path``,
     ``Results/Dynamics/Time_order{p}.npz`` with ``t`` per saved column - the columns are no longer equidistant in time - and the
-    ``(step, dt)`` list of the run.  The HDF5 container is what it was."""
-    from .dynamics import run_dynamics
+    ``(step, dt)`` list of the run.  The HDF5 container is what it was.
+    ``scheme = "newmark"``: the same run with the implicit stepper (:func:`dynamics.run_dynamics_newmark`) at ``dt = dt_factor *
+    2/omega_max`` of the linear operator, Newton tolerance ``newton_tol``; same file and keys, plus ``scheme``, ``dt_factor``,
+    ``newton_iterations``, ``cg_iterations``, ``converged``, ``failed_step``.  Not with ``parts``, the energy balance, ``dt_follow`` or
+    ``dt_check_every`` (ValueError).  ``scheme = "explicit"`` is the run it always was."""
+    from .dynamics import run_dynamics, run_dynamics_newmark
     from .mesh import plane_nodes
 
     if order not in (1, 2):
         raise ValueError("order must be 1 or 2")
+    if scheme not in ("explicit", "newmark"):
+        raise ValueError("scheme must be explicit or newmark")
+    if scheme == "newmark" and ((parts and int(parts) > 0) or energy_every or dt_follow or dt_check_every):
+        raise ValueError("scheme newmark runs the whole mesh without parts, energy balance, dt_follow or dt_check_every")
     p = {name: DEFAULTS[name] if v is None else v
          for name, v in (("E", E), ("nu", nu), ("rho", rho), ("fz", fz), ("alpha", alpha), ("gamma", gamma))}
     if order == 2:
         mesh = _quadratic(mesh)
     cells = mesh.tets10 if order == 2 else mesh.tets
+    if scheme == "newmark":
+        store, report = run_dynamics_newmark(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device,
+                                             material=material, dt_factor=float(dt_factor), newton_tol=float(newton_tol), **p)
+        return rio.save_displacement(os.path.join(out_dir, PATHS["dynamics"].format(p=order)), store), report
     epart = make_partition(mesh, int(parts), partition) if parts and int(parts) > 0 else None
     store, report, *table = run_dynamics(mesh.points, cells, plane_nodes(mesh.points), n_steps, save_every, device=device,
                                          epart=epart, energy_every=int(energy_every or 0), material=material,
@@ -990,6 +1002,13 @@ def main(argv=None):
                          "change dt exactly.  certified: gamma * 2/bound (safe, pessimistic); anchored: the linear operator's "
                          "step scaled by bound(0)/bound(state) (a heuristic, never above today's dt)")
     ap.add_argument("--dt-follow-every", type=int, default=10, help="dynamics --dt-follow: every so many steps")
+    ap.add_argument("--scheme", choices=["explicit", "newmark"], default="explicit",
+                    help="dynamics: explicit central differences (dt = gamma * 2/omega_max), or implicit Newmark (the trapezoidal "
+                         "rule; a Newton iteration per step with a Jacobi-PCG on the device) at dt = --dt-factor * 2/omega_max")
+    ap.add_argument("--dt-factor", type=float, default=10.0,
+                    help="dynamics --scheme newmark: dt as a multiple of the explicit limit 2/omega_max of the linear operator")
+    ap.add_argument("--newton-tol", type=float, default=1e-10,
+                    help="dynamics --scheme newmark: a step has converged at |r| <= tol * max(|load|, |f_int|, |inertia + damping|)")
     ap.add_argument("--n-past", type=int, default=20)
     ap.add_argument("--n-future", type=int, default=20)
     ap.add_argument("--filter-size", type=int, default=150)
@@ -1009,6 +1028,17 @@ def main(argv=None):
                     help="steady_state, modal, dynamics, stress, estimate: 2 = quadratic tetrahedra (the mesh is elevated "
                          "unless the file holds tetra10); stress and estimate then read the run of dynamics --order 2")
     args = ap.parse_args(argv)
+    if args.command == "dynamics" and args.scheme == "newmark":
+        if args.parts and args.parts > 0:
+            ap.error("dynamics --scheme newmark --parts: the implicit stepper runs the whole mesh (no partitions)")
+        if args.energy:
+            ap.error("dynamics --scheme newmark --energy: the implicit stepper records no energy table")
+        if args.dt_follow:
+            ap.error("dynamics --scheme newmark --dt-follow: the implicit step is not tied to the stability limit")
+        if args.dt_check_every:
+            ap.error("dynamics --scheme newmark --dt-check-every: the implicit step is not tied to the stability limit")
+        if not (args.dt_factor > 0 and args.newton_tol > 0):
+            ap.error("dynamics --scheme newmark: --dt-factor and --newton-tol must be > 0")
     if args.command == "dynamics" and args.energy and args.material != "linear":
         ap.error(f"dynamics --material {args.material} --energy: the energy balance is defined for the linear material only "
                  "(its identity needs a symmetric constant K)")
@@ -1063,7 +1093,9 @@ def main(argv=None):
                                     parts=args.parts, partition=args.partition,
                                     energy_every=max(args.energy_every, 1) if args.energy else 0, fz=args.fz,
                                     material=args.material, dt_check_every=args.dt_check_every, dt_follow=args.dt_follow,
-                                    dt_follow_every=args.dt_follow_every)
+                                    dt_follow_every=args.dt_follow_every,
+                                    **({"scheme": "newmark", "dt_factor": args.dt_factor, "newton_tol": args.newton_tol}
+                                       if args.scheme == "newmark" else {}))
             print(json.dumps({**report, "path": path}))
         else:  # stress, estimate: the driver of (material, order); only stress has a history and a choice of measure
             only_stress = args.command == "stress"

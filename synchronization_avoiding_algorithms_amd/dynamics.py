@@ -17,7 +17,11 @@ steps with the shared-dof overwrite), :class:`OperatorPartition` all ranks in on
 ``record_energy`` on any of the three switches the energy balance on (``saa_operator_stepper_set_energy``): per step the
 kinetic energy ``T`` of the half step, the strain energy in cross form ``U`` and at ``t_n``, the work ``W`` of the load and
 the damping loss ``D``.  :func:`energy_balance` turns the rows into ``B_n - B_0``, which stays at round-off over whole-mesh
-and synchronised steps and in a predicted window drifts by the energy the predictor injects through the interface."""
+and synchronised steps and in a predicted window drifts by the energy the predictor injects through the interface.
+
+:class:`ImplicitStepper` is the unconditionally stable integrator on the same handle (``saa_operator_implicit_*``): Newmark's
+trapezoidal rule, a Newton iteration per step and a Jacobi-PCG on the shifted tangent, all on the device;
+:func:`run_dynamics_newmark` is :func:`run_dynamics` with it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -278,6 +282,109 @@ class OperatorStepper:
     def halo_scatter(self, row):
         self._rows(row, "row", 0, 1)
         _lib.check(self._lib.saa_operator_stepper_halo_scatter(self._h, _dev(row)))
+
+
+class ImplicitStepper:
+    """``saa_operator_implicit`` on a :class:`modal.ModalOperator` (borrowed: it must stay open while this object lives, and it
+    serves one stepper at a time).  Newmark with ``beta = 1/4``, ``gamma = 1/2`` (the trapezoidal rule) on the system
+    :class:`OperatorStepper` integrates explicitly - ``m a + alpha m v + f_int(d) = scale(t) f`` - so ``dt`` is chosen by the
+    physics, not by the stiffest element.  Per step a Newton iteration whose systems ``(K_T(x) + (4/dt^2 + 2 alpha/dt) m) dx = r``
+    are solved by a Jacobi-PCG that runs on the device (``include/saa_hip.h`` states the scheme, the convergence rule and what
+    is not provided: no line search, no automatic cut of ``dt``, no HHT-alpha, no consistent mass, no partitions, no energy
+    table).  ``mass`` and ``load`` (the un-ramped ``f``): ``(n_dof,)`` float64, CUDA tensors or arrays, copied.  State ``d = v =
+    0``, ``t = 0`` and the acceleration of the balance there (:meth:`set_state`)."""
+
+    REASONS = {0: "ok", 1: "max_newton", 2: "non_finite", 3: "inverted"}
+
+    def __init__(self, op, mass, load, dt, alpha, ramp=True, material="linear"):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.op = op
+        self.n_dof = op.n_dof
+        self.dt = float(dt)
+        self._traj = None
+        self.material = str(material).replace("-", "_")
+        m, f = self._vector(mass), self._vector(load)
+        _lib.check(self._lib.saa_operator_implicit_create(op._h, _dev(m), _dev(f), float(dt), float(alpha), 1 if ramp else 0,
+                                                          _lib.material_id(material), C.byref(self._h)))
+        self.steps_done = 0
+
+    _vector = OperatorStepper._vector
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.saa_operator_implicit_destroy(self._h)
+            self._h = C.c_void_p()
+        self._traj = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def step(self, n=1):
+        """Up to ``n`` steps.  Returns ``steps_done``, ``converged``, ``reason`` (0 ok, 1 ``max_newton`` reached, 2 a residual
+        not finite, 3 an inverted element under neo-Hooke) with its name in ``reason_name``, ``newton_iterations``,
+        ``cg_iterations`` (totals of the call) and ``residual`` (the last relative one).  A step that is not accepted leaves the
+        state, the time and the step index those of the last accepted step, bit for bit; it does not raise."""
+        info = _lib.ImplicitInfo()
+        _lib.check(self._lib.saa_operator_implicit_step(self._h, int(n), C.byref(info)))
+        self.steps_done += int(info.steps_done)
+        return {"steps_done": int(info.steps_done), "converged": bool(info.converged), "reason": int(info.reason),
+                "reason_name": self.REASONS.get(int(info.reason), "?"), "newton_iterations": int(info.newton_iterations),
+                "cg_iterations": int(info.cg_iterations), "residual": float(info.residual)}
+
+    def state(self):
+        """``(d, v, a, t)``: three new ``(n_dof,)`` CUDA tensors and the time, after everything enqueued has finished."""
+        import torch
+
+        d = torch.empty(self.n_dof, dtype=torch.float64, device=self.op.torch_device)
+        v, a = torch.empty_like(d), torch.empty_like(d)
+        t = C.c_double()
+        _lib.check(self._lib.saa_operator_implicit_get_state(self._h, _dev(d), _dev(v), _dev(a), C.byref(t)))
+        return d, v, a, t.value
+
+    def set_state(self, d=None, v=None, t=0.0):
+        """Displacement and velocity (None: zeros; masked on Dirichlet dofs and at nodes without elements) and the time; the
+        acceleration is that of the balance at this state, ``(scale(t) f - f_int(d) - alpha m v) / m``."""
+        a = None if d is None else self._vector(d)
+        b = None if v is None else self._vector(v)
+        _lib.check(self._lib.saa_operator_implicit_set_state(self._h, _dev(a), _dev(b), float(t)))
+
+    def record(self, n_cols, save_every=1, next_step_index=0, out=None):
+        """The recorder of :meth:`OperatorStepper.record`, same layout and rule: the ``d`` of step index ``i`` fills column
+        ``i / save_every`` when ``i % save_every == 0`` and the column exists.  ``n_cols = 0`` switches it off."""
+        import torch
+
+        if not n_cols:
+            _lib.check(self._lib.saa_operator_implicit_set_recorder(self._h, None, 0, 1, 0))
+            self._traj = None
+            return None
+        if out is None:
+            out = torch.zeros((self.n_dof, int(n_cols)), dtype=torch.float64, device=self.op.torch_device)
+        elif out.numel() < self.n_dof * int(n_cols):
+            raise ValueError(f"the recorder needs {self.n_dof * int(n_cols)} values, got {out.numel()}")
+        _lib.check(self._lib.saa_operator_implicit_set_recorder(self._h, _dev(out), int(n_cols), int(save_every),
+                                                                int(next_step_index)))
+        self._traj = out
+        return out.reshape(-1)[: self.n_dof * int(n_cols)].view(self.n_dof, int(n_cols))
+
+    def set_dt(self, dt):
+        """A new step from the next step on: the scheme is one-step, only the shift and the preconditioner are recomputed."""
+        _lib.check(self._lib.saa_operator_implicit_set_dt(self._h, float(dt)))
+        self.dt = float(dt)
+
+    def set_option(self, name: str, value: float):
+        """``tol`` (1e-10), ``max_newton`` (25), ``max_cg`` (20 n_dof per solve), ``check_every`` (25: PCG iterations between
+        two looks of the host at the status block)."""
+        _lib.check(self._lib.saa_operator_implicit_set_option(self._h, name.encode(), float(value)))
 
 
 def energy_balance(rows):
@@ -645,6 +752,56 @@ def run_dynamics(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, n
     if energy_every:
         report["energy"] = energy_report(table)
         return store, report, table
+    return store, report
+
+
+def run_dynamics_newmark(points, cells, dirichlet_nodes, n_steps, save_every=1, E=1e6, nu=0.3, rho=1.0, fz=0.5, alpha=0.5,
+                         gamma=0.9, device=0, material="linear", dt_factor=10.0, newton_tol=1e-10):
+    """:func:`run_dynamics` of the whole mesh with the implicit stepper (:class:`ImplicitStepper`) in the place of the
+    explicit one: same handle, clamp, lumped mass, ramped load ``(0, -fz, -fz)`` and ``alpha``, but ``dt = dt_factor * 2/omega_max``
+    of the linear operator - a multiple of the explicit limit, chosen for the physics.  Returns ``(store, report)`` with the
+    explicit run's layout and keys (``dt_crit`` is still the explicit limit; with a nonlinear material ``inverted`` is 1 and
+    ``first_inverted_step`` the failed step when a trial state held an inverted element, else 0 and -1) plus ``scheme``,
+    ``dt_factor``, ``newton_iterations``, ``cg_iterations``, ``converged`` and ``failed_step`` (-1: none; else the index of the step
+    that was not accepted - the run stops there and the columns from it on stay 0)."""
+    import torch
+
+    from . import fem_setup as fs
+    from .modal import ModalOperator, stable_time_step_operator
+
+    mat = _lib.material_id(material)
+    material = str(material).replace("-", "_")
+    if not (dt_factor > 0 and newton_tol > 0):
+        raise ValueError("need dt_factor > 0 and newton_tol > 0")
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    cells = np.ascontiguousarray(cells, dtype=np.int32)
+    lmd, mu = fs.lame(E, nu)
+    with ModalOperator(points, cells, fs.node_to_dof(dirichlet_nodes), lmd, mu, rho, device) as op:
+        mass = op.lumped_mass()
+        ts = stable_time_step_operator(op, mass, gamma)
+        dt = float(dt_factor) * ts["dt_crit"]
+        n_cols = int(n_steps / save_every)
+        with ImplicitStepper(op, mass, op.load((0.0, -fz, -fz)), dt, alpha, ramp=True, material=material) as st:
+            st.set_option("tol", newton_tol)
+            traj = st.record(n_cols, save_every) if n_cols > 0 else None
+            info = st.step(n_steps)
+            d0, _, _, tn = st.state()
+            store = traj.cpu().numpy() if traj is not None else np.zeros((op.n_dof, 0))
+        d = d0.cpu().numpy().reshape(-1, 3)
+        n_vert = int(cells[:, :4].max()) + 1 if len(cells) else 0
+        tip = np.nonzero(np.abs(points[:n_vert, 0] - points[:, 0].max()) < 1e-9)[0]
+        rule = reference_rule_dt(points, cells, E, nu, rho, gamma)
+        failed = -1 if info["converged"] else info["steps_done"]
+        report = {"order": op.order, "n_nodes": op.n_nodes, "n_elems": op.n_elems,
+                  "n_free_dofs": int(op.free.sum().item()), "dt": dt, "dt_crit": ts["dt_crit"],
+                  "dt_reference_rule": rule, "ratio": rule / ts["dt_crit"], "omega_max": ts["omega_max"], "steps": int(n_steps),
+                  "tn": tn, "max_abs_d": float(np.abs(d).max()), "tip_deflection": float(-d[tip, 1].mean())}
+        if mat != 0:
+            inv = info["reason"] == 3
+            report.update(material=material, inverted=int(inv), first_inverted_step=failed if inv else -1)
+        report.update(scheme="newmark", dt_factor=float(dt_factor), newton_iterations=info["newton_iterations"],
+                      cg_iterations=info["cg_iterations"], converged=info["converged"], failed_step=failed)
+    torch.cuda.synchronize(device)
     return store, report
 
 

@@ -232,6 +232,36 @@ class ModalOperator:
                                                         C.byref(n_inv) if count else None))
         return (kv, int(n_inv.value)) if count else kv
 
+    def shifted_apply(self, u, v, shift, material="svk", dot=False):
+        """``K_T(u) v + shift * v`` (``saa_operator_shifted_apply``), 0 on Dirichlet dofs: the operator of an implicit step, with
+        ``shift`` a diagonal such as ``(4/dt^2 + 2 alpha/dt) m``.  ``u``, ``v``, ``shift``: ``(n_dof,)`` float64 CUDA tensors, ``u``
+        and ``v`` masked on Dirichlet dofs on input; ``u`` may be None with ``linear``.  ``shift=None`` is :meth:`tangent_apply` bit
+        for bit.  ``dot=True``: returns ``(out, v . out)``, the product a 0-dim CUDA tensor summed on the device in a fixed order
+        (no synchronisation)."""
+        import torch
+
+        def ok(x):
+            return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.numel() == self.n_dof
+
+        mat = _lib.material_id(material)
+        if not ok(v):
+            raise ValueError(f"v must be a float64 CUDA tensor of {self.n_dof} values")
+        if not (ok(u) or (u is None and mat == 0)):
+            raise ValueError(f"u must be a float64 CUDA tensor of {self.n_dof} values")
+        if not (shift is None or ok(shift)):
+            raise ValueError(f"shift must be None or a float64 CUDA tensor of {self.n_dof} values")
+        v = v.reshape(-1).contiguous()
+        u = u.reshape(-1).contiguous() if u is not None else None
+        shift = shift.reshape(-1).contiguous() if shift is not None else None
+        out = torch.empty_like(v)
+        prod = torch.zeros((), dtype=torch.float64, device=v.device) if dot else None
+        _lib.check(self._lib.saa_operator_shifted_apply(self._h, mat, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                        C.c_void_p(v.data_ptr()),
+                                                        C.c_void_p(shift.data_ptr()) if shift is not None else None,
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(prod.data_ptr()) if dot else None,
+                                                        None))
+        return (out, prod) if dot else out
+
     def tangent_apply_block(self, u, V, material="svk", count=False):
         """``K_T(u) v`` for every row ``v`` of the ``(m, n_dof)`` float64 CUDA block ``V`` (or one ``(n_dof,)`` vector), in as
         many ``saa_operator_tangent_apply_block`` calls of at most 16 columns as it takes: what does not depend on the column
