@@ -1910,8 +1910,69 @@ int saa_topology_destroy(saa_topology *t) {
 struct saa_operator {
   saa::ModalOp *impl = nullptr;
 };
+struct saa_operator_stepper {
+  saa::OpStepper *impl = nullptr;
+};
+struct saa_operator_implicit {
+  saa::OpImplicit *impl = nullptr;
+};
 
 namespace {
+
+// The guards that the entry points from here to the predictor share.  Each returns SAA_OK or has set the error, so an entry
+// point reads as its guards, in the order in which it tests them (the orders differ between siblings and are part of the
+// interface), and then the call.  `name` is the entry point's own name, the head of every message.
+int null_handle(const std::string &name) { return fail(SAA_E_ARG, name + ": null handle"); }
+// a handle of one of the three kinds with its implementation behind it
+int live_operator(const saa_operator *h, const std::string &name) { return h && h->impl ? SAA_OK : null_handle(name); }
+int live_stepper(const saa_operator_stepper *h, const std::string &name) { return h && h->impl ? SAA_OK : null_handle(name); }
+int live_implicit(const saa_operator_implicit *h, const std::string &name) { return h && h->impl ? SAA_OK : null_handle(name); }
+
+int handle_of_order(const saa_operator *op, const std::string &name, int order) {
+  if (const int rc = live_operator(op, name)) return rc;
+  if (saa::modal_order(op->impl) == order) return SAA_OK;
+  return fail(SAA_E_ARG, name + (order == 1 ? ": a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)"
+                                            : ": a quadratic-element formula, not available on an order-1 handle "
+                                              "(saa_operator_create)"));
+}
+
+int known_material(int32_t material, const std::string &name) {
+  if (material >= SAA_MATERIAL_LINEAR && material <= SAA_MATERIAL_NEO_HOOKEAN) return SAA_OK;
+  return fail(SAA_E_ARG, name + ": material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
+}
+
+int state_for_material(const double *u_dev, int32_t material, const std::string &name) {  // only the linear tangent needs no state
+  return u_dev || material == SAA_MATERIAL_LINEAR ? SAA_OK : fail(SAA_E_ARG, name + ": null u_dev with a nonlinear material");
+}
+
+int column_count(int32_t m, const std::string &name) {
+  if (m >= 1 && m <= saa::kModalMaxColumns) return SAA_OK;
+  return fail(SAA_E_ARG, name + ": m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
+}
+
+int finite_positive(double v, const char *what, const std::string &name) {
+  return std::isfinite(v) && v > 0.0 ? SAA_OK : fail(SAA_E_ARG, name + ": " + what + " must be finite and > 0");
+}
+
+int finite_non_negative(double v, const char *what, const std::string &name) {
+  return std::isfinite(v) && v >= 0.0 ? SAA_OK : fail(SAA_E_ARG, name + ": " + what + " must be finite and >= 0");
+}
+
+int no_step_in_flight(const saa_operator_stepper *st, const std::string &name) {  // not between step_begin and step_finish
+  return saa::opstep_pending(st->impl) ? fail(SAA_E_STATE, name + ": a synchronised step is in flight") : SAA_OK;
+}
+
+int hip_done(hipError_t e, const std::string &name) {  // the tail of an entry point that launches
+  return e == hipSuccess ? SAA_OK : fail(SAA_E_HIP, name + ": " + hipGetErrorString(e));
+}
+
+// The tail of a create and of set_shared: the sticky HIP error is cleared, and what the implementation refused in words of its
+// own (err) is an argument error.
+int hip_or_argument_done(hipError_t e, const std::string &err, const std::string &name) {
+  if (e == hipSuccess) return SAA_OK;
+  (void)hipGetLastError();
+  return err.empty() ? hip_done(e, name) : fail(SAA_E_ARG, err);
+}
 
 // saa_operator_create (npe = 4, order 1) and saa_operator_create_p2 (npe = 10, order 2): they differ in the nodes per cell
 // and in how many elements still index with 32 bits.
@@ -1939,10 +2000,9 @@ int operator_create(const std::string &name, int npe, bool too_many_elems, const
     delete op;
     return fail(SAA_E_HIP, name + ": out of host memory");
   }
-  if (e != hipSuccess) {
+  if (const int rc = hip_or_argument_done(e, err, name)) {
     delete op;
-    (void)hipGetLastError();
-    return err.empty() ? fail(SAA_E_HIP, name + ": " + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+    return rc;
   }
   *out = op;
   return SAA_OK;
@@ -1953,93 +2013,77 @@ int operator_create(const std::string &name, int npe, bool too_many_elems, const
 int saa_operator_create(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *tets,
                         const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
                         saa_operator **out) {
-  return operator_create("saa_operator_create", 4, 4 * static_cast<int64_t>(n_elems) > INT32_MAX,
-                         "more than 2^29 elements or 2^31 dofs", 1, device, n_nodes, n_elems, xyz, tets, dirichlet_dofs,
-                         n_dirichlet, lambda_, mu, rho, out);
+  static const std::string name = "saa_operator_create";
+  return operator_create(name, 4, 4 * static_cast<int64_t>(n_elems) > INT32_MAX, "more than 2^29 elements or 2^31 dofs", 1, device,
+                         n_nodes, n_elems, xyz, tets, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, out);
 }
 
 int saa_operator_create_p2(int32_t device, int32_t n_nodes, int32_t n_elems, const double *xyz, const int32_t *cells10,
                            const int32_t *dirichlet_dofs, int32_t n_dirichlet, double lambda_, double mu, double rho,
                            saa_operator **out) {
-  return operator_create("saa_operator_create_p2", 10, n_elems > saa::kP2MaxElems,
+  static const std::string name = "saa_operator_create_p2";
+  return operator_create(name, 10, n_elems > saa::kP2MaxElems,
                          "more than 214748364 elements (10 * n_elems must fit 32 bits) or 2^31 dofs", 2, device, n_nodes, n_elems,
                          xyz, cells10, dirichlet_dofs, n_dirichlet, lambda_, mu, rho, out);
 }
 
 int saa_operator_order(const saa_operator *op) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_order: null handle");
+  static const std::string name = "saa_operator_order";
+  if (const int rc = live_operator(op, name)) return rc;
   return saa::modal_order(op->impl);
 }
 
 int saa_operator_load(saa_operator *op, double fx, double fy, double fz, double *f_dev) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_load: null handle");
-  if (!f_dev) return fail(SAA_E_ARG, "saa_operator_load: null output f_dev");
-  if (!(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(fz)))
-    return fail(SAA_E_ARG, "saa_operator_load: the force density must be finite");
+  static const std::string name = "saa_operator_load";
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!f_dev) return fail(SAA_E_ARG, name + ": null output f_dev");
+  if (!(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(fz))) return fail(SAA_E_ARG, name + ": the force density must be finite");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_load(op->impl, fx, fy, fz, f_dev);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_load: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_load(op->impl, fx, fy, fz, f_dev), name);
 }
 
 int saa_operator_diagonal(saa_operator *op, double *diag_k_dev, double *diag_m_dev) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_diagonal: null handle");
-  if (!diag_k_dev && !diag_m_dev) return fail(SAA_E_ARG, "saa_operator_diagonal: no output");
+  static const std::string name = "saa_operator_diagonal";
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!diag_k_dev && !diag_m_dev) return fail(SAA_E_ARG, name + ": no output");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_diagonal(op->impl, diag_k_dev, diag_m_dev);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_diagonal: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_diagonal(op->impl, diag_k_dev, diag_m_dev), name);
 }
 
 int saa_operator_set_stream(saa_operator *op, void *hip_stream) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_set_stream: null handle");
+  static const std::string name = "saa_operator_set_stream";
+  if (const int rc = live_operator(op, name)) return rc;
   saa::modal_set_stream(op->impl, static_cast<hipStream_t>(hip_stream));
   return SAA_OK;
 }
 
 int saa_operator_apply(saa_operator *op, int32_t m, const double *x_dev, int64_t ldx, double *kx_dev, double *mx_dev,
                        int64_t ldy) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_apply: null handle");
-  if (m < 1 || m > saa::kModalMaxColumns)
-    return fail(SAA_E_ARG, "saa_operator_apply: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
-  if (!x_dev || (!kx_dev && !mx_dev)) return fail(SAA_E_ARG, "saa_operator_apply: null input or no output");
+  static const std::string name = "saa_operator_apply";
+  if (const int rc = live_operator(op, name)) return rc;
+  if (const int rc = column_count(m, name)) return rc;
+  if (!x_dev || (!kx_dev && !mx_dev)) return fail(SAA_E_ARG, name + ": null input or no output");
   const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
-  if (ldx < n_dof || ldy < n_dof) return fail(SAA_E_ARG, "saa_operator_apply: leading dimension below 3 * n_nodes");
+  if (ldx < n_dof || ldy < n_dof) return fail(SAA_E_ARG, name + ": leading dimension below 3 * n_nodes");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::modal_order(op->impl) == 2 ? saa::p2_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy)
-                                                       : saa::modal_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_apply: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::modal_order(op->impl) == 2 ? saa::p2_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy)
+                                                  : saa::modal_apply(op->impl, m, x_dev, ldx, kx_dev, mx_dev, ldy),
+                  name);
 }
 
 int saa_operator_element_bound(saa_operator *op, double *omega_e_dev, double *omega_max, int32_t *argmax,
                                int32_t *n_nonpositive) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_element_bound: null handle");
-  if (saa::modal_order(op->impl) != 1) return fail(SAA_E_ARG, "saa_operator_element_bound: a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)");
+  static const std::string name = "saa_operator_element_bound";
+  if (const int rc = handle_of_order(op, name, 1)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::modal_element_bound(op->impl, omega_e_dev, omega_max, argmax, n_nonpositive);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_element_bound: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::modal_element_bound(op->impl, omega_e_dev, omega_max, argmax, n_nonpositive), name);
 }
 
 // ---- stress recovery of both element orders (saa_stress.hip, saa_stress_p2.hip) --------------------------------------
 namespace {
 
-// The checks that the seven entry points share.  Each returns SAA_OK or has set the error.  The linear family checks the
-// handle and its order before the column count; the _p2 family checks the column count first (p2_stress_front).
-int stress_handle(const saa_operator *op, const std::string &name, int order) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, name + ": null handle");
-  if (saa::modal_order(op->impl) == order) return SAA_OK;
-  return fail(SAA_E_ARG, name + (order == 1 ? ": a linear-element formula, not available on an order-2 handle (saa_operator_create_p2)"
-                                            : ": a quadratic-element formula, not available on an order-1 handle "
-                                              "(saa_operator_create)"));
-}
-
-int stress_columns(int32_t m, const std::string &name) {
-  if (m >= 1 && m <= saa::kModalMaxColumns) return SAA_OK;
-  return fail(SAA_E_ARG, name + ": m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
-}
-
+// The checks that only the seven stress entry points share (handle_of_order, column_count and hip_done are above).  The linear
+// family checks the handle and its order before the column count; the _p2 family checks the column count first (p2_stress_front).
 int stress_ld(const std::string &name, const char *what, int64_t ld, const char *bound, int64_t need) {
   if (ld >= need) return SAA_OK;
   return fail(SAA_E_ARG, name + ": " + what + " = " + std::to_string(ld) + " below " + bound + " = " + std::to_string(need));
@@ -2057,15 +2101,11 @@ int stress_compliance(const saa_operator *op, const std::string &name) {
   return fail(SAA_E_ARG, name + ": the compliance D^-1 needs mu > 0 and 3 lambda + 2 mu > 0");
 }
 
-int stress_done(hipError_t e, const std::string &name) {
-  return e == hipSuccess ? SAA_OK : fail(SAA_E_HIP, name + ": " + hipGetErrorString(e));
-}
-
 // The front of the three order-2 entry points: a null op, then the column count, then the handle behind op and its order.
 int p2_stress_front(const saa_operator *op, int32_t m, const std::string &name) {
   if (op)
-    if (const int rc = stress_columns(m, name)) return rc;
-  return stress_handle(op, name, 2);
+    if (const int rc = column_count(m, name)) return rc;
+  return handle_of_order(op, name, 2);
 }
 
 }  // namespace
@@ -2074,8 +2114,8 @@ int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_
                         double *von_mises_dev, double *energy_dev, int64_t ld_elem, double *energy_total_dev,
                         double *von_mises_max_dev, int32_t *von_mises_argmax_dev) {
   static const std::string name = "saa_operator_stress";
-  if (const int rc = stress_handle(op, name, 1)) return rc;
-  if (const int rc = stress_columns(m, name)) return rc;
+  if (const int rc = handle_of_order(op, name, 1)) return rc;
+  if (const int rc = column_count(m, name)) return rc;
   if (!x_dev) return fail(SAA_E_ARG, name + ": null displacement x_dev");
   const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
   const int64_t n_elems = saa::modal_n_elems(op->impl);
@@ -2085,7 +2125,7 @@ int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_
   if (von_mises_dev || energy_dev)
     if (const int rc = stress_ld(name, "ld_elem", ld_elem, "n_elems", n_elems)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  return stress_done(saa::stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, energy_dev, ld_elem,
+  return hip_done(saa::stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, energy_dev, ld_elem,
                                          energy_total_dev, von_mises_max_dev, von_mises_argmax_dev),
                      name);
 }
@@ -2093,8 +2133,8 @@ int saa_operator_stress(saa_operator *op, int32_t m, const double *x_dev, int64_
 int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const double *elem_dev, int64_t ld_elem, double *node_dev,
                                int64_t ld_node) {
   static const std::string name = "saa_operator_nodal_average";
-  if (const int rc = stress_handle(op, name, 1)) return rc;
-  if (const int rc = stress_columns(m, name)) return rc;
+  if (const int rc = handle_of_order(op, name, 1)) return rc;
+  if (const int rc = column_count(m, name)) return rc;
   if (k < 1 || k > saa::kStressMaxComponents)
     return fail(SAA_E_ARG, name + ": k = " + std::to_string(k) + " components, 1 <= k <= 8");
   if (!elem_dev || !node_dev) return fail(SAA_E_ARG, name + ": null elem_dev or node_dev");
@@ -2102,7 +2142,7 @@ int saa_operator_nodal_average(saa_operator *op, int32_t m, int32_t k, const dou
   if (const int rc = stress_ld(name, "ld_elem", ld_elem, "k * n_elems", k * n_elems)) return rc;
   if (const int rc = stress_ld(name, "ld_node", ld_node, "k * n_nodes", k * n_nodes)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  return stress_done(saa::stress_nodal_average(op->impl, m, k, elem_dev, ld_elem, node_dev, ld_node), name);
+  return hip_done(saa::stress_nodal_average(op->impl, m, k, elem_dev, ld_elem, node_dev, ld_node), name);
 }
 
 int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_elem_dev, int64_t ld_sigma,
@@ -2110,8 +2150,8 @@ int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_e
                               double *eta2_dev, int64_t ld_eta, double *eta2_total_dev, double *eta2_max_dev,
                               int32_t *eta2_argmax_dev) {
   static const std::string name = "saa_operator_stress_error";
-  if (const int rc = stress_handle(op, name, 1)) return rc;
-  if (const int rc = stress_columns(m, name)) return rc;
+  if (const int rc = handle_of_order(op, name, 1)) return rc;
+  if (const int rc = column_count(m, name)) return rc;
   if (!sigma_elem_dev) return fail(SAA_E_ARG, name + ": null element stress sigma_elem_dev");
   if (const int rc = stress_one_of(name, sigma_node_dev, sigma_other_dev)) return rc;
   const int64_t n_nodes = saa::modal_n_nodes(op->impl), n_elems = saa::modal_n_elems(op->impl);
@@ -2124,7 +2164,7 @@ int saa_operator_stress_error(saa_operator *op, int32_t m, const double *sigma_e
     if (const int rc = stress_ld(name, "ld_eta", ld_eta, "n_elems", n_elems)) return rc;
   if (const int rc = stress_compliance(op, name)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  return stress_done(saa::stress_error(op->impl, m, sigma_elem_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
+  return hip_done(saa::stress_error(op->impl, m, sigma_elem_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
                                        eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev),
                      name);
 }
@@ -2145,7 +2185,7 @@ int saa_operator_stress_p2(saa_operator *op, int32_t m, const double *x_dev, int
   if (energy_dev)
     if (const int rc = stress_ld(name, "ld_elem", ld_elem, "n_elems", n_elems)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  return stress_done(saa::p2_stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, ld_vm, energy_dev, ld_elem,
+  return hip_done(saa::p2_stress_element(op->impl, m, x_dev, ldx, sigma_dev, ld_sigma, von_mises_dev, ld_vm, energy_dev, ld_elem,
                                             energy_total_dev, von_mises_max_dev, von_mises_argmax_dev),
                      name);
 }
@@ -2160,7 +2200,7 @@ int saa_operator_nodal_stress_p2(saa_operator *op, int32_t m, const double *sigm
   if (!sigma_node_dev) return SAA_OK;  // (the only output: nothing is launched)
   if (const int rc = stress_ld(name, "ld_node", ld_node, "6 * n_nodes", 6 * n_nodes)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  return stress_done(saa::p2_stress_nodal(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node), name);
+  return hip_done(saa::p2_stress_nodal(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node), name);
 }
 
 int saa_operator_stress_error_p2(saa_operator *op, int32_t m, const double *sigma_dev, int64_t ld_sigma,
@@ -2181,7 +2221,7 @@ int saa_operator_stress_error_p2(saa_operator *op, int32_t m, const double *sigm
     if (const int rc = stress_ld(name, "ld_eta", ld_eta, "n_elems", n_elems)) return rc;
   if (const int rc = stress_compliance(op, name)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  return stress_done(saa::p2_stress_error(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
+  return hip_done(saa::p2_stress_error(op->impl, m, sigma_dev, ld_sigma, sigma_node_dev, ld_node, sigma_other_dev, ld_other,
                                           eta2_dev, ld_eta, eta2_total_dev, eta2_max_dev, eta2_argmax_dev),
                      name);
 }
@@ -2197,10 +2237,10 @@ int saa_operator_stress_finite(saa_operator *op, int32_t material, int32_t measu
                                "saa_operator_stress_p2");
   if (measure != SAA_STRESS_PK2 && measure != SAA_STRESS_CAUCHY)
     return fail(SAA_E_ARG, name + ": measure " + std::to_string(measure) + " is neither 0 (pk2) nor 1 (cauchy)");
-  if (!op) return fail(SAA_E_ARG, name + ": null handle");
+  if (!op) return null_handle(name);
   if (!x_dev) return fail(SAA_E_ARG, name + ": null displacement x_dev");
-  if (const int rc = stress_columns(m, name)) return rc;
-  if (!op->impl) return fail(SAA_E_ARG, name + ": null handle");  // (the first look at what op points to)
+  if (const int rc = column_count(m, name)) return rc;
+  if (!op->impl) return null_handle(name);  // (the first look at what op points to)
   const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
   const int64_t n_points = (saa::modal_order(op->impl) == 2 ? 4 : 1) * static_cast<int64_t>(saa::modal_n_elems(op->impl));
   if (const int rc = stress_ld(name, "ldx", ldx, "3 * n_nodes", n_dof)) return rc;
@@ -2213,7 +2253,7 @@ int saa_operator_stress_finite(saa_operator *op, int32_t material, int32_t measu
   if (energy_dev)
     if (const int rc = stress_ld(name, "ld_elem", ld_elem, "n_elems", saa::modal_n_elems(op->impl))) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  return stress_done(saa::stress_finite(op->impl, material, measure, m, x_dev, ldx, stress_dev, ld_stress, von_mises_dev, ld_vm,
+  return hip_done(saa::stress_finite(op->impl, material, measure, m, x_dev, ldx, stress_dev, ld_stress, von_mises_dev, ld_vm,
                                         det_f_dev, ld_det, energy_dev, ld_elem, energy_total_dev, von_mises_max_dev,
                                         von_mises_argmax_dev, n_inverted),
                      name);
@@ -2228,291 +2268,255 @@ int saa_operator_destroy(saa_operator *op) {
 
 // ---- explicit dynamics on the operator handle (saa_opstep.hip) -----------------------------------------------------
 int saa_operator_lumped_mass(saa_operator *op, double *mass_dev) {
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_lumped_mass: null handle");
-  if (!mass_dev) return fail(SAA_E_ARG, "saa_operator_lumped_mass: null output mass_dev");
+  static const std::string name = "saa_operator_lumped_mass";
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!mass_dev) return fail(SAA_E_ARG, name + ": null output mass_dev");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_lumped_mass(op->impl, mass_dev);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_lumped_mass: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_lumped_mass(op->impl, mass_dev), name);
 }
 
 int saa_operator_internal_force(saa_operator *op, int32_t material, const double *x_dev, double *f_dev, double *energy_elem_dev,
                                 int64_t *n_inverted) {
-  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
-    return fail(SAA_E_ARG, "saa_operator_internal_force: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_internal_force: null handle");
-  if (!x_dev || !f_dev) return fail(SAA_E_ARG, "saa_operator_internal_force: null x_dev or f_dev");
+  static const std::string name = "saa_operator_internal_force";
+  if (const int rc = known_material(material, name)) return rc;
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!x_dev || !f_dev) return fail(SAA_E_ARG, name + ": null x_dev or f_dev");
   if (energy_elem_dev && material == SAA_MATERIAL_LINEAR)
-    return fail(SAA_E_ARG, "saa_operator_internal_force: energy_elem_dev with the linear material (saa_operator_stress has its energy)");
+    return fail(SAA_E_ARG, name + ": energy_elem_dev with the linear material (saa_operator_stress has its energy)");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_internal_force(op->impl, material, x_dev, f_dev, energy_elem_dev, n_inverted);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_internal_force: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_internal_force(op->impl, material, x_dev, f_dev, energy_elem_dev, n_inverted), name);
 }
 
 int saa_operator_tangent_apply(saa_operator *op, int32_t material, const double *u_dev, const double *v_dev, double *kv_dev,
                                int64_t *n_inverted) {
-  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
-    return fail(SAA_E_ARG, "saa_operator_tangent_apply: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_tangent_apply: null handle");
-  if (!v_dev || !kv_dev) return fail(SAA_E_ARG, "saa_operator_tangent_apply: null v_dev or kv_dev");
-  if (!u_dev && material != SAA_MATERIAL_LINEAR)
-    return fail(SAA_E_ARG, "saa_operator_tangent_apply: null u_dev with a nonlinear material");
+  static const std::string name = "saa_operator_tangent_apply";
+  if (const int rc = known_material(material, name)) return rc;
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!v_dev || !kv_dev) return fail(SAA_E_ARG, name + ": null v_dev or kv_dev");
+  if (const int rc = state_for_material(u_dev, material, name)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_tangent_apply(op->impl, material, u_dev, v_dev, kv_dev, n_inverted);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_tangent_apply: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_tangent_apply(op->impl, material, u_dev, v_dev, kv_dev, n_inverted), name);
 }
 
 int saa_operator_tangent_apply_block(saa_operator *op, int32_t material, const double *u_dev, int32_t m, const double *v_dev,
                                      int64_t ldv, double *kv_dev, int64_t ldkv, int64_t *n_inverted) {
-  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
-    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
-  if (m < 1 || m > saa::kModalMaxColumns)
-    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: m = " + std::to_string(m) + " columns, 1 <= m <= 16 per call");
-  if (ldv < 0 || ldkv < 0) return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: negative leading dimension");
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: null handle");
-  if (!v_dev || !kv_dev) return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: null v_dev or kv_dev");
-  if (!u_dev && material != SAA_MATERIAL_LINEAR)
-    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: null u_dev with a nonlinear material");
+  static const std::string name = "saa_operator_tangent_apply_block";
+  if (const int rc = known_material(material, name)) return rc;
+  if (const int rc = column_count(m, name)) return rc;
+  if (ldv < 0 || ldkv < 0) return fail(SAA_E_ARG, name + ": negative leading dimension");
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!v_dev || !kv_dev) return fail(SAA_E_ARG, name + ": null v_dev or kv_dev");
+  if (const int rc = state_for_material(u_dev, material, name)) return rc;
   const int64_t n_dof = 3 * static_cast<int64_t>(saa::modal_n_nodes(op->impl));
-  if (ldv < n_dof || ldkv < n_dof)
-    return fail(SAA_E_ARG, "saa_operator_tangent_apply_block: leading dimension below 3 * n_nodes");
+  if (ldv < n_dof || ldkv < n_dof) return fail(SAA_E_ARG, name + ": leading dimension below 3 * n_nodes");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_tangent_apply_block(op->impl, material, u_dev, m, v_dev, ldv, kv_dev, ldkv, n_inverted);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_tangent_apply_block: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_tangent_apply_block(op->impl, material, u_dev, m, v_dev, ldv, kv_dev, ldkv, n_inverted), name);
 }
-
-struct saa_operator_stepper {
-  saa::OpStepper *impl = nullptr;
-};
 
 int saa_operator_stepper_create(saa_operator *op, const double *mass_dev, const double *f_ext_dev, double dt, double alpha,
                                 int32_t ramp, saa_operator_stepper **out) {
-  if (!out) return fail(SAA_E_ARG, "saa_operator_stepper_create: null output");
+  static const std::string name = "saa_operator_stepper_create";
+  if (!out) return fail(SAA_E_ARG, name + ": null output");
   *out = nullptr;
-  if (!(std::isfinite(dt) && dt > 0.0)) return fail(SAA_E_ARG, "saa_operator_stepper_create: dt must be finite and > 0");
-  if (!(std::isfinite(alpha) && alpha >= 0.0)) return fail(SAA_E_ARG, "saa_operator_stepper_create: alpha must be finite and >= 0");
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_stepper_create: null handle");
-  if (!mass_dev || !f_ext_dev) return fail(SAA_E_ARG, "saa_operator_stepper_create: null mass_dev or f_ext_dev");
+  if (const int rc = finite_positive(dt, "dt", name)) return rc;
+  if (const int rc = finite_non_negative(alpha, "alpha", name)) return rc;
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!mass_dev || !f_ext_dev) return fail(SAA_E_ARG, name + ": null mass_dev or f_ext_dev");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
   saa_operator_stepper *st = new (std::nothrow) saa_operator_stepper;
-  if (!st) return fail(SAA_E_HIP, "saa_operator_stepper_create: out of host memory");
+  if (!st) return fail(SAA_E_HIP, name + ": out of host memory");
   std::string err;
   const hipError_t e = saa::opstep_create(op->impl, mass_dev, f_ext_dev, dt, alpha, ramp != 0, &st->impl, err);
-  if (e != hipSuccess) {
+  if (const int rc = hip_or_argument_done(e, err, name)) {
     delete st;
-    (void)hipGetLastError();
-    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_stepper_create: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+    return rc;
   }
   *out = st;
   return SAA_OK;
 }
 
 int saa_operator_stepper_set_state(saa_operator_stepper *st, const double *d0_dev, const double *dn_dev, double tn) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_state: null handle");
-  if (!std::isfinite(tn)) return fail(SAA_E_ARG, "saa_operator_stepper_set_state: tn must be finite");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_state: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_set_state";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (!std::isfinite(tn)) return fail(SAA_E_ARG, name + ": tn must be finite");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   hipError_t e = saa::opstep_set_state(st->impl, d0_dev, dn_dev, tn);
   if (e == hipSuccess) e = saa::opstep_clear_inverted(st->impl);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_state: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(e, name);
 }
 
 int saa_operator_stepper_get_state(saa_operator_stepper *st, double *d0_dev, double *dn_dev, double *tn) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_get_state: null handle");
+  static const std::string name = "saa_operator_stepper_get_state";
+  if (const int rc = live_stepper(st, name)) return rc;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_get_state(st->impl, d0_dev, dn_dev, tn);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_get_state: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_get_state(st->impl, d0_dev, dn_dev, tn), name);
 }
 
 int saa_operator_stepper_set_recorder(saa_operator_stepper *st, double *traj_dev, int64_t n_cols, int32_t save_every,
                                       int64_t next_step_index) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_recorder: null handle");
-  if (traj_dev && (n_cols <= 0 || save_every <= 0 || next_step_index < 0))
-    return fail(SAA_E_ARG, "saa_operator_stepper_set_recorder: bad argument");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_recorder: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_set_recorder";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (traj_dev && (n_cols <= 0 || save_every <= 0 || next_step_index < 0)) return fail(SAA_E_ARG, name + ": bad argument");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   saa::opstep_set_recorder(st->impl, traj_dev, traj_dev ? n_cols : 0, traj_dev ? save_every : 1, traj_dev ? next_step_index : 0);
   return SAA_OK;
 }
 
-int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *name, double value) {
-  if (!st || !st->impl || !name) return fail(SAA_E_ARG, "saa_operator_stepper_set_option: null handle or name");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_option: a synchronised step is in flight");
-  if (saa::opstep_energy_on(st->impl) && std::strcmp(name, "passes") == 0 && value != 3.0)
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_option: passes 1 / 2 while the energy balance is recorded");
+int saa_operator_stepper_set_option(saa_operator_stepper *st, const char *option, double value) {
+  static const std::string name = "saa_operator_stepper_set_option";
+  if (!st || !st->impl || !option) return fail(SAA_E_ARG, name + ": null handle or name");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
+  if (saa::opstep_energy_on(st->impl) && std::strcmp(option, "passes") == 0 && value != 3.0)
+    return fail(SAA_E_STATE, name + ": passes 1 / 2 while the energy balance is recorded");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   hipError_t e = hipSuccess;
-  if (!saa::opstep_set_option(st->impl, name, value, &e))
-    return fail(SAA_E_ARG, std::string("saa_operator_stepper_set_option: unknown option or value: ") + name + " (stored_geometry 0 / 1, passes 1 / 2 / 3)");
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_option: ") + hipGetErrorString(e));
-  return SAA_OK;
+  if (!saa::opstep_set_option(st->impl, option, value, &e))
+    return fail(SAA_E_ARG, name + ": unknown option or value: " + option + " (stored_geometry 0 / 1, passes 1 / 2 / 3)");
+  return hip_done(e, name);
 }
 
 int saa_operator_stepper_step(saa_operator_stepper *st, int32_t nsteps) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step: null handle");
-  if (nsteps < 0) return fail(SAA_E_ARG, "saa_operator_stepper_step: nsteps < 0");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_step";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (nsteps < 0) return fail(SAA_E_ARG, name + ": nsteps < 0");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   if (nsteps == 0) return SAA_OK;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_step(st->impl, nsteps);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_step(st->impl, nsteps), name);
 }
 
 int saa_operator_stepper_set_shared(saa_operator_stepper *st, int32_t n_shared, const int32_t *shared_local_host,
                                     const int32_t *shared_slots_host, int32_t n_global_shared) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_shared: null handle");
-  if (n_shared < 0 || n_global_shared < n_shared)
-    return fail(SAA_E_ARG, "saa_operator_stepper_set_shared: need 0 <= n_shared <= n_global_shared");
+  static const std::string name = "saa_operator_stepper_set_shared";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (n_shared < 0 || n_global_shared < n_shared) return fail(SAA_E_ARG, name + ": need 0 <= n_shared <= n_global_shared");
   if (n_shared > 0 && (!shared_local_host || !shared_slots_host))
-    return fail(SAA_E_ARG, "saa_operator_stepper_set_shared: null shared_local_host or shared_slots_host");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_shared: a synchronised step is in flight");
+    return fail(SAA_E_ARG, name + ": null shared_local_host or shared_slots_host");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
   std::string err;
   const hipError_t e = saa::opstep_set_shared(st->impl, n_shared, shared_local_host, shared_slots_host, n_global_shared, err);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_stepper_set_shared: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
-  }
-  return SAA_OK;
+  return hip_or_argument_done(e, err, name);
 }
 
 int saa_operator_stepper_set_interface_buffer(saa_operator_stepper *st, double *iface_dev) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_interface_buffer: null handle");
-  if (saa::opstep_pending(st->impl))
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_interface_buffer: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_set_interface_buffer";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   saa::opstep_set_interface_buffer(st->impl, iface_dev);
   return SAA_OK;
 }
 
 int saa_operator_stepper_step_begin(saa_operator_stepper *st) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step_begin: null handle");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step_begin: previous step not finished");
-  if (saa::opstep_lacks_interface_buffer(st->impl))
-    return fail(SAA_E_STATE, "saa_operator_stepper_step_begin: no interface buffer set");
+  static const std::string name = "saa_operator_stepper_step_begin";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, name + ": previous step not finished");
+  if (saa::opstep_lacks_interface_buffer(st->impl)) return fail(SAA_E_STATE, name + ": no interface buffer set");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_step_begin(st->impl);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step_begin: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_step_begin(st->impl), name);
 }
 
 int saa_operator_stepper_step_finish(saa_operator_stepper *st, double *hist_dev, int64_t hist_row) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step_finish: null handle");
-  if (hist_dev && hist_row < 0) return fail(SAA_E_ARG, "saa_operator_stepper_step_finish: negative history row");
-  if (!saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step_finish: no step in flight");
+  static const std::string name = "saa_operator_stepper_step_finish";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (hist_dev && hist_row < 0) return fail(SAA_E_ARG, name + ": negative history row");
+  if (!saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, name + ": no step in flight");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_step_finish(st->impl, hist_dev, hist_row);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step_finish: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_step_finish(st->impl, hist_dev, hist_row), name);
 }
 
 int saa_operator_stepper_step_predicted(saa_operator_stepper *st, int32_t nsteps, const double *table_dev, int64_t table_row0,
                                         double *hist_dev, int64_t hist_row0) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_step_predicted: null handle");
-  if (nsteps < 0 || table_row0 < 0 || (hist_dev && hist_row0 < 0))
-    return fail(SAA_E_ARG, "saa_operator_stepper_step_predicted: negative nsteps or row");
-  if (saa::opstep_n_shared(st->impl) > 0 && !table_dev) return fail(SAA_E_ARG, "saa_operator_stepper_step_predicted: null table");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_step_predicted: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_step_predicted";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (nsteps < 0 || table_row0 < 0 || (hist_dev && hist_row0 < 0)) return fail(SAA_E_ARG, name + ": negative nsteps or row");
+  if (saa::opstep_n_shared(st->impl) > 0 && !table_dev) return fail(SAA_E_ARG, name + ": null table");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   if (nsteps == 0) return SAA_OK;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_step_predicted(st->impl, nsteps, table_dev, table_row0, hist_dev, hist_row0);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_step_predicted: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_step_predicted(st->impl, nsteps, table_dev, table_row0, hist_dev, hist_row0), name);
 }
 
 int saa_operator_stepper_halo_gather(saa_operator_stepper *st, double *row_dev) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_halo_gather: null handle");
-  if (saa::opstep_n_shared(st->impl) > 0 && !row_dev) return fail(SAA_E_ARG, "saa_operator_stepper_halo_gather: null row");
+  static const std::string name = "saa_operator_stepper_halo_gather";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (saa::opstep_n_shared(st->impl) > 0 && !row_dev) return fail(SAA_E_ARG, name + ": null row");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_halo(st->impl, row_dev, true);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_halo_gather: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_halo(st->impl, row_dev, true), name);
 }
 
 int saa_operator_stepper_halo_scatter(saa_operator_stepper *st, const double *row_dev) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_halo_scatter: null handle");
-  if (saa::opstep_n_shared(st->impl) > 0 && !row_dev) return fail(SAA_E_ARG, "saa_operator_stepper_halo_scatter: null row");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_halo_scatter: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_halo_scatter";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (saa::opstep_n_shared(st->impl) > 0 && !row_dev) return fail(SAA_E_ARG, name + ": null row");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_halo(st->impl, const_cast<double *>(row_dev), false);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_halo_scatter: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_halo(st->impl, const_cast<double *>(row_dev), false), name);
 }
 
 int saa_operator_stepper_set_energy(saa_operator_stepper *st, double *energy_dev, int64_t n_rows, int32_t every,
                                     int64_t next_step_index, const uint8_t *shared_owned_host) {
-  if (n_rows < 0) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: n_rows < 0");
-  if (every < 1) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: every < 1");
-  if (next_step_index < 0) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: next_step_index < 0");
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_energy: null handle");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_set_energy";
+  if (n_rows < 0) return fail(SAA_E_ARG, name + ": n_rows < 0");
+  if (every < 1) return fail(SAA_E_ARG, name + ": every < 1");
+  if (next_step_index < 0) return fail(SAA_E_ARG, name + ": next_step_index < 0");
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   if (energy_dev && saa::opstep_passes(st->impl) != 3)
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: the passes option is 1 or 2 (a measurement aid that does not advance the state)");
+    return fail(SAA_E_STATE, name + ": the passes option is 1 or 2 (a measurement aid that does not advance the state)");
   if (energy_dev && saa::opstep_material(st->impl) != SAA_MATERIAL_LINEAR)
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_energy: a nonlinear material is set (the identity needs a symmetric constant K)");
+    return fail(SAA_E_STATE, name + ": a nonlinear material is set (the identity needs a symmetric constant K)");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_set_energy(st->impl, energy_dev, energy_dev ? n_rows : 0, energy_dev ? every : 1,
-                                              energy_dev ? next_step_index : 0, shared_owned_host);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_energy: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_set_energy(st->impl, energy_dev, energy_dev ? n_rows : 0, energy_dev ? every : 1,
+                                         energy_dev ? next_step_index : 0, shared_owned_host),
+                  name);
 }
 
 int saa_operator_stepper_set_material(saa_operator_stepper *st, int32_t material) {
-  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
-    return fail(SAA_E_ARG, "saa_operator_stepper_set_material: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_material: null handle");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_material: a synchronised step is in flight");
+  static const std::string name = "saa_operator_stepper_set_material";
+  if (const int rc = known_material(material, name)) return rc;
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   if (saa::opstep_energy_on(st->impl))
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_material: the energy balance is recorded (its identity is that of the linear operator)");
+    return fail(SAA_E_STATE, name + ": the energy balance is recorded (its identity is that of the linear operator)");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_set_material(st->impl, material);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_material: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_set_material(st->impl, material), name);
 }
 
 int saa_operator_stepper_inverted(saa_operator_stepper *st, int64_t *count, int64_t *first_step) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_inverted: null handle");
+  static const std::string name = "saa_operator_stepper_inverted";
+  if (const int rc = live_stepper(st, name)) return rc;
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_inverted(st->impl, count, first_step);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_inverted: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_inverted(st->impl, count, first_step), name);
 }
 
 int saa_operator_tangent_bound(saa_operator *op, int32_t material, const double *u_dev, double *omega_e_dev, double *omega_max,
                                int32_t *argmax, int64_t *counts) {
-  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
-    return fail(SAA_E_ARG, "saa_operator_tangent_bound: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_tangent_bound: null handle");
-  if (!omega_max || !argmax) return fail(SAA_E_ARG, "saa_operator_tangent_bound: null omega_max or argmax");
-  if (!u_dev && material != SAA_MATERIAL_LINEAR)
-    return fail(SAA_E_ARG, "saa_operator_tangent_bound: null u_dev with a nonlinear material");
+  static const std::string name = "saa_operator_tangent_bound";
+  if (const int rc = known_material(material, name)) return rc;
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!omega_max || !argmax) return fail(SAA_E_ARG, name + ": null omega_max or argmax");
+  if (const int rc = state_for_material(u_dev, material, name)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_tangent_bound(op->impl, material, u_dev, omega_e_dev, omega_max, argmax, counts);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_tangent_bound: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_tangent_bound(op->impl, material, u_dev, omega_e_dev, omega_max, argmax, counts), name);
 }
 
 int saa_operator_stepper_set_dt(saa_operator_stepper *st, double dt_new) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_stepper_set_dt: null handle");
-  if (!(std::isfinite(dt_new) && dt_new > 0.0)) return fail(SAA_E_ARG, "saa_operator_stepper_set_dt: dt_new must be finite and > 0");
+  static const std::string name = "saa_operator_stepper_set_dt";
+  if (const int rc = live_stepper(st, name)) return rc;
+  if (const int rc = finite_positive(dt_new, "dt_new", name)) return rc;
   const double alpha = saa::opstep_alpha(st->impl);
   if (alpha > 0.0 && dt_new >= 2.0 / alpha)
-    return fail(SAA_E_ARG, "saa_operator_stepper_set_dt: dt_new must be below 2/alpha (the update that continues the scheme divides by 1/dt_new - alpha/2)");
-  if (saa::opstep_pending(st->impl)) return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: a synchronised step is in flight");
+    return fail(SAA_E_ARG, name + ": dt_new must be below 2/alpha (the update that continues the scheme divides by 1/dt_new - alpha/2)");
+  if (const int rc = no_step_in_flight(st, name)) return rc;
   if (saa::opstep_has_shared_set(st->impl))
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: a shared set is in place (a rank holds only its share of the internal force)");
-  if (saa::opstep_energy_on(st->impl))
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: the energy balance is recorded (its identity assumes one dt)");
+    return fail(SAA_E_STATE, name + ": a shared set is in place (a rank holds only its share of the internal force)");
+  if (saa::opstep_energy_on(st->impl)) return fail(SAA_E_STATE, name + ": the energy balance is recorded (its identity assumes one dt)");
   if (saa::opstep_passes(st->impl) != 3)
-    return fail(SAA_E_STATE, "saa_operator_stepper_set_dt: the passes option is 1 or 2 (a measurement aid that does not advance the state)");
+    return fail(SAA_E_STATE, name + ": the passes option is 1 or 2 (a measurement aid that does not advance the state)");
   HIP_TRY(hipSetDevice(saa::opstep_device(st->impl)));
-  const hipError_t e = saa::opstep_set_dt(st->impl, dt_new);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_stepper_set_dt: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opstep_set_dt(st->impl, dt_new), name);
 }
 
 int saa_operator_stepper_destroy(saa_operator_stepper *st) {
@@ -2526,98 +2530,88 @@ int saa_operator_stepper_destroy(saa_operator_stepper *st) {
 // ---- implicit dynamics on the operator handle (saa_opimp.hip) ----------------------------------------------------
 int saa_operator_shifted_apply(saa_operator *op, int32_t material, const double *u_dev, const double *v_dev, const double *shift_dev,
                                double *out_dev, double *dot_dev, int64_t *n_inverted) {
-  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
-    return fail(SAA_E_ARG, "saa_operator_shifted_apply: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_shifted_apply: null handle");
-  if (!v_dev || !out_dev) return fail(SAA_E_ARG, "saa_operator_shifted_apply: null v_dev or out_dev");
-  if (!u_dev && material != SAA_MATERIAL_LINEAR)
-    return fail(SAA_E_ARG, "saa_operator_shifted_apply: null u_dev with a nonlinear material");
+  static const std::string name = "saa_operator_shifted_apply";
+  if (const int rc = known_material(material, name)) return rc;
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!v_dev || !out_dev) return fail(SAA_E_ARG, name + ": null v_dev or out_dev");
+  if (const int rc = state_for_material(u_dev, material, name)) return rc;
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
-  const hipError_t e = saa::operator_shifted_apply(op->impl, material, u_dev, v_dev, shift_dev, out_dev, dot_dev, n_inverted);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_shifted_apply: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::operator_shifted_apply(op->impl, material, u_dev, v_dev, shift_dev, out_dev, dot_dev, n_inverted), name);
 }
-
-struct saa_operator_implicit {
-  saa::OpImplicit *impl = nullptr;
-};
 
 int saa_operator_implicit_create(saa_operator *op, const double *mass_dev, const double *f_ext_dev, double dt, double alpha,
                                  int32_t ramp, int32_t material, saa_operator_implicit **out) {
-  if (!out) return fail(SAA_E_ARG, "saa_operator_implicit_create: null output");
+  static const std::string name = "saa_operator_implicit_create";
+  if (!out) return fail(SAA_E_ARG, name + ": null output");
   *out = nullptr;
-  if (!(std::isfinite(dt) && dt > 0.0)) return fail(SAA_E_ARG, "saa_operator_implicit_create: dt must be finite and > 0");
-  if (!(std::isfinite(alpha) && alpha >= 0.0)) return fail(SAA_E_ARG, "saa_operator_implicit_create: alpha must be finite and >= 0");
-  if (material < SAA_MATERIAL_LINEAR || material > SAA_MATERIAL_NEO_HOOKEAN)
-    return fail(SAA_E_ARG, "saa_operator_implicit_create: material " + std::to_string(material) + " is none of 0 (linear), 1 (svk), 2 (neo_hookean)");
-  if (!op || !op->impl) return fail(SAA_E_ARG, "saa_operator_implicit_create: null handle");
-  if (!mass_dev || !f_ext_dev) return fail(SAA_E_ARG, "saa_operator_implicit_create: null mass_dev or f_ext_dev");
+  if (const int rc = finite_positive(dt, "dt", name)) return rc;
+  if (const int rc = finite_non_negative(alpha, "alpha", name)) return rc;
+  if (const int rc = known_material(material, name)) return rc;
+  if (const int rc = live_operator(op, name)) return rc;
+  if (!mass_dev || !f_ext_dev) return fail(SAA_E_ARG, name + ": null mass_dev or f_ext_dev");
   HIP_TRY(hipSetDevice(saa::modal_device(op->impl)));
   saa_operator_implicit *st = new (std::nothrow) saa_operator_implicit;
-  if (!st) return fail(SAA_E_HIP, "saa_operator_implicit_create: out of host memory");
+  if (!st) return fail(SAA_E_HIP, name + ": out of host memory");
   std::string err;
   const hipError_t e = saa::opimp_create(op->impl, mass_dev, f_ext_dev, dt, alpha, ramp != 0, material, &st->impl, err);
-  if (e != hipSuccess) {
+  if (const int rc = hip_or_argument_done(e, err, name)) {
     delete st;
-    (void)hipGetLastError();
-    return err.empty() ? fail(SAA_E_HIP, std::string("saa_operator_implicit_create: ") + hipGetErrorString(e)) : fail(SAA_E_ARG, err);
+    return rc;
   }
   *out = st;
   return SAA_OK;
 }
 
 int saa_operator_implicit_set_state(saa_operator_implicit *st, const double *d_dev, const double *v_dev, double t) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_set_state: null handle");
-  if (!std::isfinite(t)) return fail(SAA_E_ARG, "saa_operator_implicit_set_state: t must be finite");
+  static const std::string name = "saa_operator_implicit_set_state";
+  if (const int rc = live_implicit(st, name)) return rc;
+  if (!std::isfinite(t)) return fail(SAA_E_ARG, name + ": t must be finite");
   HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
-  const hipError_t e = saa::opimp_set_state(st->impl, d_dev, v_dev, t);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_set_state: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opimp_set_state(st->impl, d_dev, v_dev, t), name);
 }
 
 int saa_operator_implicit_get_state(saa_operator_implicit *st, double *d_dev, double *v_dev, double *a_dev, double *t) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_get_state: null handle");
+  static const std::string name = "saa_operator_implicit_get_state";
+  if (const int rc = live_implicit(st, name)) return rc;
   HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
-  const hipError_t e = saa::opimp_get_state(st->impl, d_dev, v_dev, a_dev, t);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_get_state: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opimp_get_state(st->impl, d_dev, v_dev, a_dev, t), name);
 }
 
 int saa_operator_implicit_set_recorder(saa_operator_implicit *st, double *traj_dev, int64_t n_cols, int32_t save_every,
                                        int64_t next_step_index) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_set_recorder: null handle");
-  if (traj_dev && (n_cols <= 0 || save_every <= 0 || next_step_index < 0))
-    return fail(SAA_E_ARG, "saa_operator_implicit_set_recorder: bad argument");
+  static const std::string name = "saa_operator_implicit_set_recorder";
+  if (const int rc = live_implicit(st, name)) return rc;
+  if (traj_dev && (n_cols <= 0 || save_every <= 0 || next_step_index < 0)) return fail(SAA_E_ARG, name + ": bad argument");
   saa::opimp_set_recorder(st->impl, traj_dev, traj_dev ? n_cols : 0, traj_dev ? save_every : 1, traj_dev ? next_step_index : 0);
   return SAA_OK;
 }
 
-int saa_operator_implicit_set_option(saa_operator_implicit *st, const char *name, double value) {
-  if (!st || !st->impl || !name) return fail(SAA_E_ARG, "saa_operator_implicit_set_option: null handle or name");
-  if (!saa::opimp_set_option(st->impl, name, value))
-    return fail(SAA_E_ARG, std::string("saa_operator_implicit_set_option: unknown option or value: ") + name +
+int saa_operator_implicit_set_option(saa_operator_implicit *st, const char *option, double value) {
+  static const std::string name = "saa_operator_implicit_set_option";
+  if (!st || !st->impl || !option) return fail(SAA_E_ARG, name + ": null handle or name");
+  if (!saa::opimp_set_option(st->impl, option, value))
+    return fail(SAA_E_ARG, name + ": unknown option or value: " + option +
                                " (tol in (0, 1); max_newton, max_cg, check_every whole numbers >= 1)");
   return SAA_OK;
 }
 
 int saa_operator_implicit_set_dt(saa_operator_implicit *st, double dt) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_set_dt: null handle");
-  if (!(std::isfinite(dt) && dt > 0.0)) return fail(SAA_E_ARG, "saa_operator_implicit_set_dt: dt must be finite and > 0");
+  static const std::string name = "saa_operator_implicit_set_dt";
+  if (const int rc = live_implicit(st, name)) return rc;
+  if (const int rc = finite_positive(dt, "dt", name)) return rc;
   HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
-  const hipError_t e = saa::opimp_set_dt(st->impl, dt);
-  if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_set_dt: ") + hipGetErrorString(e));
-  return SAA_OK;
+  return hip_done(saa::opimp_set_dt(st->impl, dt), name);
 }
 
 int saa_operator_implicit_step(saa_operator_implicit *st, int32_t nsteps, saa_implicit_info *info) {
-  if (!st || !st->impl) return fail(SAA_E_ARG, "saa_operator_implicit_step: null handle");
-  if (nsteps < 0) return fail(SAA_E_ARG, "saa_operator_implicit_step: nsteps < 0");
-  if (!info) return fail(SAA_E_ARG, "saa_operator_implicit_step: null info");
+  static const std::string name = "saa_operator_implicit_step";
+  if (const int rc = live_implicit(st, name)) return rc;
+  if (nsteps < 0) return fail(SAA_E_ARG, name + ": nsteps < 0");
+  if (!info) return fail(SAA_E_ARG, name + ": null info");
   saa::OpImplicitInfo r;
   if (nsteps > 0) {
     HIP_TRY(hipSetDevice(saa::opimp_device(st->impl)));
-    const hipError_t e = saa::opimp_step(st->impl, nsteps, &r);
-    if (e != hipSuccess) return fail(SAA_E_HIP, std::string("saa_operator_implicit_step: ") + hipGetErrorString(e));
+    if (const int rc = hip_done(saa::opimp_step(st->impl, nsteps, &r), name)) return rc;
   }
   info->steps_done = r.steps_done;
   info->converged = r.converged;

@@ -32,19 +32,78 @@ from . import _lib
 from .solver import _dev
 
 
-class OperatorStepper:
-    """``saa_operator_stepper`` on a :class:`modal.ModalOperator` (borrowed: it must stay open while this object lives).
-    ``mass`` and ``load`` (the un-ramped ``f``): ``(n_dof,)`` float64, CUDA tensors or arrays, copied.  State
-    ``d0 = dn = 0``, ``tn = 0``.  ``material``: ``linear`` (the default: exactly the kernels of a stepper without a material),
-    ``svk`` or ``neo_hookean`` (:meth:`set_material`)."""
+class _StepperHandle:
+    """What :class:`OperatorStepper` and :class:`ImplicitStepper` share: the handle ``_h`` of a stepper on ``op`` and its life,
+    the vectors it takes and the recorder.  A subclass names its two C functions."""
 
-    def __init__(self, op, mass, load, dt, alpha, ramp=True, material="linear"):
+    _destroy = _set_recorder = None             # names of the ``saa_operator_*_destroy`` / ``_set_recorder`` of the subclass
+
+    def _open(self, op, dt):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.op = op
         self.n_dof = op.n_dof
         self.dt = float(dt)
         self._traj = None
+
+    def _vector(self, a):
+        import torch
+
+        t = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        t = t.to(device=self.op.torch_device, dtype=torch.float64).reshape(-1).contiguous()
+        if t.numel() != self.n_dof:
+            raise ValueError(f"expected {self.n_dof} values, got {t.numel()}")
+        return t
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+        self._traj = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def record(self, n_cols, save_every=1, next_step_index=0, out=None):
+        """Switches the recorder on and returns its ``(n_dof, n_cols)`` CUDA matrix (``saa_set_recorder``'s layout and
+        meaning: step index ``i`` fills column ``i / save_every`` when ``i % save_every == 0`` and the column exists; the
+        implicit stepper records its ``d``).  ``out``: a contiguous float64 CUDA tensor of at least ``n_dof * n_cols`` values
+        to record into instead of a new one.  ``n_cols = 0`` switches it off."""
+        import torch
+
+        set_recorder = getattr(self._lib, self._set_recorder)
+        if not n_cols:
+            _lib.check(set_recorder(self._h, None, 0, 1, 0))
+            self._traj = None
+            return None
+        if out is None:
+            out = torch.zeros((self.n_dof, int(n_cols)), dtype=torch.float64, device=self.op.torch_device)
+        elif out.numel() < self.n_dof * int(n_cols):
+            raise ValueError(f"the recorder needs {self.n_dof * int(n_cols)} values, got {out.numel()}")
+        _lib.check(set_recorder(self._h, _dev(out), int(n_cols), int(save_every), int(next_step_index)))
+        self._traj = out
+        return out.reshape(-1)[: self.n_dof * int(n_cols)].view(self.n_dof, int(n_cols))
+
+
+class OperatorStepper(_StepperHandle):
+    """``saa_operator_stepper`` on a :class:`modal.ModalOperator` (borrowed: it must stay open while this object lives).
+    ``mass`` and ``load`` (the un-ramped ``f``): ``(n_dof,)`` float64, CUDA tensors or arrays, copied.  State
+    ``d0 = dn = 0``, ``tn = 0``.  ``material``: ``linear`` (the default: exactly the kernels of a stepper without a material),
+    ``svk`` or ``neo_hookean`` (:meth:`set_material`)."""
+
+    _destroy, _set_recorder = "saa_operator_stepper_destroy", "saa_operator_stepper_set_recorder"
+
+    def __init__(self, op, mass, load, dt, alpha, ramp=True, material="linear"):
+        self._open(op, dt)
         self._iface = None
         self._energy = None
         self.n_shared = self.n_global_shared = 0
@@ -138,33 +197,9 @@ class OperatorStepper:
         _lib.check(self._lib.saa_operator_stepper_inverted(self._h, C.byref(count), C.byref(first)))
         return int(count.value), int(first.value)
 
-    def _vector(self, a):
-        import torch
-
-        t = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float64))
-        t = t.to(device=self.op.torch_device, dtype=torch.float64).reshape(-1).contiguous()
-        if t.numel() != self.n_dof:
-            raise ValueError(f"expected {self.n_dof} values, got {t.numel()}")
-        return t
-
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.saa_operator_stepper_destroy(self._h)
-            self._h = C.c_void_p()
-        self._traj = None
+        super().close()
         self._energy = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def step(self, n=1):
         _lib.check(self._lib.saa_operator_stepper_step(self._h, int(n)))
@@ -185,26 +220,6 @@ class OperatorStepper:
         a = None if d0 is None else self._vector(d0)
         b = None if dn is None else self._vector(dn)
         _lib.check(self._lib.saa_operator_stepper_set_state(self._h, _dev(a), _dev(b), float(tn)))
-
-    def record(self, n_cols, save_every=1, next_step_index=0, out=None):
-        """Switches the recorder on and returns its ``(n_dof, n_cols)`` CUDA matrix (``saa_set_recorder``'s layout and
-        meaning: step index ``i`` fills column ``i / save_every`` when ``i % save_every == 0`` and the column exists).
-        ``out``: a contiguous float64 CUDA tensor of at least ``n_dof * n_cols`` values to record into instead of a new
-        one.  ``n_cols = 0`` switches it off."""
-        import torch
-
-        if not n_cols:
-            _lib.check(self._lib.saa_operator_stepper_set_recorder(self._h, None, 0, 1, 0))
-            self._traj = None
-            return None
-        if out is None:
-            out = torch.zeros((self.n_dof, int(n_cols)), dtype=torch.float64, device=self.op.torch_device)
-        elif out.numel() < self.n_dof * int(n_cols):
-            raise ValueError(f"the recorder needs {self.n_dof * int(n_cols)} values, got {out.numel()}")
-        _lib.check(self._lib.saa_operator_stepper_set_recorder(self._h, _dev(out), int(n_cols), int(save_every),
-                                                               int(next_step_index)))
-        self._traj = out
-        return out.reshape(-1)[: self.n_dof * int(n_cols)].view(self.n_dof, int(n_cols))
 
     def record_energy(self, n_rows, every=1, next_step_index=0, owned=None):
         """Switches the energy balance on and returns its ``(n_rows, 5)`` CUDA matrix of zeros, columns ``T_{n+1/2},
@@ -284,7 +299,7 @@ class OperatorStepper:
         _lib.check(self._lib.saa_operator_stepper_halo_scatter(self._h, _dev(row)))
 
 
-class ImplicitStepper:
+class ImplicitStepper(_StepperHandle):
     """``saa_operator_implicit`` on a :class:`modal.ModalOperator` (borrowed: it must stay open while this object lives, and it
     serves one stepper at a time).  Newmark with ``beta = 1/4``, ``gamma = 1/2`` (the trapezoidal rule) on the system
     :class:`OperatorStepper` integrates explicitly - ``m a + alpha m v + f_int(d) = scale(t) f`` - so ``dt`` is chosen by the
@@ -296,38 +311,15 @@ class ImplicitStepper:
 
     REASONS = {0: "ok", 1: "max_newton", 2: "non_finite", 3: "inverted"}
 
+    _destroy, _set_recorder = "saa_operator_implicit_destroy", "saa_operator_implicit_set_recorder"
+
     def __init__(self, op, mass, load, dt, alpha, ramp=True, material="linear"):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        self.op = op
-        self.n_dof = op.n_dof
-        self.dt = float(dt)
-        self._traj = None
+        self._open(op, dt)
         self.material = str(material).replace("-", "_")
         m, f = self._vector(mass), self._vector(load)
         _lib.check(self._lib.saa_operator_implicit_create(op._h, _dev(m), _dev(f), float(dt), float(alpha), 1 if ramp else 0,
                                                           _lib.material_id(material), C.byref(self._h)))
         self.steps_done = 0
-
-    _vector = OperatorStepper._vector
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.saa_operator_implicit_destroy(self._h)
-            self._h = C.c_void_p()
-        self._traj = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def step(self, n=1):
         """Up to ``n`` steps.  Returns ``steps_done``, ``converged``, ``reason`` (0 ok, 1 ``max_newton`` reached, 2 a residual
@@ -357,24 +349,6 @@ class ImplicitStepper:
         a = None if d is None else self._vector(d)
         b = None if v is None else self._vector(v)
         _lib.check(self._lib.saa_operator_implicit_set_state(self._h, _dev(a), _dev(b), float(t)))
-
-    def record(self, n_cols, save_every=1, next_step_index=0, out=None):
-        """The recorder of :meth:`OperatorStepper.record`, same layout and rule: the ``d`` of step index ``i`` fills column
-        ``i / save_every`` when ``i % save_every == 0`` and the column exists.  ``n_cols = 0`` switches it off."""
-        import torch
-
-        if not n_cols:
-            _lib.check(self._lib.saa_operator_implicit_set_recorder(self._h, None, 0, 1, 0))
-            self._traj = None
-            return None
-        if out is None:
-            out = torch.zeros((self.n_dof, int(n_cols)), dtype=torch.float64, device=self.op.torch_device)
-        elif out.numel() < self.n_dof * int(n_cols):
-            raise ValueError(f"the recorder needs {self.n_dof * int(n_cols)} values, got {out.numel()}")
-        _lib.check(self._lib.saa_operator_implicit_set_recorder(self._h, _dev(out), int(n_cols), int(save_every),
-                                                                int(next_step_index)))
-        self._traj = out
-        return out.reshape(-1)[: self.n_dof * int(n_cols)].view(self.n_dof, int(n_cols))
 
     def set_dt(self, dt):
         """A new step from the next step on: the scheme is one-step, only the shift and the preconditioner are recomputed."""
