@@ -13,7 +13,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("SAA_LIB_PATH") or os.path.join(_HERE, "libsaa_hip.so")  # override: experiments only
-#: diagnostic build (-DSAA_DIAGNOSTICS: ablated step kernels, in-kernel stamps, saa_debug_* exports) used by tools/
+#: diagnostic build (-DSAA_DIAGNOSTICS: experiment switches, saa_debug_* exports; the same step kernels as the product) used by tools/
 #: only; built on request (``build_library(diag=True)``), loaded through SAA_LIB_PATH, never by the package itself
 DIAG_LIB_PATH = os.path.join(_HERE, "libsaa_hip_diag.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "saa_hip.h")

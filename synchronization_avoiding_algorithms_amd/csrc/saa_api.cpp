@@ -815,6 +815,28 @@ int check_launch() {
   return SAA_OK;
 }
 
+// Milliseconds that what `call` enqueues on `stream` takes, between two events that are destroyed on every path.
+// Returns the first HIP failure of the measurement itself, else what `call` returned.
+template <typename Call>
+int time_on_stream(hipStream_t stream, double *elapsed_ms, Call call) {
+  hipEvent_t a = nullptr, b = nullptr;
+  const int rc = [&]() -> int {
+    HIP_TRY(hipEventCreate(&a));
+    HIP_TRY(hipEventCreate(&b));
+    HIP_TRY(hipEventRecord(a, stream));
+    const int rc_call = call();
+    HIP_TRY(hipEventRecord(b, stream));
+    HIP_TRY(hipEventSynchronize(b));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, a, b));
+    *elapsed_ms = ms;
+    return rc_call;
+  }();
+  if (a) (void)hipEventDestroy(a);
+  if (b) (void)hipEventDestroy(b);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1833,19 +1855,7 @@ int saa_synchronize(saa_solver *s) {
 int saa_time_steps(saa_solver *s, int32_t nsteps, double *elapsed_ms) {
   if (!s || !elapsed_ms || nsteps < 0) return fail(SAA_E_ARG, "saa_time_steps: bad argument");
   HIP_TRY(hipSetDevice(s->device));
-  hipEvent_t a, b;
-  HIP_TRY(hipEventCreate(&a));
-  HIP_TRY(hipEventCreate(&b));
-  HIP_TRY(hipEventRecord(a, s->stream));
-  int rc = saa_step(s, nsteps);
-  HIP_TRY(hipEventRecord(b, s->stream));
-  HIP_TRY(hipEventSynchronize(b));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, a, b));
-  *elapsed_ms = ms;
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  return rc;
+  return time_on_stream(s->stream, elapsed_ms, [&] { return saa_step(s, nsteps); });
 }
 
 // ---- partition bookkeeping of one rank (saa_topology.hip) ------------------------------------------------------
@@ -2739,36 +2749,6 @@ int saa_train_stats(int32_t device, int64_t n, const float *out_dev, const float
   return SAA_OK;
 }
 
-#ifdef SAA_DIAGNOSTICS
-// Diagnostic build only (libsaa_hip_diag.so, -DSAA_DIAGNOSTICS; never in the product library): time `nsteps`
-// launches of an ablated step kernel (state is not rotated; outputs are meaningless).  Used by tools/ablate.py only.
-int saa_debug_time_ablated(saa_solver *s, int32_t variant, int32_t nsteps, double *elapsed_ms) {
-  if (!s || !elapsed_ms) return fail(SAA_E_ARG, "saa_debug_time_ablated: bad argument");
-  HIP_TRY(hipSetDevice(s->device));
-  hipEvent_t a, b;
-  HIP_TRY(hipEventCreate(&a));
-  HIP_TRY(hipEventCreate(&b));
-  // variant 8 writes 12 stamps per wave into scratch[0] (needs 12*8*waves bytes <= 24*n_nodes: checked)
-  if (int rc = ensure_scratch(s, 1)) return rc;
-  if (variant == 8 && 12ull * s->mesh.n_blocks * (s->threads / 64) > 3ull * s->plan.n_nodes)
-    return fail(SAA_E_ARG, "saa_debug_time_ablated: scratch too small for stamps");
-  s->set_ramp();
-  HIP_TRY(hipEventRecord(a, s->stream));
-  for (int32_t k = 0; k < nsteps; ++k)
-    saa::launch_fused_step_ablated(variant, s->mesh, s->threads, s->lds_bytes, s->stream, s->dbuf[s->i0].p,
-                                   s->dbuf[s->in_].p, s->dbuf[s->i1].p, s->consts, s->scratch[0].p);
-  HIP_TRY(hipEventRecord(b, s->stream));
-  HIP_TRY(hipEventSynchronize(b));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, a, b));
-  *elapsed_ms = ms;
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  return check_launch();
-}
-
-#endif  // SAA_DIAGNOSTICS
-
 int saa_peer_attach_loopback(saa_solver *s, int32_t world) {
   if (!s || world < 2 || world > 8 || s->n_shared <= 0) return fail(SAA_E_ARG, "saa_peer_attach_loopback: bad argument");
   uint8_t handle[64];
@@ -2784,21 +2764,12 @@ int saa_peer_attach_loopback(saa_solver *s, int32_t world) {
 }
 
 #ifdef SAA_DIAGNOSTICS
+// Diagnostic build only (libsaa_hip_diag.so, -DSAA_DIAGNOSTICS; never in the product library), tools/peer_loopback.py:
+// saa_time_steps for steps with the peer exchange.
 int saa_debug_time_peer(saa_solver *s, int32_t nsteps, double *elapsed_ms) {
   if (!s || !elapsed_ms || nsteps < 0) return fail(SAA_E_ARG, "saa_debug_time_peer: bad argument");
   HIP_TRY(hipSetDevice(s->device));
-  hipEvent_t a, b;
-  HIP_TRY(hipEventCreate(&a));
-  HIP_TRY(hipEventCreate(&b));
-  HIP_TRY(hipEventRecord(a, s->stream));
-  int rc = saa_step_peer(s, nsteps, nullptr, 0);
-  HIP_TRY(hipEventRecord(b, s->stream));
-  HIP_TRY(hipEventSynchronize(b));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, a, b));
-  *elapsed_ms = ms;
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
+  const int rc = time_on_stream(s->stream, elapsed_ms, [&] { return saa_step_peer(s, nsteps, nullptr, 0); });
   return rc ? rc : check_peer_error(s);
 }
 
@@ -2818,14 +2789,6 @@ int saa_debug_counters(saa_solver *s, uint32_t *peer_seq, uint32_t *ps_steps, in
 int saa_debug_set_stamp_buffer(saa_solver *s, double *buf_dev) {
   if (!s) return fail(SAA_E_ARG, "saa_debug_set_stamp_buffer: null handle");
   s->ps_dbg = buf_dev;
-  return SAA_OK;
-}
-
-// Diagnostic: copies the stamps of the last variant-8 launch to the host (n = 12 * blocks * waves values).
-int saa_debug_read_stamps(saa_solver *s, unsigned long long *out, int64_t n) {
-  if (!s || !out || !s->scratch[0].p) return fail(SAA_E_ARG, "saa_debug_read_stamps: bad argument");
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(out, s->scratch[0].p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return SAA_OK;
 }
 #endif  // SAA_DIAGNOSTICS

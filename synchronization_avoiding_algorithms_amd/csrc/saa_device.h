@@ -160,10 +160,6 @@ void launch_fused_step(const DeviceMesh &m, int threads, int lds_bytes, hipStrea
                        const double *dn, double *d1, double *iface, const double *table_row, double *hist_row,
                        const StepConsts &k, const double *tn_dev = nullptr);
 void launch_set_scalar(hipStream_t st, double *p, double v);
-#ifdef SAA_DIAGNOSTICS
-void launch_fused_step_ablated(int variant, const DeviceMesh &m, int threads, int lds_bytes, hipStream_t st,
-                               const double *d0, const double *dn, double *d1, const StepConsts &k, double *dbg);
-#endif
 void launch_force_only(const DeviceMesh &m, int threads, int lds_bytes, hipStream_t st, const double *d,
                        double *f);
 // tn_in / tn_out (nullable pair): device-side clock of graph-replayed steps - ramp from *tn_in, *tn_out = *tn_in + dt

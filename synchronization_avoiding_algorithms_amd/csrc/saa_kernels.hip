@@ -21,9 +21,7 @@
 // gfx950 anyway).  64-wide waves; cross-workgroup data flows through kernel boundaries (cross-RANK data of the
 // PEER variant through self-validating entries in fine-grained memory).
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include <cstddef>
-#include <cstdlib>
 #include <stdint.h>
 
 #include "saa_device.h"
@@ -187,101 +185,52 @@ __device__ __forceinline__ Vec3 neg_sum3(const Vec3 &a, const Vec3 &b, const Vec
   return {-(a.x + b.x + c.x), -(a.y + b.y + c.y), -(a.z + b.z + c.z)};
 }
 
-// In-kernel stamp (diagnostic build ABLATE == 8 only): shader clock after all outstanding LDS work has drained.
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
 struct NoHook {
   __device__ __forceinline__ void operator()() const {}
 };
+// Where the five force vectors of an item go: `out(slot, node, f)` with slot a = 0, p = 1, q = 2, r = 3, b = 4 and the
+// block-local node index.  ToLds adds f to the LDS accumulator of an owned node (fused and resident kernels).
+template <bool ALL_OWNED>
+struct ToLds {
+  double *acc;
+  int n_owned;
+  __device__ __forceinline__ void operator()(int, unsigned n, const Vec3 &f) const { flush<ALL_OWNED>(acc, n, n_owned, f); }
+};
+// The item arithmetic of every step kernel, atomic or deterministic.  The order of the operations and of the outputs
+// (a, [b], p, q, r) is part of the kernels' schedule of LDS reads and atomics: keep it.
 // `mid` runs once per call, half-way through the item (after tet A): the resident kernel issues its halo loads there.
-template <int ABLATE, typename Hook = NoHook, bool ALL_OWNED = false>
-__device__ __forceinline__ void item_forces(const uint2 w, const double *rec, double *acc, int n_owned,
-                                            double lam6, double mu6, int tid, double &sink, unsigned long long *T = nullptr,
+template <typename Out, typename Hook = NoHook>
+__device__ __forceinline__ void item_forces(const uint2 w, const double *rec, double lam6, double mu6, Out out,
                                             Hook mid = Hook()) {
-  Item it = unpack(w);
+  const Item it = unpack(w);
   if (it.null) {  // idle lane left by the LDS packing (saa_plan.cpp)
     mid();
     return;
   }
-  if (ABLATE == 2) {  // every lane reads its own fixed records: no index-dependent LDS traffic
-    it.a = tid & 63; it.p = it.a + 1; it.q = it.a + 2; it.r = it.a + 3; it.b = it.a + 4;
-  }
-  Vec3 fa, fp, fq, fr, fb = {0, 0, 0};
-  if (ABLATE == 6) {  // VALU only: operands from registers, results to a register sink
-    const double t = 1.0 + 1e-3 * tid + sink;
-    Vec3 g1, g2, g3;
-    tet_forces({t, 0.1, 0.2}, {1.1 * t, 0.3, 0.1}, {0.2, t, 0.3}, {0.1, 0.2, 1.3 * t}, {t, t, 0}, {0, t, t}, {t, 0, t},
-               {t, t, t}, lam6, mu6, fa, fr, fq);
-    tet_forces({t, 0.1, 0.2}, {1.2 * t, 0.3, 0.1}, {0.1, 0.2, 1.3 * t}, {0.2, t, 0.3}, {t, t, 0}, {0, 2 * t, t}, {t, t, t},
-               {t, 0, t}, lam6, mu6, g1, g2, g3);
-    sink += fa.x + fa.y + fa.z + fr.x + fr.y + fr.z + fq.x + fq.y + fq.z + g1.x + g1.y + g1.z + g2.x + g2.y + g2.z +
-            g3.x + g3.y + g3.z;
-    mid();
-    return;
-  }
-  unsigned long long t0 = 0, t1 = 0;
-  if (ABLATE == 8) t0 = stamp();
+  Vec3 fa, fq, fr, fb = {0, 0, 0};
   const Rec rp = load_rec(rec, it.p), rq = load_rec(rec, it.q), rr = load_rec(rec, it.r);
   PairShared pg;
   {
     const Rec ra = load_rec(rec, it.a);
-    if (ABLATE == 8) {
-      t1 = stamp();
-      T[0] += t1 - t0;  // 12 reads: issue + arrival
-    }
-    if (ABLATE == 7) {  // LDS only: reads and atomics without the element arithmetic
-      fa = add3(ra.x, ra.u); fp = add3(rp.x, rp.u); fq = add3(rq.x, rq.u); fr = add3(rr.x, rr.u);
-    } else {
-      // A as (p; a, r, q): forces on a, r, q; p gets minus their sum
-      pg = pair_shared(rp.x, rq.x, rr.x, rp.u, rq.u, rr.u);
-      tet_a_forces(pg, rp.x, ra.x, rp.u, ra.u, lam6, mu6, fa, fr, fq);
-    }
+    // A as (p; a, r, q): forces on a, r, q; p gets minus their sum
+    pg = pair_shared(rp.x, rq.x, rr.x, rp.u, rq.u, rr.u);
+    tet_a_forces(pg, rp.x, ra.x, rp.u, ra.u, lam6, mu6, fa, fr, fq);
   }
-  if (ABLATE == 8) {
-    t0 = stamp();
-    T[1] += t0 - t1;  // VALU of tet A
-  }
-  if (ABLATE != 1) flush<ALL_OWNED>(acc, it.a, n_owned, fa);
-  else sink += fa.x + fa.y + fa.z;
+  out(0, it.a, fa);
   mid();  // (the resident kernel's halo requests: before tet A 8.43, here 7.84, behind tet B 8.04 us per step - round 3)
   if (it.pair) {
     const Rec rb = load_rec(rec, it.b);
-    if (ABLATE == 8) {
-      t1 = stamp();
-      T[2] += t1 - t0;  // 3 atomics + 3 reads round trip
-    }
-    if (ABLATE == 7) {
-      fb = add3(rb.x, rb.u);
-    } else {
-      // B as (p; b, q, r)
-      Vec3 gq, gr;
-      tet_b_forces(pg, rp.x, rb.x, rp.u, rb.u, lam6, mu6, fb, gq, gr);
-      fq = add3(fq, gq);
-      fr = add3(fr, gr);
-    }
-    if (ABLATE == 8) {
-      t0 = stamp();
-      T[3] += t0 - t1;  // VALU of tet B
-    }
-    if (ABLATE != 1) flush<ALL_OWNED>(acc, it.b, n_owned, fb);
-    else sink += fb.x + fb.y + fb.z;
+    // B as (p; b, q, r)
+    Vec3 gq, gr;
+    tet_b_forces(pg, rp.x, rb.x, rp.u, rb.u, lam6, mu6, fb, gq, gr);
+    fq = add3(fq, gq);
+    fr = add3(fr, gr);
+    out(4, it.b, fb);
   }
   // the forces of an element sum to zero, those of the pair too: p gets minus the sum of the other four (fb = 0 without B)
-  if (ABLATE != 7) fp = neg_sum3(add3(fa, fb), fq, fr);
-  if (ABLATE == 1) {
-    sink += fp.x + fp.y + fp.z + fq.x + fq.y + fq.z + fr.x + fr.y + fr.z;
-    return;
-  }
-  flush<ALL_OWNED>(acc, it.p, n_owned, fp);
-  flush<ALL_OWNED>(acc, it.q, n_owned, fq);
-  flush<ALL_OWNED>(acc, it.r, n_owned, fr);
-  if (ABLATE == 8) T[4] += stamp() - t0;  // remaining atomics: issue + drain
+  out(1, it.p, neg_sum3(add3(fa, fb), fq, fr));
+  out(2, it.q, fq);
+  out(3, it.r, fr);
 }
 
 // Per-thread prefetch depth (dofs): the update operands of the first kPreOwn*blockDim owned dofs and
@@ -362,13 +311,13 @@ __device__ __forceinline__ double peer_collect(const PeerMap *pm, const PeerRecv
   return f;
 }
 
-// ABLATE (diagnostic builds only, never launched by the product path): 1 = no LDS atomics,
-// 2 = no indexed LDS reads, 3 = no staging loads, 4 = no update phase, 5 = no element phase.
-// 10 = 3 and 4 together: the element phase alone with its real LDS traffic (what a workgroup whose memory phases were
-// hidden completely would still take).
+// One time step in one launch (phases 0-6 below; see the head of this file).
+// FORCE_ONLY: write f_int of the owned dofs into `out` instead of updating them.
 // PEER: synchronised step with the direct peer exchange - shared nodes are pushed to / collected from the
 // neighbour ranks inside this kernel (one launch per step, no collective).
-template <bool FORCE_ONLY, int ABLATE = 0, bool PEER = false>
+// (What each phase costs was measured with variants of this kernel that left one phase out and with in-kernel stamps:
+// profiles/EXPERIMENTS_r01_r03.md, profiles/r04_fused_8Mtets_ablation.txt.)
+template <bool FORCE_ONLY, bool PEER = false>
 __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const double *__restrict__ d0, const double *__restrict__ dn,
                                   double *__restrict__ out, double *__restrict__ iface,
                                   const double *__restrict__ table_row, double *__restrict__ hist_row, StepConsts k,
@@ -380,8 +329,7 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
     const double t = *tn_dev;
     k.ramp = t <= 1 ? t : 1.0;
   }
-  // (ABLATE == 9: eight steps' worth of blocks in one launch - what the launch boundary and its tail cost)
-  const int pblock = plan_block(ABLATE == 9 ? blockIdx.x % m.n_blocks : blockIdx.x, m.n_blocks);
+  const int pblock = plan_block(blockIdx.x, m.n_blocks);
   const BlockDesc bd = m.blocks[pblock];
   const int tid = threadIdx.x, nt = blockDim.x;
   double *rec = lds;                       // [n_owned + n_halo][6]: x y z ux uy uz
@@ -391,8 +339,6 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
   const int32_t *hid = m.halo_ids + bd.halo_off;
 
   // ---- 0. interior connectivity and halo ids first (see kPreConn) ------------------------------
-  unsigned long long T[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tk = 0;
-  if (ABLATE == 8) tk = stamp();
   const uint2 *conn = m.conn + bd.elem_off;
   uint2 cpre[kPreConn];
 #pragma unroll
@@ -414,8 +360,8 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
     const double *uo = d0 + base;
     for (int i = tid; i < n_own3; i += nt) {
       const int n = i / 3, c = i - 3 * n;
-      rec[6 * n + c] = (ABLATE == 3 || ABLATE == 10) ? 1.0 * i : xo[i];
-      rec[6 * n + 3 + c] = (ABLATE == 3 || ABLATE == 10) ? 1e-3 * i : uo[i];
+      rec[6 * n + c] = xo[i];
+      rec[6 * n + 3 + c] = uo[i];
       acc[3 * n + c] = 0.0;
     }
   }
@@ -424,8 +370,8 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
   double hx[kPreHalo], hu[kPreHalo];
 #pragma unroll
   for (int j = 0; j < kPreHalo; ++j) {
-    hx[j] = (ABLATE == 3 || ABLATE == 10) ? 1.0 * tid : m.xyz[hg[j]];
-    hu[j] = (ABLATE == 3 || ABLATE == 10) ? 1e-3 * tid : d0[hg[j]];
+    hx[j] = m.xyz[hg[j]];
+    hu[j] = d0[hg[j]];
   }
   double pm_[kPreOwn], pf[kPreOwn], pn[kPreOwn];
   int32_t ptag[kPreOwn];
@@ -433,26 +379,20 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
 #pragma unroll
     for (int j = 0; j < kPreOwn; ++j) {
       const int i = min(tid + j * nt, n_own3 - 1);
-      pm_[j] = (ABLATE == 4 || ABLATE == 10) ? 1.0 : (m.mass_node ? m.mass_node[bd.node_start + i / 3] : m.mass[base + i]);
-      pf[j] = (ABLATE == 4 || ABLATE == 10) ? 0.0 : (m.fext_yz ? (i % 3 == 0 ? 0.0 : m.fext_yz[bd.node_start + i / 3]) : m.fext[base + i]);
-      pn[j] = (ABLATE == 4 || ABLATE == 10) ? 0.0 : dn[base + i];
-      ptag[j] = (ABLATE == 4 || ABLATE == 10) ? 0 : m.tag[bd.node_start + i / 3];
+      pm_[j] = m.mass_node ? m.mass_node[bd.node_start + i / 3] : m.mass[base + i];
+      pf[j] = m.fext_yz ? (i % 3 == 0 ? 0.0 : m.fext_yz[bd.node_start + i / 3]) : m.fext[base + i];
+      pn[j] = dn[base + i];
+      ptag[j] = m.tag[bd.node_start + i / 3];
     }
   }
   lds_barrier();
-  if (ABLATE == 8) {
-    const unsigned long long t = stamp();
-    T[6] = t - tk;  // staging up to and including the first barrier
-    tk = t;
-  }
 
   // ---- 3. interior elements (all four nodes owned) --------------------------------------------
-  double sink = 0.0;
-  if (ABLATE != 5) {
+  {
+    const ToLds<true> to_owned = {acc, bd.n_owned};
 #pragma unroll
     for (int j = 0; j < kPreConn; ++j)
-      if (tid + j * nt < bd.n_interior)
-        item_forces<ABLATE, NoHook, true>(cpre[j], rec, acc, bd.n_owned, m.lambda6, m.mu6, tid, sink, T);
+      if (tid + j * nt < bd.n_interior) item_forces(cpre[j], rec, m.lambda6, m.mu6, to_owned);
     // (rare) further interior sweeps, software-pipelined: the next connectivity entry is in flight while
     // the current element computes - a dependent global load per sweep would expose its L2 latency
     if (tid + kPreConn * nt < bd.n_interior) {
@@ -460,15 +400,10 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
       uint2 cur = conn[tid + kPreConn * nt];
       for (int e = tid + kPreConn * nt; e < bd.n_interior; e += nt) {
         const uint2 nxt = conn[min(e + nt, last)];
-        item_forces<ABLATE, NoHook, true>(cur, rec, acc, bd.n_owned, m.lambda6, m.mu6, tid, sink, T);
+        item_forces(cur, rec, m.lambda6, m.mu6, to_owned);
         cur = nxt;
       }
     }
-  }
-  if (ABLATE == 8) {
-    const unsigned long long t = stamp();
-    T[7] = t - tk;  // interior loop
-    tk = t;
   }
   // first boundary sweep's connectivity: issued now, consumed after the halo records are in LDS
   // Wave balance: a wave's items are a serial chain, so the workgroup is as slow as its busiest wave.
@@ -504,7 +439,7 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
     if (iface != nullptr && (tag & kTagShared)) iface[3 * (int64_t)(tag >> kTagSlotShift) + c] = f;
     double v = cd_update_dof(f, fpre, mass, rec[6 * n + 3 + c], dnv, k);
     if (tag & (1 << c)) v = 0.0;  // d1[Local_Dirichlet] = 0   (Dynamic_solver.py:20)
-    if (ABLATE != 8 && table_row != nullptr && (tag & kTagShared)) {
+    if (table_row != nullptr && (tag & kTagShared)) {
       // predicted phase: d1[loc_dof_shared] = prediction, recorded as history (Online_predictor.py:298,301)
       const int64_t j = 3 * (int64_t)m.slot_sidx[tag >> kTagSlotShift] + c;
       v = table_row[j];
@@ -512,36 +447,17 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
     }
     out[base + i] = v;
   };
-  if (ABLATE == 8) {
-    const unsigned long long t = stamp();
-    T[8] = t - tk;  // halo records to LDS + barrier
-    tk = t;
-  }
   // ---- 5. boundary elements (at least one halo node) ----------------------------------------------
-  if (ABLATE != 5) {
+  {
+    const ToLds<false> to_lds = {acc, bd.n_owned};
     const int last = bd.n_elem - 1;
     for (int e = e_b0; e < bd.n_elem; e += nt) {
       const uint2 nxt = conn[min(e + nt, last)];
-      item_forces<ABLATE>(bcur, rec, acc, bd.n_owned, m.lambda6, m.mu6, tid, sink, T);
+      item_forces(bcur, rec, m.lambda6, m.mu6, to_lds);
       bcur = nxt;
     }
   }
-  if ((ABLATE == 1 || ABLATE == 6) && sink == 12345.678) acc[0] = sink;
-  if (ABLATE == 8) {
-    const unsigned long long t = stamp();
-    T[9] = t - tk;  // boundary loop
-    tk = t;
-  }
   lds_barrier();
-  if (ABLATE == 8) {
-    const unsigned long long t = stamp();
-    T[10] = t - tk;  // waiting for the slowest wave
-    tk = t;
-  }
-  if (ABLATE == 4 || ABLATE == 10) {
-    if (tid == 0) out[base] = acc[0];
-    return;
-  }
 
   // ---- 6. owned dofs: write f_int, or update --------------------------------------------------------
   if (FORCE_ONLY) {
@@ -590,14 +506,6 @@ __global__ void __launch_bounds__(SAA_LB) fused_step_kernel(DeviceMesh m, const 
       if (hist_row != nullptr) hist_row[3 * (int64_t)r.sidx + c] = v;  // Online_predictor.py:260
     }
   }
-  if (ABLATE == 8) {  // stamps leave through a buffer of their own (passed in place of the history row)
-    T[11] = stamp() - tk;  // update phase
-    if ((tid & 63) == 0) {
-      unsigned long long *dbg = reinterpret_cast<unsigned long long *>(hist_row) +
-                                12 * ((size_t)blockIdx.x * (nt >> 6) + (tid >> 6));
-      for (int j = 0; j < 12; ++j) dbg[j] = T[j];
-    }
-  }
 }
 
 template __global__ void fused_step_kernel<false>(DeviceMesh, const double *, const double *, double *, double *,
@@ -606,9 +514,9 @@ template __global__ void fused_step_kernel<false>(DeviceMesh, const double *, co
 template __global__ void fused_step_kernel<true>(DeviceMesh, const double *, const double *, double *, double *,
                                                   const double *, double *, StepConsts, const PeerMap *, unsigned,
                                                   const double *);
-template __global__ void fused_step_kernel<false, 0, true>(DeviceMesh, const double *, const double *, double *, double *,
-                                                            const double *, double *, StepConsts, const PeerMap *, unsigned,
-                                                            const double *);
+template __global__ void fused_step_kernel<false, true>(DeviceMesh, const double *, const double *, double *, double *,
+                                                         const double *, double *, StepConsts, const PeerMap *, unsigned,
+                                                         const double *);
 
 // Attach-time proof of the peer path: one exchange of known values (own[3*q+c], node-sorted order) -> the sums
 // in the caller's shared order.
@@ -666,6 +574,16 @@ __host__ __device__ inline int persist_off_dn(int max_local, int max_owned) { re
 #define SAA_PERSIST_PRE 2
 #endif
 constexpr int kPH = SAA_PERSIST_PRE;  // stamped halo entries per thread in flight during the first round
+#ifdef SAA_PERSIST_STAMPS
+// In-kernel stamp (PSTAMP below, tools/persist_stamps.py): shader clock after all outstanding LDS work has drained.
+__device__ __forceinline__ unsigned long long stamp() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#endif
 // PREDICT: the predicted phase (table / history rows); a separate instantiation keeps its pointers out of the plain
 // kernel's scalar registers.  The argument block is read field by field where it is needed for the same reason.
 // PEER: synchronised steps with the direct peer exchange (shared nodes pushed to / collected from the neighbour
@@ -837,7 +755,6 @@ __global__ void __launch_bounds__(SAA_LB) persistent_steps_kernel(DeviceMesh m, 
   const int n_ir = bd.n_interior - n_pre, n_ir_pad = (n_ir + 63) & ~63;  // interior items left for the second phase
   const int n_post = n_ir_pad + (bd.n_elem - bd.n_interior);
   double tn = a.tn0;
-  double sink = 0.0;
   // The work items of a lane are the same in every step of the launch: the one of the first round and the first two of
   // the second phase stay in registers (two each) instead of being read from LDS again - not for the read's bandwidth
   // but for its round trip, which every wave sat out right behind a barrier, twice per step, before it could request a
@@ -898,7 +815,7 @@ __global__ void __launch_bounds__(SAA_LB) persistent_steps_kernel(DeviceMesh m, 
     // (interior items: the variant of the item code without ownership tests; a lane without an item of this round holds
     // the null item, which only runs the hook)
     asm volatile("" : "+v"(w_first.x), "+v"(w_first.y), "+v"(w_post[0].x), "+v"(w_post[0].y), "+v"(w_post[1].x), "+v"(w_post[1].y));
-    item_forces<0, decltype(fetch), true>(w_first, rec, acc, bd.n_owned, m.lambda6, m.mu6, tid, sink, nullptr, fetch);
+    item_forces(w_first, rec, m.lambda6, m.mu6, ToLds<true>{acc, bd.n_owned}, fetch);
     PSTAMP(0)
     PSTAMP(1)
     // ---- 2. halo displacements -> LDS (an entry still carrying an older stamp is simply read again) ------
@@ -946,11 +863,11 @@ __global__ void __launch_bounds__(SAA_LB) persistent_steps_kernel(DeviceMesh m, 
     //         (the ownership-test-free variant of the interior items, which the first round and the fused kernel use,
     //         was measured here too, behind a wave-uniform branch: 8.60-8.67 against 8.43 us/step in round 2, 8.06 against
     //         8.03 in round 3 with 104 instead of 112 registers in use)
-    if (tid < n_post) item_forces<0>(w_post[0], rec, acc, bd.n_owned, m.lambda6, m.mu6, tid, sink);
-    if (tid + nt < n_post) item_forces<0>(w_post[1], rec, acc, bd.n_owned, m.lambda6, m.mu6, tid, sink);
+    if (tid < n_post) item_forces(w_post[0], rec, m.lambda6, m.mu6, ToLds<false>{acc, bd.n_owned});
+    if (tid + nt < n_post) item_forces(w_post[1], rec, m.lambda6, m.mu6, ToLds<false>{acc, bd.n_owned});
     for (int p = tid + 2 * nt; p < n_post; p += nt) {  // (blocks with more than two sweeps in this phase)
       const int e = p < n_ir_pad ? (p < n_ir ? n_pre + p : -1) : bd.n_interior + (p - n_ir_pad);
-      if (e >= 0) item_forces<0>(connl[e], rec, acc, bd.n_owned, m.lambda6, m.mu6, tid, sink);
+      if (e >= 0) item_forces(connl[e], rec, m.lambda6, m.mu6, ToLds<false>{acc, bd.n_owned});
     }
     PSTAMP(4)
     // ---- 5. update of the owned dofs: LDS operands; the new value leaves as a plain double (state) and as a
@@ -1098,7 +1015,6 @@ __global__ void __launch_bounds__(SAA_LB) persistent_steps_kernel(DeviceMesh m, 
     for (int j = 0; j < 8; ++j) dbg[j] = T[j];
   }
 #endif
-  if (sink == 12345.678) acc[0] = sink;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1129,24 +1045,15 @@ __global__ void __launch_bounds__(SAA_LB) det_items_kernel(DeviceMesh m, const d
   }
   __syncthreads();
   for (int e = tid; e < bd.n_elem; e += nt) {
-    const Item it = unpack(m.conn[bd.elem_off + e]);
-    if (it.null) continue;
-    // exactly the evaluation order of item_forces: A as (p; a, r, q), B as (p; b, q, r), face forces summed in registers
-    const Rec rp = load_rec(rec, it.p), rq = load_rec(rec, it.q), rr = load_rec(rec, it.r), ra = load_rec(rec, it.a);
-    Vec3 fa, fp, fq, fr, fb = {0, 0, 0};
-    const PairShared pg = pair_shared(rp.x, rq.x, rr.x, rp.u, rq.u, rr.u);
-    tet_a_forces(pg, rp.x, ra.x, rp.u, ra.u, m.lambda6, m.mu6, fa, fr, fq);
-    if (it.pair) {
-      const Rec rb = load_rec(rec, it.b);
-      Vec3 gq, gr;
-      tet_b_forces(pg, rp.x, rb.x, rp.u, rb.u, m.lambda6, m.mu6, fb, gq, gr);
-      fq = add3(fq, gq);
-      fr = add3(fr, gr);
-    }
-    fp = neg_sum3(add3(fa, fb), fq, fr);
+    const uint2 w = m.conn[bd.elem_off + e];
+    if (unpack(w).null) continue;
+    // the five vectors by slot, collected in registers and stored as ONE contiguous run of 120 bytes: stored from the
+    // functor, slot by slot where they become ready, the step took 77.8 instead of 75.3 us at 1M tets
+    Vec3 f[5] = {};  // (slot 4 of a single item: zero; saa_set_deterministic lists four slots for it)
+    item_forces(w, rec, m.lambda6, m.mu6, [&f](int slot, unsigned, const Vec3 &v) { f[slot] = v; });
     double *o = item_force + 15 * (int64_t)(bd.elem_off + e);
-    o[0] = fa.x; o[1] = fa.y; o[2] = fa.z; o[3] = fp.x; o[4] = fp.y; o[5] = fp.z; o[6] = fq.x; o[7] = fq.y; o[8] = fq.z;
-    o[9] = fr.x; o[10] = fr.y; o[11] = fr.z; o[12] = fb.x; o[13] = fb.y; o[14] = fb.z;
+    o[0] = f[0].x; o[1] = f[0].y; o[2] = f[0].z; o[3] = f[1].x; o[4] = f[1].y; o[5] = f[1].z; o[6] = f[2].x; o[7] = f[2].y;
+    o[8] = f[2].z; o[9] = f[3].x; o[10] = f[3].y; o[11] = f[3].z; o[12] = f[4].x; o[13] = f[4].y; o[14] = f[4].z;
   }
 }
 
@@ -1282,7 +1189,7 @@ hipError_t configure_kernels(int lds_bytes) {
   e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_step_kernel<true>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_step_kernel<false, 0, true>),
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_step_kernel<false, true>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
 }
 
@@ -1317,7 +1224,7 @@ void launch_det_step(const DeviceMesh &m, const DetLists &det, int threads, int 
 void launch_fused_step_peer(const DeviceMesh &m, int threads, int lds_bytes, hipStream_t st, const double *d0,
                             const double *dn, double *d1, double *hist_row, const StepConsts &k,
                             const PeerMap *pm_dev, unsigned seq) {
-  hipLaunchKernelGGL((fused_step_kernel<false, 0, true>), dim3(m.n_blocks), dim3(threads), lds_bytes, st, m, d0, dn,
+  hipLaunchKernelGGL((fused_step_kernel<false, true>), dim3(m.n_blocks), dim3(threads), lds_bytes, st, m, d0, dn,
                      d1, static_cast<double *>(nullptr), static_cast<const double *>(nullptr), hist_row, k, pm_dev, seq,
                      static_cast<const double *>(nullptr));
 }
@@ -1327,29 +1234,6 @@ void launch_peer_selftest(const PeerMap &pm, hipStream_t st, const double *own, 
   const int blocks = n == 0 ? 1 : ((n + 255) / 256 < 64 ? (n + 255) / 256 : 64);
   hipLaunchKernelGGL(peer_selftest_kernel, dim3(blocks), dim3(256), 0, st, pm, own, out, seq);
 }
-
-#ifdef SAA_DIAGNOSTICS
-// Diagnostic build only (tools/ablate.py): the step kernel with one phase removed; results are garbage.
-void launch_fused_step_ablated(int variant, const DeviceMesh &m, int threads, int lds_bytes, hipStream_t st,
-                               const double *d0, const double *dn, double *d1, const StepConsts &k, double *dbg) {
-  double *none = nullptr;
-  const double *cnone = nullptr;
-  // SAA_ABLATE_EXTRA_LDS (bytes): unused dynamic LDS on top of the image, e.g. to leave room for ONE workgroup per CU only
-  if (const char *env = getenv("SAA_ABLATE_EXTRA_LDS")) lds_bytes = std::min(160 * 1024, lds_bytes + atoi(env));
-#define SAA_ABL(V)                                                                                         \
-  case V:                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_step_kernel<false, V>),                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);                      \
-    hipLaunchKernelGGL((fused_step_kernel<false, V>), dim3(V == 9 ? 8 * m.n_blocks : m.n_blocks), dim3(threads), lds_bytes, st, m, d0, \
-                       dn, d1, none, cnone, V == 8 ? dbg : none, k, static_cast<const PeerMap *>(nullptr), 0u, cnone); \
-    break;
-  switch (variant) {
-    SAA_ABL(0) SAA_ABL(1) SAA_ABL(2) SAA_ABL(3) SAA_ABL(4) SAA_ABL(5) SAA_ABL(6) SAA_ABL(7) SAA_ABL(8) SAA_ABL(9) SAA_ABL(10)
-    default: break;
-  }
-#undef SAA_ABL
-}
-#endif  // SAA_DIAGNOSTICS
 
 int persistent_lds_bytes(int max_local, int max_owned, int max_items, int max_halo) {
   const long long bytes = 8ll * (persist_off_dn(max_local, max_owned) + 3 * max_owned + 2 * max_owned) + 8ll * max_items +

@@ -29,8 +29,8 @@ def test_library_exports_every_declared_symbol():
     for name in _declared_functions():
         assert hasattr(lib, name), name
     assert _lib.load().saa_abi_version() == _lib.ABI_VERSION
-    # the product library exports the header's entry points and nothing else of ours: diagnostics (ablated kernels,
-    # stamps, saa_debug_*) live in the separate libsaa_hip_diag.so the tools build for themselves
+    # the product library exports the header's entry points and nothing else of ours: diagnostics (experiment
+    # switches, saa_debug_*) live in the separate libsaa_hip_diag.so the tools build for themselves
     import subprocess
 
     syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout

@@ -570,6 +570,65 @@ def test_deterministic_mode_is_bit_reproducible_and_equals_the_atomic_path(monke
     det.close()
 
 
+DET_FIXTURE = "det_steps.npz"
+
+
+def _det_fixture_case():
+    """Mesh, plan size and host-side plan statistics of ``golden/det_steps.npz``."""
+    from synchronization_avoiding_algorithms_amd import plan_host_stats
+
+    mesh, _ = _scrambled_mesh(4, seed=11)
+    sol, lay, _, _, _ = _serial_solver(mesh, block_nodes=60)
+    st = plan_host_stats(mesh.points[lay.nodes], lay.cells_local, 60)
+    return sol, lay, st
+
+
+def _det_fixture_run(sol, lay):
+    """Deterministic mode on the fixture's case: K.d of a seeded d, and the state 60 steps after a seeded start."""
+    rng = np.random.default_rng(23)
+    sol.set_deterministic(True)
+    f = sol.internal_force(rng.uniform(-1e-2, 1e-2, size=(sol.n_dof, 1)))
+    d0 = rng.uniform(-1e-5, 1e-5, size=(sol.n_dof, 1))
+    d0[lay.dirichlet_dofs] = 0
+    sol.set_state(d0, d0, 0.1)
+    sol.step(60)
+    return f, sol.get_state()[0]
+
+
+def record_det_steps():
+    """Writes ``golden/det_steps.npz`` from the library that is loaded: run it on the commit BEFORE a change of the
+    deterministic kernels (``python -c "import test_gpu_parity as t; t.record_det_steps()"`` in tests/, on the GPU)."""
+    import os
+
+    from conftest import GOLDEN
+
+    sol, lay, _ = _det_fixture_case()
+    f, d = _det_fixture_run(sol, lay)
+    sol.close()
+    np.savez(os.path.join(GOLDEN, DET_FIXTURE), internal_force=f, state_60=d)
+    print(f"wrote {DET_FIXTURE}: {os.path.getsize(os.path.join(GOLDEN, DET_FIXTURE))} bytes")
+
+
+def test_deterministic_mode_reproduces_the_recorded_bits():
+    """Deterministic mode promises the same bits from every build, not only from every run: K.d and the state after 60
+    steps equal, bit for bit, what the library recorded in ``golden/det_steps.npz`` before ``det_items_kernel`` came to
+    share ``item_forces`` with the atomic kernels.  The plan has paired items, single items and idle slots in blocks with
+    halo nodes (asserted from the host-side statistics, so that a plan change cannot hollow the comparison out)."""
+    sol, lay, st = _det_fixture_case()
+    singles = st["n_elem_copies"] - 2 * st["n_pairs"]
+    idle = st["n_items"] - st["n_pairs"] - singles
+    print(f"det fixture plan: {st['n_blocks']} blocks, {st['n_pairs']} pairs, {singles} singles, {idle} idle, "
+          f"{st['n_halo_total']} halo nodes")
+    assert st["n_blocks"] > 1 and st["n_halo_total"] > 0
+    assert st["n_pairs"] > 0 and singles > 0 and idle > 0
+    want = load_golden(DET_FIXTURE)
+    f, d = _det_fixture_run(sol, lay)
+    sol.close()
+    assert f.shape == want["internal_force"].shape and d.shape == want["state_60"].shape
+    assert np.array_equal(f, want["internal_force"])
+    assert np.array_equal(d, want["state_60"])
+
+
 def _delaunay_mesh(n_points, seed):
     """A genuinely unstructured mesh: Delaunay tetrahedra of random points in a 4 x 1 x 1 box (plus a lattice on the
     clamp plane x = 0), positively oriented, slivers dropped (volume < 2 % of the cube of the longest edge: their

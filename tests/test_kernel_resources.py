@@ -2,6 +2,7 @@
 SIMD (1024-thread workgroups, one per CU, or two 512-thread ones): 128 VGPRs is the ceiling, and a spill of either kind
 or any scratch use is a performance regression that no parity test would notice (27 scalar spills in the
 PEER variant of the resident kernel)."""
+import functools
 import os
 import subprocess
 import sys
@@ -11,11 +12,26 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+@functools.lru_cache(maxsize=None)  # (the product run serves two tests)
+def _kernel_resources(*flags):
+    out =subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), *flags], capture_output=True,
+                         text=True, timeout=600)
+    assert out.returncode == 0, out.stderr
+    return out
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not installed")
+def test_diagnostic_build_compiles_the_product_step_kernels():
+    """-DSAA_DIAGNOSTICS adds switches and entry points on the host side, no kernel: the same kernel names with the same
+    registers, spills, scratch and occupancy as the product build, row for row."""
+    product, diag = _kernel_resources().stdout, _kernel_resources("-DSAA_DIAGNOSTICS").stdout
+    assert len(product.splitlines()) > 6, product
+    assert diag == product
+
+
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not installed")
 def test_step_kernels_fit_their_register_budget_without_spills():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py")], capture_output=True, text=True,
-                         timeout=600)
-    assert out.returncode == 0, out.stderr
+    out = _kernel_resources()
     rows = {}
     for ln in out.stdout.splitlines()[1:]:
         f = ln.split()
@@ -29,8 +45,8 @@ def test_step_kernels_fit_their_register_budget_without_spills():
     # Register counts pinned per variant: twice in round 2 a change OUTSIDE the step loop moved the allocation of the whole
     # kernel and cost 4 % that no test saw.  A deliberate change of the kernels updates this table - together with a fresh
     # A/B measurement (tools/ab.py) of what it did to the step time.
-    pinned = {"fused_step_kernel<false, 0, false>": (118, 80), "fused_step_kernel<true, 0, false>": (100, 43),
-              "fused_step_kernel<false, 0, true>": (116, 86), "persistent_steps_kernel<false, false>": (110, 97),
+    pinned = {"fused_step_kernel<false, false>": (118, 80), "fused_step_kernel<true, false>": (100, 43),
+              "fused_step_kernel<false, true>": (116, 86), "persistent_steps_kernel<false, false>": (110, 97),
               "persistent_steps_kernel<true, false>": (110, 99), "persistent_steps_kernel<false, true>": (122, 105)}
     for name, r in step.items():
         key = name.split("saa::")[-1]

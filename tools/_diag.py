@@ -1,5 +1,5 @@
-"""Tools that need the diagnostic build of the library (-DSAA_DIAGNOSTICS: ablated step kernels, in-kernel stamps,
-saa_debug_* exports) import this module BEFORE the package: it builds ``libsaa_hip_diag.so`` when missing or stale and
+"""Tools that need the diagnostic build of the library (-DSAA_DIAGNOSTICS: experiment switches and the
+saa_debug_* exports; the same step kernels as the product) import this module BEFORE the package: it builds ``libsaa_hip_diag.so`` when missing or stale and
 points SAA_LIB_PATH at it.  The product library never contains any of that."""
 import os
 import sys
