@@ -753,8 +753,10 @@ int saa_operator_stepper_set_dt(saa_operator_stepper *st, double dt_new);
  * and a fixed-order final sum folded into the kernel that needs it, 4 launches per PCG iteration, no floating-point atomics -
  * every result is bitwise repeatable and independent of how a run is split into calls.  The host reads one small status block
  * (iteration count, |r|, guard flag, inversion count) once per Newton iteration and every check_every PCG iterations, and once at
- * the end of the linear material's solve: that step is accepted on the recurrence residual of its PCG, because a residual
- * evaluated afresh has the round-off floor of f_int (eps times the cancellation inside it), which a tight tol lies below.
+ * the end of the linear material's solve: that step is accepted on the recurrence residual of its PCG over the scale at the
+ * solved x (one more residual pass gives it; the solve is repeated from there if the scale has fallen below what the
+ * recurrence residual needs), because a residual evaluated afresh has the round-off floor of f_int (eps times the
+ * cancellation inside it), which a tight tol lies below.
  *
  * saa_operator_shifted_apply: out = K_T(u) v + shift (.) v, 0 on Dirichlet dofs; u, v are masked on input as
  *   saa_operator_tangent_apply masks them, u_dev may be NULL with SAA_MATERIAL_LINEAR.  shift_dev: 3 * n_nodes device doubles, or

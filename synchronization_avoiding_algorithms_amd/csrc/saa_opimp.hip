@@ -22,8 +22,9 @@
 //    p, x_cg = 0, partials of |r|^2, the three scale terms and r . z - f_int is never written as a vector), a one-block final
 //    kernel and the x += dx pass; a step adds the predictor and the finish pass.
 //  * The host reads one status block (kStLen doubles) once per Newton iteration and every check_every PCG iterations (and once
-//    at the end of the linear material's one solve, whose result it takes when the recurrence residual has reached tol: a
-//    residual evaluated afresh has the round-off floor of f_int, which a tight tol lies below).
+//    at the end of the linear material's solve, whose result it takes when the recurrence residual is within tol of the scale
+//    at the solved x, which the next residual pass gives: a residual evaluated afresh has the round-off floor of f_int, which
+//    a tight tol lies below).
 //  * No floating-point atomics: every result is bitwise repeatable and independent of how a run is split into calls.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -681,6 +682,7 @@ hipError_t opimp_step(OpImplicit *st, int32_t nsteps, OpImplicitInfo *info) {
     hipLaunchKernelGGL(opimp_predict_kernel, dim3(nbd), dim3(kThreads), 0, op->stream, n, st->minv, st->d, st->v, dt, st->x);
     SAA_HIP_TRY(hipGetLastError());
     double previous = -1.0;
+    double solved = -1.0;  // linear material: |r_cg| of a solve that reached its target, until the scale at the solved x is known
     int reason = 0;
     for (int32_t newton = 0;; ++newton) {
       SAA_HIP_TRY(force_pass(st, st->x, contrib));
@@ -704,6 +706,12 @@ hipError_t opimp_step(OpImplicit *st, int32_t nsteps, OpImplicitInfo *info) {
       }
       info->residual = ref > 0.0 ? rnorm / ref : rnorm;
       if (rnorm <= goal) break;
+      // the linear system, solved to the tolerance, is the step: a residual evaluated afresh has a round-off floor of its
+      // own, which tol may lie below.  The recurrence residual is held to the scale at the solved x, as every other |r| is.
+      if (solved >= 0.0 && solved <= goal) {
+        info->residual = ref > 0.0 ? solved / ref : solved;
+        break;
+      }
       if (newton >= st->max_newton) {
         reason = 1;
         break;
@@ -720,13 +728,7 @@ hipError_t opimp_step(OpImplicit *st, int32_t nsteps, OpImplicitInfo *info) {
       SAA_HIP_TRY(hipGetLastError());
       previous = rnorm;
       ++info->newton_iterations;
-      // the linear system, solved to the tolerance, is the step: a residual evaluated afresh has a round-off floor of its
-      // own, which tol may lie below
-      if (st->material == 0 && end[kSLive] == 0.0 && end[kSGuard] == 0.0 && end[kSNorm] <= target) {
-        info->residual = end[kSNorm] / ref;
-        info->cg_iterations += static_cast<int64_t>(end[kSIter]);
-        break;
-      }
+      solved = st->material == 0 && end[kSLive] == 0.0 && end[kSGuard] == 0.0 && end[kSNorm] <= target ? end[kSNorm] : -1.0;
     }
     if (reason != 0) {
       info->converged = 0;

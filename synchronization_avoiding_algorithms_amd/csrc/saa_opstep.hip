@@ -139,6 +139,12 @@ __global__ void __launch_bounds__(kThreads) opstep_geometry_kernel(int32_t n_ele
   int32_t v[10];
   double p[10][3];
   bits[e] = load_element10(xyz, cells, free_mask, e, v, p);
+  // coordinates relative to node 0 (sum_a dN_a = 0: J is the same): the products are of the element's size, not of the
+  // mesh's, so a thin element far from the origin keeps the digits of its thin direction
+#pragma unroll
+  for (int a = 9; a >= 0; --a)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[a][c] -= p[0][c];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     double J[3][3], G[3][3];
